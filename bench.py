@@ -16,6 +16,14 @@ Other workloads (not the headline line; used for profiles and DESIGN.md numbers)
                       distinct and 8 ... 77 tokens long, DB = a random 50 000-row subset of the train split
                       (run_lemon.py:121-127), one GPU.  The N = 1 headline line carries a bounded-size run of it
                       (`mscoco`: 8 000 + 500 + 500 samples).
+
+A plain run sets up, warms up, times the steps and prints the line: the headline figure (`value`, `ms_per_step`) and what the
+timed steps themselves recorded (per-launch HIP events of the dominant kernels: `roofline`, `knn`; `exchange` for N > 1).
+Everything that takes runs of its own -- the stage split and encoder fraction of an extra step, the text-dedup and all-fp32
+GEMM steps, the CPU baselines with their AUROC / parity checks, per-tower GEMM passes and the `mscoco` / `knn_1m` objects of
+the N = 1 line -- runs only with --full (the --no_* switches then leave parts of it out).
+  --dump-outputs DIR  after the timed steps, the records of the last one (what run_hot_path hands its caller) as
+                      DIR/<name>.npy, float32 / float64; large outputs as a fixed seeded row sample, at most 64 MB in all.
 """
 import argparse
 import json
@@ -170,6 +178,11 @@ def parse():
                          "(the line then carries `exchange`)")
     ap.add_argument("--knn_cpu_queries", type=int, default=10000,
                     help="query slice of the kNN workload's CPU baseline (BASELINE.md 3.5: 10 000 queries against the full DB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: stage split, encoder fraction, text-dedup and all-fp32 GEMM "
+                         "steps, CPU baselines and AUROC checks, per-tower GEMM passes, the `mscoco` and `knn_1m` objects")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64; large ones as a fixed seeded row sample)")
     args = ap.parse_args()
     if args.arch is None:
         args.arch = "vit-b-16" if args.workload == "mscoco" else "vit-b-32"
@@ -308,6 +321,44 @@ def max_over_ranks(x, world, dev):
     t = torch.tensor([x], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ROWS_1D = 1 << 16       # per-sample vectors: every row up to this many, else a fixed seeded sample of rows
+DUMP_ROWS_ND = 1024          # matrices (embeddings, neighbour lists): every row up to this many, else a fixed seeded sample
+
+
+def dump_rows(n, m):
+    """Rows written of an n-row output: None (all of them) when n <= m, else m sorted rows drawn with a fixed seed -- the same
+    rows for the same n on every run and every build."""
+    if n <= m:
+        return None
+    return np.sort(np.random.default_rng(12345).choice(n, m, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: tensor} as out_dir/<name>.npy -- floating outputs as float32 (float64 where they are float64),
+    indices as float64 (exact).  An output with more rows than DUMP_ROWS_1D / DUMP_ROWS_ND is written at the rows dump_rows
+    draws, and those row numbers as out_dir/<name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if not torch.is_tensor(t):
+            t = torch.as_tensor(np.asarray(t))
+        t = t.detach()
+        files = {name: t}
+        rows = dump_rows(t.shape[0], DUMP_ROWS_1D if t.dim() == 1 else DUMP_ROWS_ND) if t.dim() else None
+        if rows is not None:
+            files[name] = t[torch.from_numpy(rows).to(t.device)]
+            files[name + "_rows"] = torch.from_numpy(rows)
+        for fname, v in files.items():
+            v = v.double() if (v.dtype == torch.float64 or not v.is_floating_point()) else v.float()
+            a = v.cpu().numpy()
+            total += a.nbytes
+            if total > DUMP_MAX_BYTES:
+                raise SystemExit(f"bench.py: --dump-outputs would exceed {DUMP_MAX_BYTES >> 20} MB at {fname}")
+            np.save(os.path.join(out_dir, fname + ".npy"), a)
+    return total
 
 
 # ------------------------------------------------------------------------------ workloads
@@ -463,12 +514,15 @@ def bench_cifar(args, world, rank, dev):
     for db_ in timed:
         collect(db_)
     del timed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {f"{name}_{key}": v for name, rec in recs.items() for key, v in rec.items()})
 
-    # one extra, untimed step with host syncs between stages: embed vs kNN+score wall split
-    timers = {}
-    recs, db = step(timers=timers)
-    for k_ in stage:
-        stage[k_] += timers[k_]
+    if args.full:
+        # one extra, untimed step with host syncs between stages: embed vs kNN+score wall split
+        timers = {}
+        recs, db = step(timers=timers)
+        for k_ in stage:
+            stage[k_] += timers[k_]
     info = db.index_img.last_search_info()
     # text tokens actually run: the longest prompt rounded up to the tower's bucket (clip.TextTower.seq_len_for)
     f_img, f_txt = encoder_flops(cfg, n_tokens_text=model.text.seq_len_for(int(data["train"]["ids"].argmax(-1).max().item())))
@@ -529,18 +583,20 @@ def bench_cifar(args, world, rank, dev):
         # the folded LayerNorm's mean bound -> LayerNorm kernels).  Non-zero = the step did part of its encoder work twice.
         "fallback_batches": fb1[0] - fb0[0], "fold_fallback_batches": fb1[1] - fb0[1],
         "fallback_rows": fb1[2] - fb0[2], "fold_fallback_rows": fb1[3] - fb0[3],
-        "stages_s": {k_: v for k_, v in stage.items()},
-        "encoder": {"bound": "mfma", "unit": "TFLOP/s", "gemm_mode": gemm_mode,
-                    # fp32-equivalent peak of the mode: the 16-bit matrix peak divided by the products one fp32 product costs
-                    "peak": {"f32": PEAK_F32_MFMA_TFLOPS, "bf16x6": PEAK_BF16_MFMA_TFLOPS / 6, "f16x3": PEAK_BF16_MFMA_TFLOPS / 3}[gemm_mode],
-                    "achieved": (f_img + f_txt) * n_scored / max(stage["embed_s"], 1e-9) / 1e12,
-                    "frac": (f_img + f_txt) * n_scored / max(stage["embed_s"], 1e-9) / 1e12
-                            / {"f32": PEAK_F32_MFMA_TFLOPS, "bf16x6": PEAK_BF16_MFMA_TFLOPS / 6, "f16x3": PEAK_BF16_MFMA_TFLOPS / 3}[gemm_mode],
-                    "note": "algorithmic forward FLOPs (img+txt) of the fp32 model / embed stage wall time (preprocess, LayerNorm, attention and split passes included), against the fp32-equivalent matrix peak of the GEMM mode; "
-                            "in gemm_mode 'bf16x6' / 'f16x3' the four GEMMs of every block run as split GEMMs on the 16-bit matrix "
-                            "cores (fp32-equivalent results; 16-bit MFMA peak / 6 = 416.7, / 3 = 833 TFLOP/s-equivalent), the patch "
-                            "embedding with them; the two final projections (1 000 pooled rows per micro-batch) stay fp32 GEMMs"},
     }
+    if args.full:
+        line["stages_s"] = {k_: v for k_, v in stage.items()}
+        line["encoder"] = {
+            "bound": "mfma", "unit": "TFLOP/s", "gemm_mode": gemm_mode,
+            # fp32-equivalent peak of the mode: the 16-bit matrix peak divided by the products one fp32 product costs
+            "peak": {"f32": PEAK_F32_MFMA_TFLOPS, "bf16x6": PEAK_BF16_MFMA_TFLOPS / 6, "f16x3": PEAK_BF16_MFMA_TFLOPS / 3}[gemm_mode],
+            "achieved": (f_img + f_txt) * n_scored / max(stage["embed_s"], 1e-9) / 1e12,
+            "frac": (f_img + f_txt) * n_scored / max(stage["embed_s"], 1e-9) / 1e12
+                    / {"f32": PEAK_F32_MFMA_TFLOPS, "bf16x6": PEAK_BF16_MFMA_TFLOPS / 6, "f16x3": PEAK_BF16_MFMA_TFLOPS / 3}[gemm_mode],
+            "note": "algorithmic forward FLOPs (img+txt) of the fp32 model / embed stage wall time (preprocess, LayerNorm, attention and split passes included), against the fp32-equivalent matrix peak of the GEMM mode; "
+                    "in gemm_mode 'bf16x6' / 'f16x3' the four GEMMs of every block run as split GEMMs on the 16-bit matrix "
+                    "cores (fp32-equivalent results; 16-bit MFMA peak / 6 = 416.7, / 3 = 833 TFLOP/s-equivalent), the patch "
+                    "embedding with them; the two final projections (1 000 pooled rows per micro-batch) stay fp32 GEMMs"}
     if coco:
         H_, W_ = (int(v) for v in args.image_hw.lower().split("x"))
         line["metric"] = "label-error scores/sec (embed+kNN), mscoco-shaped captions noise=0.4"
@@ -556,6 +612,7 @@ def bench_cifar(args, world, rank, dev):
         line["config"]["length_bucketing"] = bool(emb.length_bucketing)
         line["config"]["text_tokens_run_per_caption"] = text_tokens_per_caption
         line["config"]["text_tokens_mean_caption"] = float(np.mean(np.concatenate([data[n_]["caption_tokens"] for n_ in data])))
+    if coco and args.full:
         line["encoder"]["text_flops_note"] = ("text FLOPs = the tokens the tower ran (captions sorted by length, a micro-batch runs its longest caption's "
                                               "8-token bucket); padded to 77 tokens as upstream the same captions cost "
                                               f"{f_txt_padded / 1e9:.2f} GFLOP each instead of {f_txt / 1e9:.2f}")
@@ -575,7 +632,7 @@ def bench_cifar(args, world, rank, dev):
                 by_tower[tname] = {"launches": gpt["launches"], "avg_launch_ms": gpt["kernel_ms"] / gpt["launches"], "achieved": tf_,
                                    "frac": tf_ / PEAK_BF16_MFMA_TFLOPS}
         line["gemm_by_tower"] = by_tower
-    if world == 1 and not args.text_dedup and not args.no_f32_gemm_check and not coco:
+    if args.full and world == 1 and not args.text_dedup and not args.no_f32_gemm_check and not coco:
         # what `python -m lemon_amd.run_lemon` does by default (cli_common: --no_text_dedup turns it off): every DISTINCT prompt is
         # embedded once and gathered -- 100 prompts instead of 50 000 on this workload.  One extra step, an untimed region of its
         # own; NOT the headline (which encodes every sample's prompt, as upstream does, run_lemon.py:140-161,207-233)
@@ -589,7 +646,7 @@ def bench_cifar(args, world, rank, dev):
             "max_abs_val_score_diff_vs_headline": float((recs_d["val"]["score"] - recs["val"]["score"]).abs().max().item()),
             "note": "run_lemon's default text path (distinct prompts embedded once); reported beside the headline, never as `value`"}
         del recs_d, emb_d
-    if gemm_mode != "f32" and world == 1 and not args.no_f32_gemm_check and not coco:
+    if args.full and gemm_mode != "f32" and world == 1 and not args.no_f32_gemm_check and not coco:
         # the same step once more, untimed region of its own, with every GEMM on the fp32 matrix cores (LEMON_GEMM=f32): what
         # the split GEMMs buy, and the score difference between the two modes on the val split
         os.environ["LEMON_GEMM"] = "f32"
@@ -651,31 +708,32 @@ def bench_cifar(args, world, rank, dev):
             line["roofline"] = knn
     if world > 1 or args.rccl_world1:
         line["exchange"] = exchange_report(glog, world, info, db, args.steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if coco:
             cores = __import__("oracle.oracle", fromlist=["usable_cores"]).usable_cores()
             line["cpu_baseline"] = cpu_reference_style(args, cfg, data, recs, db, n_scored, cores, 0.0)
             line["cpu_baseline"]["preprocess_note"] = "image decoding / resizing not timed on the CPU side (generous to the CPU)"
         else:
             line["cpu_baseline"], line["auroc_check"] = cpu_baseline_cifar(args, cfg, model, data, recs, db, n_scored)
-    if world == 1 and not coco and not (args.no_knn_1m and args.no_mscoco):
+    if args.full and world == 1 and not coco and not (args.no_knn_1m and args.no_mscoco):
         del recs, db, data, emb, model
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_mscoco and not coco:
+    if args.full and world == 1 and not args.no_mscoco and not coco:
         # BASELINE configs[2] (caption-shaped: every text row distinct, 8 ... 77 tokens, ViT-B/16, DB = random subset) at a BOUNDED
         # size inside the same driver run; the full-size line is committed under profiles/ (tools/gpu_profile.sh)
         ma = argparse.Namespace(**{**vars(args), "workload": "mscoco", "arch": "vit-b-16", "n_train": 8000, "n_val": 500, "n_test": 500,
                                    "db_limit": 5000, "encoder_batch": 664, "steps": 2, "warmup": 1, "no_cpu_baseline": True,
                                    "no_knn_1m": True, "no_mscoco": True, "no_f32_gemm_check": True, "text_dedup": False, "algo": "auto",
-                                   "input": "u8", "knn_k": 50, "dist_type": "cosine", "rccl_world1": False})
+                                   "input": "u8", "knn_k": 50, "dist_type": "cosine", "rccl_world1": False,
+                                   "dump_outputs": None})
         m1 = bench_cifar(ma, world, rank, dev)
         line["mscoco"] = {k_: m1[k_] for k_ in ("metric", "value", "unit", "ms_per_step", "config", "stages_s", "encoder", "roofline",
                                                   "gemm_by_tower", "fallback_rows", "fold_fallback_rows") if k_ in m1}
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_knn_1m and not coco:
+    if args.full and world == 1 and not args.no_knn_1m and not coco:
         # north_star's second target inside the same driver-timed run: the 1M x 768, k=50 self-join on this GPU
         ka = argparse.Namespace(**{**vars(args), "knn_n": 1_000_000, "knn_d": 768, "knn_k": 50, "steps": 1, "warmup": 0,
-                                   "algo": "auto", "dist_type": "cosine"})
+                                   "algo": "auto", "dist_type": "cosine", "dump_outputs": None})
         k1 = bench_knn(ka, world, rank, dev)
         line["knn_1m"] = {"workload": k1["config"]["workload"], "ms": k1["ms_per_step"], "scores_per_s": k1["value"],
                           "roofline": k1["roofline"], "cpu_baseline": k1.get("cpu_baseline")}
@@ -935,14 +993,14 @@ def bench_knn(args, world, rank, dev):
             db.index_img.set_profiling(True); db.index_txt.set_profiling(True)
         rec = db.neighbors(img, txt, k, drop_self=True, return_indices=False)
         s = ops.lemon_score(rec, FIXED_HPARAMS)
-        return db, s
+        return db, rec, s
 
     for _ in range(args.warmup):
         step(False)
     barrier_sync(world, dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        db, s = step(True)       # events recorded on the launch stream, read after the region
+        db, rec, s = step(True)  # events recorded on the launch stream, read after the region
         torch.cuda.synchronize(dev)
         for ix in (db.index_img, db.index_txt):
             p = ix.profile_read()
@@ -950,12 +1008,14 @@ def bench_knn(args, world, rank, dev):
                 prof[k_] += p[k_]
     barrier_sync(world, dev)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(rec, score=s))
     info = db.index_img.last_search_info()
     sec = prof["kernel_ms"] / 1e3
     f32 = info["algo"] == _lib.ALGO_F32_MFMA
     peak = PEAK_F32_MFMA_TFLOPS if f32 else PEAK_BF16_MFMA_TFLOPS
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_knn(args, db, img, txt, s, k)
     line = {
         "metric": "label-error scores/sec (kNN+score only), synthetic embeddings", "value": n * args.steps / elapsed,

@@ -1,10 +1,10 @@
 #!/bin/bash
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
-timeout -k 10 900 python -m pytest tests/test_gpu_rccl.py tests/test_gpu_encoder.py tests/test_gpu_parity.py -x -q -m gpu > gpurun_out/r4_t2.log 2>&1; tail -15 gpurun_out/r4_t2.log
-timeout -k 10 600 python bench.py > gpurun_out/r4_bench1.json 2> gpurun_out/r4_bench1.err; tail -3 gpurun_out/r4_bench1.err
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R; export OUT=${OUT:-$R/build/r4_check1}; mkdir -p $OUT
+timeout -k 10 900 python -m pytest tests/test_gpu_rccl.py tests/test_gpu_encoder.py tests/test_gpu_parity.py -x -q -m gpu > $OUT/r4_t2.log 2>&1 || { tail -15 $OUT/r4_t2.log; exit 1; }; tail -15 $OUT/r4_t2.log
+timeout -k 10 600 python bench.py --full > $OUT/r4_bench1.json 2> $OUT/r4_bench1.err || { tail -3 $OUT/r4_bench1.err; exit 2; }
 python - <<'PY'
-import json
-d = json.load(open("gpurun_out/r4_bench1.json"))
+import json, os
+d = json.load(open(os.path.join(os.environ["OUT"], "r4_bench1.json")))
 print(d["value"], d["ms_per_step"], d["dtype"])
 print(json.dumps(d["roofline"])[:900])
 print(json.dumps(d["cpu_baseline"])[:2500])
