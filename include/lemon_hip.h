@@ -111,6 +111,23 @@ int lemon_preprocess_u8_f16x3t(const uint8_t *img_dev, int64_t batch, int in_h, 
                                const int32_t *bnd_h_dev, int ks_h, const int32_t *kk_v_dev, const int32_t *bnd_v_dev,
                                int ks_v, int out_size, int max_rows_per_block, int rows_per_block,
                                const float *mean3_host, const float *std3_host, int patch, uint16_t *outt_dev, void *stream);
+/* generic_transform for a RAGGED batch: images of different (H, W), as the file datasets deliver them (the reference decodes and
+ * transforms them one by one in 8 forked DataLoader workers: run_lemon.py:129-131,199-201, lib/datasets/dataloader.py:167-198,
+ * transform lib/datasets/utils.py:163-170).  Same arithmetic and bits as lemon_preprocess_u8 per image.
+ * data_dev: packed uint8 HWC images, data_bytes long.  aux_dev (int64): [batch, 4] descriptors (byte offset into data_dev, H, W, plan index),
+ * then [batch + 1] first horizontal-pass block of each image (h_blocks = the last entry), [batch + 1] first vertical-pass
+ * block (v_blocks = the last entry), [batch] byte offset of each image's horizontally resampled rows in work_dev.
+ * plans_dev (int32): 16 per distinct input shape: H, W, offsets into taps_dev of kk_h, bnd_h, kk_v, bnd_v (the CROPPED PIL
+ * tables of lemon_preprocess_u8), ks_h, ks_v, R (output rows per vertical block, R (2 + ks_v) <= 4096), vertical blocks,
+ * first input row of the crop window, its input row count, horizontal blocks (16 input rows each), 3 unused.
+ * work_dev: >= sum over images of rows x out_size x 3 bytes (4-byte aligned).  Output at batch position i: operand == 0 ->
+ * out_dev float32 NCHW (patch == 0) or patch-major (patch > 0) as lemon_preprocess_u8; operand != 0 -> the tile-major fp16
+ * split operand of lemon_preprocess_u8_f16x3t (rows = batch (out_size/patch)^2 padded to 128).  Any input size whose vertical
+ * window has at most 4 094 taps (R = 1): a short side up to ~1 020 x out_size (229 000 px for 224).  An image whose plan does
+ * not match its descriptor, or that does not lie inside data_bytes, is not read and its outputs are NaN. */
+int lemon_preprocess_ragged(const uint8_t *data_dev, int64_t data_bytes, int64_t batch, const int64_t *aux_dev, int64_t h_blocks, int64_t v_blocks,
+                            const int32_t *plans_dev, const int32_t *taps_dev, uint8_t *work_dev, int out_size,
+                            const float *mean3_host, const float *std3_host, int patch, int operand, void *out_dev, void *stream);
 
 /* Multi-head self-attention of the CLIP towers, fused to one pass: the attention inside
  * encode_image / encode_text (lib/models/downstream_models.py:37-41 -> HF CLIPAttention; in-tree twin

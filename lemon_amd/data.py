@@ -43,6 +43,9 @@ def generic_transform(img, size=224):
     return (x - mean) / std
 
 
+_GENERIC_TRANSFORM = generic_transform
+
+
 # ------------------------------------------------------------------------------ preprocessing on the GPU
 PIL_PRECISION_BITS = 22      # Pillow Resample.c: 32 - 8 - 2
 
@@ -63,31 +66,49 @@ def pil_bicubic_tables(in_size, out_size):
     """Pillow's precompute_coeffs + normalize_coeffs_8bpc for BICUBIC (Resample.c), restated: for every
     output index the first input index, the tap count and the 22-bit fixed-point taps.  in == out -> the
     identity table (Pillow skips the pass; tap 1<<22 reproduces the pixel exactly)."""
+    return pil_bicubic_rows(in_size, out_size, 0, out_size)
+
+
+def pil_bicubic_rows(in_size, out_size, lo, hi):
+    """Rows [lo, hi) of pil_bicubic_tables(in_size, out_size), computed for those output indices only (a 2 x 300 image resizes
+    to a width of 33 600 before generic_transform's crop keeps 224 of them)."""
     if in_size == out_size:
-        kk = np.full((out_size, 1), 1 << PIL_PRECISION_BITS, np.int32)
-        bounds = np.stack([np.arange(out_size), np.ones(out_size, np.int64)], 1).astype(np.int32)
+        kk = np.full((hi - lo, 1), 1 << PIL_PRECISION_BITS, np.int32)
+        bounds = np.stack([np.arange(lo, hi), np.ones(hi - lo, np.int64)], 1).astype(np.int32)
         return kk, bounds
+    # the scalar recipe of pil_bicubic_tables, vectorised over output indices: every value is computed by the same float64
+    # operations in the same order (the weight sum runs over taps in order; the zero weights past a window add exactly 0.0)
     scale = filterscale = in_size / out_size
     if filterscale < 1.0:
         filterscale = 1.0
     support = 2.0 * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
-    kk = np.zeros((out_size, ksize), np.int32)
-    bounds = np.zeros((out_size, 2), np.int32)
     ss = 1.0 / filterscale
-    for xx in range(out_size):
-        center = (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
-        ww = 0.0
-        for v in w:
-            ww += v
-        for x in range(xmax):
-            v = w[x] / ww if ww != 0.0 else w[x]
-            kk[xx, x] = int(-0.5 + v * (1 << PIL_PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PIL_PRECISION_BITS))
-        bounds[xx] = (xmin, xmax)
+    center = (np.arange(lo, hi, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size) - xmin
+    t = np.arange(ksize)
+    x = np.abs(((t[None, :] + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
+    a_ = -0.5                                                   # Pillow's bicubic_filter
+    w = np.where(x < 1.0, ((a_ + 2.0) * x - (a_ + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a_, 0.0))
+    w = np.where(t[None, :] < xmax[:, None], w, 0.0)
+    ww = np.zeros(hi - lo)
+    for j in range(ksize):
+        ww = ww + w[:, j]
+    v = np.where(ww[:, None] != 0.0, w / np.where(ww != 0.0, ww, 1.0)[:, None], w)
+    f = v * (1 << PIL_PRECISION_BITS)
+    kk = np.trunc(np.where(v < 0, -0.5 + f, 0.5 + f)).astype(np.int32)
+    bounds = np.stack([xmin, xmax], 1).astype(np.int32)
     return kk, bounds
+
+
+def resize_geometry(h, w, size):
+    """generic_transform's resized size (nh, nw) and crop origin (top, left) for an h x w image."""
+    if (w <= h and w != size) or (h <= w and h != size):
+        nw, nh = (size, int(size * h / w)) if w <= h else (int(size * w / h), size)
+    else:
+        nw, nh = w, h
+    return nh, nw, int(round((nh - size) / 2.0)), int(round((nw - size) / 2.0))
 
 
 @functools.lru_cache(maxsize=16)
@@ -168,12 +189,149 @@ def gpu_transform_batch(images_u8, size=224, patch=0, operand=False):
     return out
 
 
+# ------------------------------------------------------------------------------ ragged batches (file datasets)
+RAGGED_HROWS = 16             # input rows per horizontal-pass workgroup (preprocess.hip)
+RAGGED_PLAN_INTS = 16         # int32 per plan (preprocess.hip: PL_*)
+_VTAB_MAX_INTS = 4096        # ints of a vertical-pass workgroup's window table (preprocess.hip: RAGGED_VTAB_INTS)
+
+
+@functools.lru_cache(maxsize=4096)
+def ragged_plan(h, w, size):
+    """The resize plan of one input shape for lemon_preprocess_ragged: the cropped PIL tap tables (only the `size` kept rows /
+    columns are computed) and the block geometry -> (int32 header [RAGGED_PLAN_INTS] with offsets relative to the plan's own
+    taps, int32 taps [kk_h | bnd_h | kk_v | bnd_v])."""
+    nh, nw, top, left = resize_geometry(h, w, size)
+    if nw < size or nh < size:
+        raise ValueError(f"image {h}x{w} resizes to {nh}x{nw}, smaller than the {size}x{size} crop")
+    kk_h, b_h = pil_bicubic_rows(w, nw, left, left + size)
+    kk_v, b_v = pil_bicubic_rows(h, nh, top, top + size)
+    ks_h, ks_v = kk_h.shape[1], kk_v.shape[1]
+    R = min(16, _VTAB_MAX_INTS // (2 + ks_v))
+    if R < 1:
+        raise ValueError(f"image {h}x{w}: {ks_v} vertical taps per output row exceed the kernel's window table")
+    vmin = int(b_v[:, 0].min())
+    rows = int((b_v[:, 0] + b_v[:, 1]).max()) - vmin
+    parts = [kk_h.ravel(), b_h.ravel(), kk_v.ravel(), b_v.ravel()]
+    offs = np.cumsum([0] + [len(a) for a in parts])
+    hdr = np.zeros(RAGGED_PLAN_INTS, np.int32)
+    hdr[:13] = (h, w, offs[0], offs[1], offs[2], offs[3], ks_h, ks_v, R, (size + R - 1) // R, vmin, rows,
+                (rows + RAGGED_HROWS - 1) // RAGGED_HROWS)
+    return hdr, np.concatenate(parts).astype(np.int32)
+
+
+class RaggedPlans:
+    """The distinct input shapes of a ragged batch and, per output size, their plans on the device (built once, shared by
+    every sub-batch)."""
+
+    def __init__(self, shapes):
+        self.shapes = list(shapes)          # plan index -> (H, W)
+        self._dev = {}
+
+    def tables(self, size, device):
+        key = (size, str(device))
+        if key not in self._dev:
+            hdrs, taps, base = [], [], 0
+            for h, w in self.shapes:
+                hdr, t = ragged_plan(h, w, size)
+                hdr = hdr.copy()
+                hdr[2:6] += base
+                hdrs.append(hdr); taps.append(t); base += len(t)
+            hdr = np.stack(hdrs) if hdrs else np.zeros((0, RAGGED_PLAN_INTS), np.int32)
+            taps = np.concatenate(taps) if taps else np.zeros(1, np.int32)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
+            self._dev[key] = (hdr, up(hdr), up(taps))
+        return self._dev[key]
+
+
+class RaggedImages:
+    """A batch of uint8 HWC images of different sizes on the device: `data` one packed uint8 buffer, `desc` (host int64
+    [n, 4]: byte offset, H, W, plan index) and the batch's RaggedPlans.  len(), contiguous slices and index tensors select
+    sub-batches: a subset of descriptors over the same buffer, nothing is repacked."""
+    dtype = torch.uint8
+
+    def __init__(self, data, desc, plans):
+        self.data, self.desc, self.plans = data, np.asarray(desc, np.int64).reshape(-1, 4), plans
+        self.device, self.is_cuda = data.device, data.is_cuda
+
+    @classmethod
+    def from_arrays(cls, arrays, device):
+        """Pack a list of uint8 HWC numpy arrays (any sizes) into one device batch."""
+        shapes, desc, off = {}, [], 0
+        for a in arrays:
+            h, w = a.shape[:2]
+            desc.append((off, h, w, shapes.setdefault((h, w), len(shapes))))
+            off += a.nbytes
+        buf = torch.empty(max(off, 1), dtype=torch.uint8).pin_memory()
+        flat = buf.numpy()
+        for (o, h, w, _), a in zip(desc, arrays):
+            flat[o:o + a.nbytes] = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+        return cls(buf.to(device, non_blocking=True), np.array(desc, np.int64), RaggedPlans(shapes))
+
+    def __len__(self):
+        return len(self.desc)
+
+    @property
+    def shape(self):
+        return (len(self),)
+
+    def __getitem__(self, sel):
+        if isinstance(sel, torch.Tensor):
+            sel = sel.cpu().numpy()
+        return RaggedImages(self.data, self.desc[sel], self.plans)
+
+    def to(self, device, non_blocking=False):
+        assert torch.device(device) == self.device or (torch.device(device).type == "cuda" and torch.device(device).index is None)
+        return self
+
+    def image(self, i):
+        """Image i as a uint8 [H, W, 3] device tensor (a view of the packed buffer)."""
+        o, h, w, _ = (int(v) for v in self.desc[i])
+        return self.data[o:o + h * w * 3].view(h, w, 3)
+
+
+def gpu_transform_ragged(images, size=224, patch=0, operand=False):
+    """generic_transform of a RaggedImages batch in one lemon_preprocess_ragged call (two launches): float32 [B,3,size,size],
+    patch-major [B, (size/P)^2, 3 P^2] with patch=P, or with operand=True a PatchOperand -- row i = image i of the batch, the
+    same bits as gpu_transform_batch on each image (and as the PIL + torch pipeline)."""
+    import ctypes
+    from . import _lib
+    from .ops import ptr, stream_ptr
+    assert isinstance(images, RaggedImages) and images.is_cuda
+    dev = images.device
+    B = len(images)
+    hdr, plans_dev, taps_dev = images.plans.tables(size, dev)
+    desc = images.desc
+    ph = hdr[desc[:, 3]] if B else np.zeros((0, RAGGED_PLAN_INTS), np.int32)
+    rows = ph[:, 11].astype(np.int64)
+    hpre = np.concatenate([[0], np.cumsum(ph[:, 12], dtype=np.int64)])
+    vpre = np.concatenate([[0], np.cumsum(ph[:, 9], dtype=np.int64)])
+    ioff = np.concatenate([[0], np.cumsum(rows * 3 * size)])
+    aux = torch.from_numpy(np.concatenate([desc.ravel(), hpre, vpre, ioff[:-1]]).astype(np.int64)).pin_memory()
+    aux = aux.to(dev, non_blocking=True)
+    work = torch.empty((max(int(ioff[-1]), 4),), dtype=torch.uint8, device=dev)
+    mean = (ctypes.c_float * 3)(*[float(np.float32(v)) for v in ds.CLIP_MEAN])
+    std = (ctypes.c_float * 3)(*[float(np.float32(v)) for v in ds.CLIP_STD])
+    if operand:
+        assert patch_operand_supported(patch, size)
+        nP, K = (size // patch) ** 2, 3 * patch * patch
+        out = torch.empty(((B * nP + 127) // 128 * 128 * K * 2,), dtype=torch.float16, device=dev)
+    else:
+        out = torch.empty((B, 3, size, size) if not patch else (B, (size // patch) ** 2, 3 * patch * patch),
+                          dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lemon_preprocess_ragged(ptr(images.data), images.data.numel(), B, ptr(aux), int(hpre[-1]), int(vpre[-1]), ptr(plans_dev),
+                                                       ptr(taps_dev), ptr(work), size, mean, std, int(patch), int(bool(operand)),
+                                                       ptr(out), stream_ptr(dev)), "lemon_preprocess_ragged")
+    return PatchOperand(out, B, nP, K) if operand else out
+
+
 class ImageLabelSet:
     """(x, clean, noisy) triples like NoisyCombinedDataset / CaptioningDataset.  `images` is one of
       * uint8 [N,H,W,3] in memory (CIFAR pickles, `pixels.npy`): generic_transform runs on the GPU per batch;
       * float32 [N,...] in memory: pixel tensors that are ALREADY what the model consumes (a preprocessed cache);
         passed through unchanged;
-      * a list of file paths: PIL decode + generic_transform in a thread pool.
+      * a list of file paths: with a CUDA device, decoded by worker processes and transformed on the GPU as RaggedImages
+        batches (lemon_amd/loader.py); otherwise (or with LEMON_DECODE_WORKERS=0) PIL decode + generic_transform in a thread pool.
     Labels are ints (class datasets) or strings (captions)."""
 
     def __init__(self, images, clean, noisy, image_size=224, workers=8):
@@ -214,6 +372,20 @@ class ImageLabelSet:
                 u8 = torch.from_numpy(np.ascontiguousarray(self.images[sl])).to(device, non_blocking=True)
                 yield gpu_transform_batch(u8, self.image_size), self.clean[sl], self.noisy[sl]
             return
+        if device is not None and torch.device(device).type == "cuda" and isinstance(self.images, list) \
+                and generic_transform is _GENERIC_TRANSFORM:
+            # image files: decoded by a pool of worker processes ahead of the consumer, copied as uint8, and transformed on
+            # the GPU as a ragged batch (lemon_amd/loader.py); LEMON_DECODE_WORKERS=0 keeps the thread path below, and so
+            # does a transform other than generic_transform installed in this module (the GPU kernel computes that one only)
+            from . import loader
+            world = 1
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                world = torch.distributed.get_world_size()
+            workers = loader.default_workers(world)
+            if workers > 0:
+                for s, e, imgs in loader.ragged_batches(self.images, batch_size, lo, hi, device, workers=workers):
+                    yield imgs, self.clean[s:e], self.noisy[s:e]
+                return
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             for s in range(lo, hi, batch_size):
                 idx = range(s, min(hi, s + batch_size))

@@ -206,24 +206,30 @@ class Embedder:
 
     @torch.no_grad()
     def embed_images(self, pixel_values):
-        """pixel_values: float [n,3,S,S] already preprocessed, or uint8 [n,H,W,3] raw images -- then
-        generic_transform runs on the GPU per micro-batch (lemon_preprocess_u8, lib/datasets/utils.py:159-170)."""
-        raw = pixel_values.dtype == torch.uint8
+        """pixel_values: float [n,3,S,S] already preprocessed, uint8 [n,H,W,3] raw images, or a data.RaggedImages batch (raw
+        images of different sizes) -- then generic_transform runs on the GPU per micro-batch (lemon_preprocess_u8 /
+        lemon_preprocess_ragged, lib/datasets/utils.py:159-170)."""
+        from .data import RaggedImages
+        ragged = isinstance(pixel_values, RaggedImages)
+        raw = ragged or pixel_values.dtype == torch.uint8
         if raw:
-            from .data import gpu_transform_batch, patch_operand_supported
+            from .data import gpu_transform_batch, gpu_transform_ragged, patch_operand_supported
 
         def one(sel):
-            px = pixel_values[sel if isinstance(sel, slice) else sel.to(pixel_values.device)].to(self.device, non_blocking=True)
+            if ragged:                          # images of different sizes (file datasets): a subset of its descriptors
+                px = pixel_values[sel]
+            else:
+                px = pixel_values[sel if isinstance(sel, slice) else sel.to(pixel_values.device)].to(self.device, non_blocking=True)
             if raw:
                 # f16x3 with the hand-written GEMM: the transform writes the patch-embedding GEMM's operand itself
                 cfg = self.model.cfg
                 operand = (ops.gemm_mode() == "f16x3" and ops.mlp_mode() != "lib" and patch_operand_supported(cfg.patch_size, cfg.image_size)
                            and cfg.vision.width % 256 == 0 and hasattr(self.model, "vision")
                            and os.environ.get("LEMON_PATCH_OPERAND", "1") != "0")          # (=0: A/B knob, the fp32 patch rows + split pass)
-                px = gpu_transform_batch(px, cfg.image_size, patch=cfg.patch_size, operand=operand)
+                px = (gpu_transform_ragged if ragged else gpu_transform_batch)(px, cfg.image_size, patch=cfg.patch_size, operand=operand)
             return self.model.encode_image(px)
 
-        e = self._run_batches(pixel_values.shape[0], self.batch_size, one)
+        e = self._run_batches(len(pixel_values), self.batch_size, one)
         if e is None:
             e = torch.empty((0, self.model.cfg.embed_dim), device=self.device)
         return ops.normalize_vectors(self._note(e)) if e.shape[0] else e              # :164 / :233
