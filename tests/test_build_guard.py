@@ -49,6 +49,15 @@ def _kernel_meta(src):
     return meta
 
 
+# mangled-name fragments of the hand-written GEMM's instantiations (k_gemm_f16x3t<EPI>: 32x32x16; k_gemm_f16x3t16<EPI, FOLD, EMIT,
+# LEAN>: 16x16x32; EPI 0 fp32, 1 SiLU, 2 GELU operand) checked by the two parametrisations below; every instantiation in the code
+# object must be matched by one fragment of each list (test_every_gemm_instantiation_is_guarded)
+_GEMM_CLEAN = ["k_gemm_f16x3tILi0E", "k_gemm_f16x3tILi1E", "k_gemm_f16x3tILi2E",
+               "k_gemm_f16x3t16ILi0E", "k_gemm_f16x3t16ILi1E", "k_gemm_f16x3t16ILi2E"]
+_GEMM_ASM = ["k_gemm_f16x3tILi0E", "k_gemm_f16x3tILi1E", "k_gemm_f16x3tILi2E",
+             "k_gemm_f16x3t16ILi0E", "k_gemm_f16x3t16ILi1E", "k_gemm_f16x3t16ILi2E"]
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src,must_be_clean", [
     # (mangled-name fragments of the PRODUCTION instantiations: PROF = false)
@@ -60,7 +69,7 @@ def _kernel_meta(src):
                       "k_scan_f16_qs4ILi12ELi16ELb0E", "k_scan_f16_qs4ILi8ELi0ELb0E", "k_scan_f16_qs4ILi8ELi0ELb1E"]),
     # the hand-written GEMM (asm LDS-DMA / ds_read / MFMA with pinned accumulators: two workgroups per CU need <= 256 registers)
     # and the attention kernels (three waves per SIMD)
-    ("gemm_f16x3.hip", ["k_gemm_f16x3tILi0E", "k_gemm_f16x3tILi1E"]),
+    ("gemm_f16x3.hip", _GEMM_CLEAN),
     ("attention.hip", ["k_attention_hd64_shortILi2ELi2ELb1E", "k_attention_hd64_shortILi1ELi2ELb1E", "k_attention_hd64_shortILi2ELi0ELb1E",
                        "k_attention_hd64ILi2ELb1E", "k_attention_hd64ILi0ELb1E"]),
 ])
@@ -186,7 +195,7 @@ def _check_asm_discipline(name, lines):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src,kernels", [
-    ("gemm_f16x3.hip", ["k_gemm_f16x3tILi0E", "k_gemm_f16x3tILi1E", "k_gemm_f16x3t16ILi0E", "k_gemm_f16x3t16ILi1E"]),
+    ("gemm_f16x3.hip", _GEMM_ASM),
     ("knn_bf16.hip", ["k_scan_bf16_qs2ILi12ELi16ELb0ELb0ELb1E", "k_scan_bf16_qs2ILi12ELi20ELb1ELb0ELb1E", "k_scan_bf16_qs2ILi8ELi0ELb0ELb0ELb1E",
                       "k_scan_f16_qs4ILi12ELi16ELb0E", "k_scan_f16_qs4ILi8ELi0ELb0E", "k_scan_f16_qs4ILi8ELi0ELb1E"]),
     ("knn_f32.hip", ["k_scan_f32ILb0ELb0ELb0E", "k_scan_f32ILb1ELb0ELb0E"]),
@@ -200,6 +209,31 @@ def test_hand_issued_asm_is_left_alone_by_the_compiler(src, kernels):
         for n in hits:
             problems = _check_asm_discipline(n, bodies[n])
             assert not problems, "\n".join(problems[:10])
+
+
+def _unguarded_gemm_kernels(names, clean, asm):
+    """GEMM kernels among `names` that a fragment of `clean` or of `asm` does not match, as [(name, list)]"""
+    out = []
+    for n in names:
+        for label, frags in (("spill/register", clean), ("hand-issued asm", asm)):
+            if not any(f in n for f in frags):
+                out.append((n, label))
+    return out
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_every_gemm_instantiation_is_guarded():
+    # a new instantiation of the hand-written GEMM (another epilogue, another chain form) gets both checks above or fails here
+    names = [n for n in _kernel_bodies(_kernel_asm("gemm_f16x3.hip")) if "k_gemm_f16x3t" in n]
+    assert len(names) >= 13, sorted(names)           # 3 x k_gemm_f16x3t, 10 x k_gemm_f16x3t16 (the dispatcher's 13 launches)
+    missing = _unguarded_gemm_kernels(names, _GEMM_CLEAN, _GEMM_ASM)
+    assert not missing, missing
+    # (and the check itself notices a dropped fragment)
+    for frags in (_GEMM_CLEAN, _GEMM_ASM):
+        for f in frags:
+            fewer = [g for g in frags if g != f]
+            assert _unguarded_gemm_kernels(names, fewer if frags is _GEMM_CLEAN else _GEMM_CLEAN,
+                                           fewer if frags is _GEMM_ASM else _GEMM_ASM), f
 
 
 # ---- k_attention_hd64_f16 (64 < L <= 288): built for four waves per SIMD (two workgroups of seven waves per CU) ----------------
