@@ -438,6 +438,48 @@ int lemon_grid_f1(const float *d1_dev, const float *D_n_dev, const float *dists_
                   const uint8_t *y_dev, int64_t n, int k, const double *hp_dev, int G, double xtol, int maxfun,
                   double *scores_ws_dev, double *f1_dev, double *thres_dev, void *stream);
 
+/* ---- k-means on caption embeddings + the deep-kNN label score ------------------------ */
+
+/* FaissKMeans.predict = index.search(x, 1) (lib/datasets/clustering.py:38-41) and the assignment step of faiss.Kmeans.train
+ * (:28-36): nearest centroid of every row of x_dev [n, d] among c_dev [C, d], squared L2 with the exact key of the numeric
+ * contract max(0, fma(-2, <x,c>, |x|^2 + |c|^2)) (chain norms), ties to the lower index.  assign_dev int32 [n] and dist_dev
+ * float32 [n] (may be NULL) equal, bit for bit, lemon_index_search(IndexFlatL2 over c, x, 1).  A dedicated kernel: no
+ * workspace, no candidate lists.  1 <= C <= 16384; d a multiple of 4, 4 <= d <= 1024; x_dev and c_dev 16-byte aligned;
+ * anything else is refused with LEMON_E_INVALID, never truncated. */
+int lemon_kmeans_assign(const float *x_dev, int64_t n, int d, const float *c_dev, int C, int32_t *assign_dev, float *dist_dev,
+                        void *stream);
+/* The centroid step of faiss.Kmeans.train (clustering.py:28-36): c_dev [C, d] (in/out) = mean of the points assigned to each
+ * cluster, summed in float64 in ascending point order (stable radix sort of the ids by cluster, then one serial sum per
+ * cluster and coordinate: no floating-point atomics, the same bits on every run and every launch geometry) and rounded
+ * once to float32; a cluster without points keeps its centroid.  count_dev int64 [C]; obj_dev double [1] (may be NULL) =
+ * sum of dist_dev in float64, in a fixed order.  ws_dev: lemon_kmeans_workspace_bytes(n, d, C) bytes, 256-byte aligned. */
+int lemon_kmeans_update(const float *x_dev, int64_t n, int d, const int32_t *assign_dev, const float *dist_dev, int C,
+                        float *c_dev, int64_t *count_dev, double *obj_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+/* Empty clusters (faiss split_clusters inside Kmeans.train): for each empty cluster in ascending index the currently largest
+ * cluster (ties: lower index) is the donor; the empty one takes a copy of the donor's centroid with even coordinates
+ * x (1 + eps) and odd ones x (1 - eps), the donor the other way round, eps = 1/1024; the empty one gets floor(count / 2) of
+ * the donor's count.  faiss draws the donor at random in proportion to its size: its RNG stream is not pinned here (faiss is
+ * not available to this project's tests), the rule is otherwise faiss's. */
+int lemon_kmeans_split(float *c_dev, int d, int C, int64_t *count_dev, void *stream);
+/* faiss.Kmeans(d, C, niter).train(x) for ONE redo from the initial centroids in c_dev (clustering.py:28-36): enqueues niter x
+ * (assign, update, split) and a last assign against the final centroids, with no host synchronisation.  obj_hist_dev double
+ * [niter]: the objective of every iteration; count_dev: the last update's (after its split); assign_dev int32 [n]: the
+ * final assignment.  n >= C.  Early stop on the device: after an iteration that changes no assignment and leaves no
+ * cluster empty (a fixed point: the remaining iterations could not change anything) a device flag makes the kernels of the
+ * remaining iterations return at once and obj_hist is filled with the last value; the host never reads the flag.
+ * LEMON_KMEANS_EARLY_STOP=0 runs every iteration in full (same result). */
+int lemon_kmeans_train(const float *x_dev, int64_t n, int d, int C, int niter, float *c_dev, double *obj_hist_dev,
+                       int64_t *count_dev, int32_t *assign_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+int64_t lemon_kmeans_workspace_bytes(int64_t n, int d, int C); /* < 0: LEMON_E_* */
+/* The deep-kNN score of lib/baselines/run_deepknn.py on the labels lib/datasets/dataloader.py:190-192 hands out: the
+ * fraction of a query's k kept neighbours whose label differs from the query's.  I_dev int64 [nq, kk] from
+ * lemon_index_search; drop_self as in lemon_neighbors (run_lemon.py:257-263: searched kk >= k + 1, drop result[0] where
+ * in_db_dev[i] != 0 (NULL = all), else result[-1]); db_label_dev int32 [ntotal]; a slot with I outside [0, ntotal) counts as
+ * disagreeing, a query label of -1 matches nothing.  out_dev float32 [nq]. */
+int lemon_knn_label_disagreement(const int64_t *I_dev, int64_t nq, int kk, int k, int drop_self, const uint8_t *in_db_dev,
+                                 const int32_t *db_label_dev, int64_t ntotal, const int32_t *q_label_dev, float *out_dev,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

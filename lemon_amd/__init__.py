@@ -18,4 +18,10 @@ def __getattr__(name):
     if name == "LemonDB":
         from . import neighbors
         return neighbors.LemonDB
+    if name in ("KMeans", "cluster_caption_text"):
+        from . import kmeans
+        return getattr(kmeans, name)
+    if name in ("deep_knn_scores", "count_knn_distribution"):
+        from . import baselines
+        return getattr(baselines, name)
     raise AttributeError(name)

@@ -22,6 +22,8 @@ EXPORTS = [
     "lemon_index_ntotal", "lemon_index_dim", "lemon_index_data", "lemon_index_search",
     "lemon_index_set_algo", "lemon_index_set_query_dedup", "lemon_index_last_search_info", "lemon_index_set_profiling",
     "lemon_index_profile_read", "lemon_debug_scan_plan", "lemon_neighbors", "lemon_discrepancy", "lemon_score", "lemon_grid_f1",
+    "lemon_kmeans_assign", "lemon_kmeans_update", "lemon_kmeans_split", "lemon_kmeans_train", "lemon_kmeans_workspace_bytes",
+    "lemon_knn_label_disagreement",
 ]
 
 
@@ -117,6 +119,13 @@ def load():
     lib.lemon_neighbors.argtypes = [vp, vp, vp, vp, vp, c_i64, c_int, c_int, vp, c_int, vp, vp] + [vp] * 9 + [vp]
     lib.lemon_discrepancy.argtypes = [c_int, vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp]
     lib.lemon_score.argtypes = [vp] * 7 + [c_i64, c_int, ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp]
+    lib.lemon_kmeans_assign.argtypes = [vp, c_i64, c_int, vp, c_int, vp, vp, vp]
+    lib.lemon_kmeans_update.argtypes = [vp, c_i64, c_int, vp, vp, c_int, vp, vp, vp, vp, c_i64, vp]
+    lib.lemon_kmeans_split.argtypes = [vp, c_int, c_int, vp, vp]
+    lib.lemon_kmeans_train.argtypes = [vp, c_i64, c_int, c_int, c_int, vp, vp, vp, vp, vp, c_i64, vp]
+    lib.lemon_kmeans_workspace_bytes.argtypes = [c_i64, c_int, c_int]
+    lib.lemon_kmeans_workspace_bytes.restype = c_i64
+    lib.lemon_knn_label_disagreement.argtypes = [vp, c_i64, c_int, c_int, c_int, vp, vp, c_i64, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -3,6 +3,7 @@
   discrepancy_scores   lib/baselines/discrepancy_baseline.py:164-242   dis_x | dis_y | div_x | div_y
   clip_similarity      lib/baselines/run_clip_sim.py:235-248 (DistanceEvaluator.our_metric)
   cos_distance_topk / count_knn_distribution   lib/metrics/utils.py:198-233 (in-tree brute-force kNN)
+  deep_knn_scores      lib/baselines/run_deepknn.py:255-261 (--dist_method deep_knn) on class or cluster labels
 """
 import ctypes
 
@@ -81,3 +82,34 @@ def count_knn_distribution(num_classes, min_similarity, feat_cord, label, k, nor
     if norm == "l1":
         return cnt / cnt.sum(1, keepdim=True)
     raise NameError("Undefined norm")
+
+
+def label_disagreement(I, k, db_label, q_label, drop_self=False, in_db=None):
+    """Fraction of the k kept neighbours of every query whose label differs from the query's (float32 [nq], CUDA).
+    I: int64 [nq, kk] neighbour lists (kk >= k + drop_self); with drop_self the self-exclusion of run_lemon.py:257-263
+    (drop result[0] where in_db, else result[-1]); I = -1 slots disagree, a query label of -1 matches nothing."""
+    assert torch.is_tensor(I) and I.is_cuda and I.dim() == 2 and I.dtype == torch.int64
+    I = I.contiguous()
+    dev = I.device
+    db = torch.as_tensor(db_label).to(device=dev, dtype=torch.int32).contiguous()
+    ql = torch.as_tensor(q_label).to(device=dev, dtype=torch.int32).contiguous()
+    assert ql.shape[0] == I.shape[0]
+    mask = None
+    if in_db is not None:
+        mask = torch.as_tensor(in_db).to(device=dev, dtype=torch.uint8).contiguous()
+        assert mask.shape[0] == I.shape[0]
+    out = torch.empty(I.shape[0], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lemon_knn_label_disagreement(ptr(I), I.shape[0], I.shape[1], int(k), int(bool(drop_self)), ptr(mask),
+                                                            ptr(db), db.shape[0], ptr(ql), ptr(out), stream_ptr(dev)),
+                   "lemon_knn_label_disagreement")
+    return out
+
+
+def deep_knn_scores(index_img, q_img, q_label, db_label, k, is_train=False, in_db=None):
+    """Deep-kNN baseline score (the --dist_method deep_knn of lib/baselines/run_deepknn.py:255-261): search the image index
+    for k (+ 1 on the train split, whose queries are in the DB) neighbours and return the fraction whose (noisy) label
+    differs from the query's.  Labels are class ids or the cluster ids of get_dataset(..., cluster_text=True)."""
+    q = dev_f32(q_img, "q_img")
+    _, I = index_img.search(q, int(k) + int(bool(is_train)))
+    return label_disagreement(I, k, db_label, q_label, drop_self=is_train, in_db=in_db)

@@ -440,9 +440,64 @@ def _read_cifar(root, name, train=True):
     return np.ascontiguousarray(x.reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)), y
 
 
-def get_dataset(name, data_seed, percent_flips=0.40, flip_type="real", data_root="./data", image_size=224):
+CAPTION_DATASETS = ("mscoco", "flickr30k", "mimiccxr_caption", "mmimdb", "cc3m")
+
+
+def cluster_text_labels(sets, embedder, tokenizer, n_clusters=100, random_state=42, **kmeans_kwargs):
+    """lib/datasets/utils.py:312-316,396-400 + lib/datasets/dataloader.py:190-192: k-means on the embeddings of the NOISY
+    train sentences, val / test predicted with the same model; every caption set becomes a label set with
+    noisy = cluster id of the given sentence and clean = -1 where the sentence was swapped (is_mislabel), else the same id
+    (int64).  Returns (km, (train, val, test)); the new sets keep the sentences as `.noisy_text` / `.clean_text`."""
+    from . import kmeans
+    train = sets[0]
+    km, labels = kmeans.cluster_caption_text(embedder, tokenizer, list(train.noisy), n_clusters=n_clusters,
+                                             random_state=random_state, **kmeans_kwargs)
+    out = []
+    for i, part in enumerate(sets):
+        if i > 0:
+            labels = km.predict(list(part.noisy)).squeeze(1).cpu().numpy() if len(part) else np.zeros(0, np.int64)
+        noisy = np.asarray(labels, dtype=np.int64)
+        mis = np.array([c != t for c, t in zip(part.clean, part.noisy)], dtype=bool)
+        new = ImageLabelSet(part.images, np.where(mis, np.int64(-1), noisy), noisy, part.image_size, part.workers)
+        new.noisy_text, new.clean_text, new.cluster_model = list(part.noisy), list(part.clean), km
+        out.append(new)
+    return km, tuple(out)
+
+
+def _cluster_tools(cluster_kwargs):
+    """(embedder, tokenizer, n_clusters, extra KMeans arguments) from get_dataset's cluster_kwargs: either a ready
+    (`embedder`, `tokenizer`) pair or (`clip_model`, `clip_path`[, `bpe_path`, `device`, `encoder_batch`]), from which both are
+    built the way lemon_amd/cli_common.py builds them."""
+    kw = dict(cluster_kwargs or {})
+    n_clusters = int(kw.pop("n_clusters", 100))
+    embedder, tokenizer = kw.pop("embedder", None), kw.pop("tokenizer", None)
+    clip_model, clip_path = kw.pop("clip_model", "huggingface_clip"), kw.pop("clip_path", None)
+    bpe_path, device, batch = kw.pop("bpe_path", None), kw.pop("device", None), int(kw.pop("encoder_batch", 512))
+    if (embedder is None) != (tokenizer is None):
+        raise ValueError("cluster_kwargs: give both `embedder` and `tokenizer`, or `clip_model` and `clip_path`")
+    if embedder is None:
+        if clip_path is None:
+            raise ValueError("cluster_kwargs needs (`embedder`, `tokenizer`) or (`clip_model`, `clip_path`) to embed the captions")
+        from . import clip as clip_mod
+        from .pipeline import Embedder
+        model, tokenizer = clip_mod.algorithm_class_from_scratch(clip_model, text_base_name=clip_path, img_base=None,
+                                                                 return_tokenizer=True, bpe_path=bpe_path)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        embedder = Embedder(model, device, batch_size=batch, text_dedup=True)
+    return embedder, tokenizer, n_clusters, kw
+
+
+def get_dataset(name, data_seed, percent_flips=0.40, flip_type="real", data_root="./data", image_size=224,
+                cluster_text=False, cluster_kwargs=None):
     """train/val/test ImageLabelSets for the datasets run_lemon.py accepts (run_lemon.py:37-38,105-106).
-    `data_root='synthetic:N'` builds an N-sample synthetic class dataset with the named dataset's labels."""
+    `data_root='synthetic:N'` builds an N-sample synthetic class dataset with the named dataset's labels.
+    `cluster_text=True` (lib/datasets/utils.py:312-316,352,396-400) turns the captions of a caption dataset into cluster
+    labels (cluster_text_labels; `cluster_kwargs`: n_clusters and the text tower, see _cluster_tools); class datasets ignore
+    it, as upstream."""
+    if cluster_text and name in CAPTION_DATASETS:
+        sets = get_dataset(name, data_seed, percent_flips, flip_type, data_root, image_size)
+        embedder, tokenizer, n_clusters, extra = _cluster_tools(cluster_kwargs)
+        return cluster_text_labels(sets, embedder, tokenizer, n_clusters=n_clusters, **extra)[1]
     if name in ("cifar10", "cifar100"):
         C = ds.class_num_dict[name]
         if str(data_root).startswith("synthetic"):
