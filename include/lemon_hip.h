@@ -134,7 +134,10 @@ int lemon_preprocess_ragged(const uint8_t *data_dev, int64_t data_bytes, int64_t
  * lib/models/chexzero_clip.py:191-212 with the causal mask of :348-354 for text).
  * qkv_dev [batch, seq_len, 3, heads, head_dim] float32 = the fused q/k/v projection output;
  * out_dev [batch, seq_len, heads*head_dim] = softmax(q k^T / sqrt(head_dim) [+ causal]) v with heads
- * concatenated, ready for the output projection.  head_dim must be 64, seq_len <= 288.
+ * concatenated, ready for the output projection.  head_dim must be 64, seq_len <= LEMON_ATTENTION_MAX_SEQ.
+ * seq_len <= 288: one workgroup per (batch, head), K and V of the head staged in LDS once.  Beyond 288 (the 577 tokens of
+ * ViT-L/14@336, 1025 at 448 px, long text contexts): the streaming kernels -- query tiles dealt to several workgroups per
+ * (batch, head), the keys passing through LDS in blocks of 128 -- with the same arithmetic per key tile, in every output form.
  * Arithmetic (all lemon_attention_* entry points): by default the two products run as SPLIT products on the fp16 matrix cores
  * -- q, k, v and the probabilities are carried as fp16 pairs (hi = f16(v), lo = the remainder: 22 bits + sign, fp32
  * accumulate; error vs float64 at the level of the all-fp32 form).  RANGE: |q|, |k|, |v| must stay below 65 520, beyond that
@@ -145,7 +148,12 @@ int lemon_preprocess_ragged(const uint8_t *data_dev, int64_t data_bytes, int64_t
  * every thread there. */
 int lemon_attention_f32(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                         int causal, float *out_dev, void *stream);
+#define LEMON_ATTENTION_MAX_SEQ 4096
 int lemon_attention_set_f16(int on);
+/* Sequences LONGER than seq_len go to the streaming kernels, for the calling thread: default 288 (what the one-workgroup
+ * kernels hold), accepted 64 .. 288 (anything else: LEMON_E_INVALID, nothing changes); returns the previous value.  The two
+ * families give the same bits; the switch exists for the test of that and for A/B timing. */
+int lemon_attention_set_stream_min(int seq_len);
 /* The same attention with the result written as the 3-way bf16 split activation operand of lemon_linear_bf16x6 (below):
  * out6_dev [batch*seq_len, 6*heads*64] bf16, 16-byte aligned.  The fp32 result is split at the store, not recomputed. */
 int lemon_attention_split3(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,

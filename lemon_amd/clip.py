@@ -60,6 +60,12 @@ class ClipConfig:
         if name in ("vit-l-14", "vit-large-patch14", "l14"):
             return ClipConfig(embed_dim=768, patch_size=14, vision=TowerConfig(1024, 24, 16, 4096),
                               text=TowerConfig(768, 12, 12, 3072))
+        # beyond 288 tokens per image (577): the streaming attention kernels, same chain of hand-written GEMMs
+        if name in ("vit-l-14-336", "vit-large-patch14-336", "l14-336"):
+            return ClipConfig(embed_dim=768, image_size=336, patch_size=14, vision=TowerConfig(1024, 24, 16, 4096),
+                              text=TowerConfig(768, 12, 12, 3072))
+        if name in ("vit-b-16-384", "vit-base-patch16-384", "b16-384"):
+            return ClipConfig(image_size=384, patch_size=16)
         if name in ("chexzero-scratch-256", "mimic-clip-from-scratch", "scratch-b16-256"):
             # lib/models/chexzero_clip.py:458-470 load_clip(): ViT-B/16 vision, 512-wide text, 768-d, context 256
             return ClipConfig(embed_dim=768, patch_size=16, context_length=256)

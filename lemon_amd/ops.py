@@ -101,7 +101,7 @@ def grid_f1(rec, y, hparams, xtol=1e-8, maxfun=500, return_scores=False):
     return f1.cpu().numpy(), th.cpu().numpy()
 
 
-ATTENTION_MAX_SEQ = 288
+ATTENTION_MAX_SEQ = _lib.ATTENTION_MAX_SEQ    # the header's LEMON_ATTENTION_MAX_SEQ; beyond 288 tokens the streaming kernels
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 _ACT_CODE = {None: ACT_NONE, "silu": ACT_SILU, "gelu": ACT_GELU}      # 'gelu': the exact (erf) GELU of BiomedCLIP's towers
 QUICK_GELU_SCALE = 1.702
