@@ -488,6 +488,48 @@ int lemon_knn_label_disagreement(const int64_t *I_dev, int64_t nq, int kk, int k
                                  const int32_t *db_label_dev, int64_t ntotal, const int32_t *q_label_dev, float *out_dev,
                                  void *stream);
 
+/* ---- baseline JPEG files decoded on the GPU (the reference decodes every file with PIL, `Image.open(p).convert("RGB")`, in its
+ * DataLoader workers: lib/datasets/dataloader.py:167-198, run_lemon.py:129-131,199-201).  The decode is split: the serial
+ * Huffman pass runs on the host (lemon_jpeg_entropy), the data-parallel rest on the device (lemon_jpeg_decode); the pixels are
+ * bit for bit PIL's (libjpeg-turbo: JDCT_ISLOW, fancy upsampling).  The three host functions are also exported by
+ * liblemon_jpeg_host.so, which links no HIP runtime (the decode workers load that one). */
+typedef struct LemonJpegInfo {
+    int32_t status;                   /* 0 = accepted; > 0 = declined, decode with PIL (codes: csrc/jpeg_entropy.hpp) */
+    int32_t width, height, components;
+    int32_t hs, vs;                   /* sampling factors of component 0: 1x1, 2x1 or 2x2 (1x1 with one component) */
+    int32_t mcus_x, mcus_y;
+    int32_t max_abs;                  /* largest |coefficient * quantiser| of the image */
+    int32_t exact_blocks;             /* blocks whose envelope check needed the exact form */
+    int64_t blocks;                   /* 8x8 blocks of all components over the MCU-padded grid */
+    int64_t record_bytes;             /* 384 + 128 * blocks */
+    uint16_t quant[3][64];            /* per component, natural order */
+} LemonJpegInfo;
+/* Header pass of lib/datasets/dataloader.py:167-198's decode: geometry, quantisers and record size of the file in data[0, n), or
+ * the reason it is declined (progressive, arithmetic, 12-bit, several scans, 16-bit tables, other sampling, 4 components, Adobe
+ * marker, non-YCbCr component ids, a zero dimension, anything malformed).  Returns info->status.  Host only, no GPU. */
+int lemon_jpeg_info(const uint8_t *data, int64_t n, LemonJpegInfo *info);
+/* The whole host pass for the same call site (lib/datasets/dataloader.py:167-198; run_lemon.py:129-131,199-201 run it in 8
+ * workers): header + Huffman decoding into `record` (info->record_bytes <= record_cap bytes: uint16 quant[3][64], then int16
+ * coefficient blocks, component 0 [block row][block col][64] natural order, then components 1 and 2).  Also declines a bit
+ * stream that ends early or runs past its last MCU and an image with a block outside the arithmetic envelope
+ * (csrc/jpeg_entropy.hpp).  Every read of `data` is bounds-checked.  Returns info->status.  Host only, no GPU. */
+int lemon_jpeg_entropy(const uint8_t *data, int64_t n, uint8_t *record, int64_t record_cap, LemonJpegInfo *info);
+/* The device arithmetic of lemon_jpeg_decode run on the host (csrc/jpeg_core.hpp): record -> uint8 RGB [h, w, 3].  Test support
+ * for lib/datasets/dataloader.py:167-198's pixels on a machine without a GPU; no product path calls it.  0 = ok. */
+int lemon_jpeg_reconstruct_host(const uint8_t *record, int64_t record_bytes, int32_t w, int32_t h, int32_t ncomp, int32_t hs,
+                                int32_t vs, uint8_t *rgb);
+/* Device half for a batch (lib/datasets/dataloader.py:167-198 per image; run_lemon.py:129-131,199-201 per loader batch):
+ * rec_dev holds the records (rec_bytes long, 16-byte aligned).  aux_dev (int64): [batch, 8] descriptors (record offset -- a
+ * multiple of 16 --, output offset, width, height, components, hs, vs, work offset -- a multiple of 16), then [batch + 1] first
+ * inverse-DCT workgroup of each image (32 blocks per workgroup; idct_blocks = the last entry), then [batch + 1] first colour
+ * workgroup (1024 pixel slots of 4 pixels per row-quad, i.e. ceil(h * ceil(w / 4) / 256) per image; rgb_blocks = the last entry).
+ * Two launches: dequantise + inverse DCT into uint8 component planes in work_dev (64 bytes per block), then chroma upsampling,
+ * YCbCr -> RGB and the crop to w x h, written as packed uint8 RGB [h, w, 3] at each image's output offset in out_dev -- the
+ * layout lemon_preprocess_ragged reads.  An image whose record, planes or pixels would not lie inside rec_bytes / work_bytes /
+ * out_bytes is neither read nor written. */
+int lemon_jpeg_decode(const uint8_t *rec_dev, int64_t rec_bytes, int64_t batch, const int64_t *aux_dev, int64_t idct_blocks,
+                      int64_t rgb_blocks, uint8_t *work_dev, int64_t work_bytes, uint8_t *out_dev, int64_t out_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ EXPORTS = [
     "lemon_index_set_algo", "lemon_index_set_query_dedup", "lemon_index_last_search_info", "lemon_index_set_profiling",
     "lemon_index_profile_read", "lemon_debug_scan_plan", "lemon_neighbors", "lemon_discrepancy", "lemon_score", "lemon_grid_f1",
     "lemon_kmeans_assign", "lemon_kmeans_update", "lemon_kmeans_split", "lemon_kmeans_train", "lemon_kmeans_workspace_bytes",
-    "lemon_knn_label_disagreement",
+    "lemon_knn_label_disagreement", "lemon_jpeg_info", "lemon_jpeg_entropy", "lemon_jpeg_reconstruct_host", "lemon_jpeg_decode",
 ]
 
 
@@ -128,6 +128,10 @@ def load():
     lib.lemon_kmeans_workspace_bytes.argtypes = [c_i64, c_int, c_int]
     lib.lemon_kmeans_workspace_bytes.restype = c_i64
     lib.lemon_knn_label_disagreement.argtypes = [vp, c_i64, c_int, c_int, c_int, vp, vp, c_i64, vp, vp, vp]
+    lib.lemon_jpeg_info.argtypes = [vp, c_i64, vp]
+    lib.lemon_jpeg_entropy.argtypes = [vp, c_i64, vp, c_i64, vp]
+    lib.lemon_jpeg_reconstruct_host.argtypes = [vp, c_i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp]
+    lib.lemon_jpeg_decode.argtypes = [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp]
     _lib = lib
     return lib
 

@@ -14,9 +14,14 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 SO = os.path.join(HERE, "liblemon_hip.so")
 SOURCES = ["api.hip", "rowwise.hip", "knn_f32.hip", "knn_bf16.hip", "attention.hip", "linear.hip", "preprocess.hip",
-           "gridf1.hip", "dedup.hip", "encoder.hip", "gemm_f16x3.hip", "kmeans.hip"]
-HEADERS = ["common.hpp", "knn_common.hpp", "split3.hpp", "scan_plan.hpp", os.path.join("..", "..", "include", "lemon_hip.h")]
+           "gridf1.hip", "dedup.hip", "encoder.hip", "gemm_f16x3.hip", "kmeans.hip", "jpeg.hip"]
+HEADERS = ["common.hpp", "knn_common.hpp", "split3.hpp", "scan_plan.hpp", "jpeg_core.hpp", "jpeg_entropy.hpp", "jpeg_abi.hpp",
+           os.path.join("..", "..", "include", "lemon_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
+# the JPEG host pass alone, built with the host compiler: no HIP runtime, loaded by the decode workers (decode_worker.py)
+JPEG_HOST_SO = os.path.join(HERE, "liblemon_jpeg_host.so")
+JPEG_HOST_SOURCE = "jpeg_host.cpp"
+JPEG_HOST_HEADERS = ["jpeg_core.hpp", "jpeg_entropy.hpp", "jpeg_abi.hpp", os.path.join("..", "..", "include", "lemon_hip.h")]
 
 
 def _hipcc():
@@ -37,12 +42,37 @@ def _stale(target, deps):
     return any(os.path.getmtime(p) > t for p in deps)
 
 
+def _host_cxx():
+    for cand in (os.environ.get("CXX"), "g++", "c++", "clang++"):
+        path = shutil.which(cand) if cand else None
+        if path:
+            return path
+    raise RuntimeError("no host C++ compiler found: liblemon_jpeg_host.so cannot be built")
+
+
+def _jpeg_host_deps():
+    return [os.path.join(CSRC, s) for s in [JPEG_HOST_SOURCE] + JPEG_HOST_HEADERS]
+
+
+def build_jpeg_host(force=False, verbose=False):
+    if not force and not _stale(JPEG_HOST_SO, _jpeg_host_deps()):
+        return JPEG_HOST_SO
+    cmd = [_host_cxx(), "-O3", "-std=c++17", "-fPIC", "-shared", "-o", JPEG_HOST_SO, os.path.join(CSRC, JPEG_HOST_SOURCE)]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return JPEG_HOST_SO
+
+
 def needs_build():
     deps = [os.path.join(CSRC, s) for s in _sources() + HEADERS]
-    return _stale(SO, deps)
+    return _stale(SO, deps) or _stale(JPEG_HOST_SO, _jpeg_host_deps())
 
 
 def build_hip(force=False, verbose=False, jobs=None):
+    if not force and not needs_build():
+        return SO
+    build_jpeg_host(force, verbose)
     if not force and not needs_build():
         return SO
     hipcc = _hipcc()

@@ -289,6 +289,72 @@ class RaggedImages:
         return self.data[o:o + h * w * 3].view(h, w, 3)
 
 
+def launch_jpeg_decode(data, layout, poison=None):
+    """Enqueue lemon_jpeg_decode on the current stream for a device buffer `data` laid out by a jpeg_host.BatchLayout
+    ([payload with records and aux table | decoded RGB]): the records' pixels appear at their RaggedImages offsets.  `poison`
+    (a byte, for tests) pre-fills the decoded region and the work buffer."""
+    from . import _lib
+    import ctypes
+    from .ops import stream_ptr
+    if not layout.n_jpeg:
+        return
+    assert data.is_cuda and data.dtype == torch.uint8 and data.numel() >= layout.total_bytes
+    dev = data.device
+    with torch.cuda.device(dev):
+        work = torch.empty((layout.work_bytes,), dtype=torch.uint8, device=dev)
+        if poison is not None:
+            work.fill_(poison)
+            data[layout.decoded_off:].fill_(poison)
+        base, vp = data.data_ptr(), ctypes.c_void_p
+        _lib.check(_lib.load().lemon_jpeg_decode(vp(base), layout.payload_bytes, layout.n_jpeg, vp(base + layout.aux_off),
+                                                 layout.idct_blocks, layout.rgb_blocks, vp(work.data_ptr()), work.numel(), vp(base),
+                                                 data.numel(), stream_ptr(dev)), "lemon_jpeg_decode")
+
+
+def decode_jpegs(files, device, fallback=False, poison=None):
+    """Decode JPEG files on the GPU -> RaggedImages of `Image.open(f).convert("RGB")`'s pixels, bit for bit.  `files`: paths or
+    bytes objects.  The Huffman pass runs here on the host (csrc/jpeg_entropy.hpp), everything after it in lemon_jpeg_decode.
+    A file the host pass declines (progressive, CMYK, not a JPEG, corrupt, ...) raises ValueError, or with fallback=True is
+    decoded by PIL (whose own exception a corrupt file then raises).  The result carries `layout` (jpeg_host.BatchLayout)."""
+    import io
+    from PIL import Image
+    from . import jpeg_host
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError("decode_jpegs needs a CUDA/HIP device: there is no CPU path")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    lay, items, off = jpeg_host.BatchLayout(), [], 0
+    for f in files:
+        raw = f if isinstance(f, (bytes, bytearray, memoryview)) else open(f, "rb").read()
+        rec, info = jpeg_host.decode_record(bytes(raw))
+        if rec is None:
+            what = "<bytes>" if raw is f else f
+            if not fallback:
+                raise ValueError(f"{what}: not decodable on the GPU ({jpeg_host.STATUS.get(info.status, info.status)})")
+            px = np.asarray(Image.open(io.BytesIO(raw)).convert("RGB"), dtype=np.uint8)
+            lay.add_pixels(off, px.shape[0], px.shape[1])
+            items.append((off, px.reshape(-1)))
+            off = (off + px.nbytes + 15) & ~15
+        else:
+            lay.add_record(off, rec)
+            items.append((off, rec.data))
+            off = (off + rec.data.nbytes + 15) & ~15
+    aux = lay.finish(off)
+    buf = torch.empty((max(lay.payload_bytes, 1),), dtype=torch.uint8).pin_memory()
+    flat = buf.numpy()
+    for o, a in items:
+        flat[o:o + a.nbytes] = a
+    if aux.size:
+        flat[lay.aux_off:lay.payload_bytes] = aux.view(np.uint8)
+    data = torch.empty((max(lay.total_bytes, buf.numel()),), dtype=torch.uint8, device=device)
+    data[:buf.numel()].copy_(buf, non_blocking=True)
+    launch_jpeg_decode(data, lay, poison)
+    out = RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
+    out.layout = lay
+    return out
+
+
 def gpu_transform_ragged(images, size=224, patch=0, operand=False):
     """generic_transform of a RaggedImages batch in one lemon_preprocess_ragged call (two launches): float32 [B,3,size,size],
     patch-major [B, (size/P)^2, 3 P^2] with patch=P, or with operand=True a PatchOperand -- row i = image i of the batch, the
@@ -331,7 +397,7 @@ class ImageLabelSet:
       * float32 [N,...] in memory: pixel tensors that are ALREADY what the model consumes (a preprocessed cache);
         passed through unchanged;
       * a list of file paths: with a CUDA device, decoded by worker processes and transformed on the GPU as RaggedImages
-        batches (lemon_amd/loader.py); otherwise (or with LEMON_DECODE_WORKERS=0) PIL decode + generic_transform in a thread pool.
+        batches (lemon_amd/loader.py), with LEMON_JPEG=gpu baseline JPEGs with the device half of their decode on the GPU (default pil: all by PIL); otherwise (or with LEMON_DECODE_WORKERS=0) PIL decode + generic_transform in a thread pool.
     Labels are ints (class datasets) or strings (captions)."""
 
     def __init__(self, images, clean, noisy, image_size=224, workers=8):

@@ -2,11 +2,18 @@
 the HIP library, never the GPU) and decodes exactly `Image.open(p).convert("RGB")` -- the reference's loader step
 (lib/datasets/dataloader.py:167-198) without its transform, which runs on the GPU -- into a shared-memory ring of its own.
 
-Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY`), so that not even the lemon_amd package is imported.
+With RECORDS = 1 a file that starts with FF D8 goes through the JPEG host pass instead (jpeg_host.py -> liblemon_jpeg_host.so,
+which links no HIP runtime): its Huffman decoding runs straight into the ring and the ring receives the coefficient record that
+lemon_jpeg_decode turns into the same pixels on the GPU.  A file the host pass declines (progressive, CMYK, corrupt, ...) is
+decoded with PIL exactly as without RECORDS, PIL's own exception for a corrupt file included.
+
+Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS]`), so that not even the lemon_amd package is imported.
 Protocol (pickled frames on stdin / stdout, in order):
   parent -> worker: ("task", seq, path) | ("free", nbytes) | ("stop",)
   worker -> parent: ("hello", pid, torch_imported)
-                    ("ok", seq, offset, h, w, consumed, oversize_path or None) | ("err", seq, path, message)
+                    ("ok", seq, offset, h, w, consumed, oversize_path or None, kind, nbytes, (components, hs, vs) or None)
+                    | ("err", seq, path, message)
+`kind` 0: nbytes = h * w * 3 of RGB pixels; `kind` 1: nbytes of coefficient record.
 The ring is a circular byte buffer of CAPACITY bytes.  An image is written at `offset` once `consumed` bytes (its own plus the
 unused tail skipped when it wraps) are free; the parent returns them with "free" after it has copied the image, in the order
 the results came.  An image larger than the whole ring waits until the ring is empty and goes to a one-off segment
@@ -27,6 +34,10 @@ def main(argv):
     import numpy as np
     from PIL import Image
     shm_path, cap = argv[0], int(argv[1])
+    records = len(argv) > 2 and argv[2] == "1"
+    if records:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import jpeg_host
     inp, out = sys.stdin.buffer, sys.stdout.buffer
     fd = os.open(shm_path, os.O_RDWR)
     ring = mmap.mmap(fd, cap)
@@ -45,6 +56,18 @@ def main(argv):
         else:
             raise SystemExit(0)
 
+    def reserve(n):
+        """(offset, bytes consumed) of n <= cap free contiguous bytes of the ring; waits for the parent to free them."""
+        nonlocal head
+        while True:
+            if used == 0:
+                head = 0
+            if head + n <= cap and used + n <= cap:
+                return head, n
+            if head + n > cap and used + (cap - head) + n <= cap:
+                return 0, (cap - head) + n
+            take(pickle.load(inp))
+
     while True:
         if not tasks:
             try:
@@ -53,6 +76,28 @@ def main(argv):
                 return 0
             continue
         _, seq, path = tasks.popleft()
+        if records:
+            # the host pass, straight into the ring: the record size is known after the frame header.  Nothing is committed
+            # (head, used) until the pass has accepted the file; a declined file falls through to PIL below
+            data = None
+            try:
+                with open(path, "rb") as fh:
+                    data = fh.read()
+            except OSError:
+                pass                    # (PIL below reports it)
+            if data is not None and data[:2] == b"\xff\xd8":
+                head_info = jpeg_host.info(data)
+                n = head_info.record_bytes
+                if head_info.status == 0 and n + 15 <= cap:
+                    off, consumed = reserve(n + 15)         # (the record's int16 blocks start at a multiple of 16)
+                    at = (off + 15) & ~15
+                    full = jpeg_host.entropy(data, view[at:at + n])
+                    if full.status == 0:
+                        head = off + n + 15
+                        used += consumed
+                        _send(out, ("ok", seq, at, full.height, full.width, consumed, None, 1, n, (full.components, full.hs, full.vs)))
+                        continue
+            del data
         try:
             img = np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
         except Exception as e:          # noqa: BLE001  (reported to the parent, which raises naming the path)
@@ -70,22 +115,13 @@ def main(argv):
                 np.frombuffer(m, np.uint8)[:n] = img.reshape(-1)
                 del m
             os.close(bfd)
-            _send(out, ("ok", seq, 0, h, w, 0, big))
+            _send(out, ("ok", seq, 0, h, w, 0, big, 0, n, None))
             continue
-        while True:
-            if used == 0:
-                head = 0
-            if head + n <= cap and used + n <= cap:
-                off, consumed = head, n
-                break
-            if head + n > cap and used + (cap - head) + n <= cap:
-                off, consumed = 0, (cap - head) + n
-                break
-            take(pickle.load(inp))      # wait for the parent to free space
+        off, consumed = reserve(n)
         view[off:off + n] = img.reshape(-1)
         head = off + n
         used += consumed
-        _send(out, ("ok", seq, off, h, w, consumed, None))
+        _send(out, ("ok", seq, off, h, w, consumed, None, 0, n, None))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,136 @@
+"""ctypes binding of liblemon_jpeg_host.so (the JPEG host pass, csrc/jpeg_entropy.hpp) and the batch layout of
+lemon_jpeg_decode (include/lemon_hip.h).  Imports ctypes and numpy only -- never torch, never the HIP library -- because the
+decode workers (decode_worker.py, run by path) import it as a top-level module; the package imports it as lemon_amd.jpeg_host.
+"""
+import ctypes
+import os
+from collections import namedtuple
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+SO_PATH = os.path.join(_HERE, "liblemon_jpeg_host.so")
+IDCT_GROUP = 32          # blocks per inverse-DCT workgroup (csrc/jpeg.hip: JPEG_GROUP)
+RGB_PIXELS = 4           # pixels per lane of the colour kernel (JPEG_PIX), 256 lanes per workgroup
+QUANT_BYTES = 384
+STATUS = {0: "ok", 1: "not a JPEG", 2: "truncated header", 3: "progressive / arithmetic / lossless process", 4: "not 8-bit",
+          5: "not 1 or 3 components", 6: "unsupported sampling factors", 7: "not YCbCr (Adobe marker or component ids)",
+          8: "bad or unsupported table", 9: "not one interleaved scan", 10: "bad Huffman code or coefficient",
+          11: "bit stream ends early or runs past its last MCU", 12: "outside the arithmetic envelope", 13: "record buffer too small",
+          14: "zero dimension", 15: "unexpected marker"}
+
+
+class Info(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32),
+                ("hs", ctypes.c_int32), ("vs", ctypes.c_int32), ("mcus_x", ctypes.c_int32), ("mcus_y", ctypes.c_int32),
+                ("max_abs", ctypes.c_int32), ("exact_blocks", ctypes.c_int32), ("blocks", ctypes.c_int64),
+                ("record_bytes", ctypes.c_int64), ("quant", (ctypes.c_uint16 * 64) * 3)]
+
+
+# a coefficient record of one accepted file: `data` uint8 [record_bytes] (a view; copy it to keep it)
+JpegRecord = namedtuple("JpegRecord", "data w h components hs vs")
+
+_lib = None
+
+
+def load():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO_PATH):
+            raise RuntimeError(f"{SO_PATH} is missing: build it with `python -m lemon_amd.build`")
+        lib = ctypes.CDLL(SO_PATH)
+        vp, c_i64, c_i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+        lib.lemon_jpeg_info.argtypes = [ctypes.c_char_p, c_i64, ctypes.POINTER(Info)]
+        lib.lemon_jpeg_entropy.argtypes = [ctypes.c_char_p, c_i64, vp, c_i64, ctypes.POINTER(Info)]
+        lib.lemon_jpeg_reconstruct_host.argtypes = [vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, vp]
+        _lib = lib
+    return _lib
+
+
+def info(data):
+    """Header pass over the bytes of a file -> Info (status 0: accepted so far, record_bytes known)."""
+    out = Info()
+    load().lemon_jpeg_info(data, len(data), ctypes.byref(out))
+    return out
+
+
+def entropy(data, record):
+    """The host pass over the bytes of a file into `record` (a writable contiguous uint8 numpy array) -> Info."""
+    assert record.dtype == np.uint8 and record.flags.c_contiguous and record.flags.writeable
+    out = Info()
+    load().lemon_jpeg_entropy(data, len(data), record.ctypes.data, record.size, ctypes.byref(out))
+    return out
+
+
+def decode_record(data):
+    """bytes -> (JpegRecord, Info) or (None, Info) when the host pass declines the file."""
+    head = info(data)
+    if head.status != 0:
+        return None, head
+    rec = np.empty(head.record_bytes, np.uint8)
+    full = entropy(data, rec)
+    if full.status != 0:
+        return None, full
+    return JpegRecord(rec, full.width, full.height, full.components, full.hs, full.vs), full
+
+
+def reconstruct(rec):
+    """The device arithmetic on the host (csrc/jpeg_core.hpp): JpegRecord -> uint8 [h, w, 3].  For tests."""
+    out = np.empty((rec.h, rec.w, 3), np.uint8)
+    data = np.ascontiguousarray(rec.data)
+    rc = load().lemon_jpeg_reconstruct_host(data.ctypes.data, data.size, rec.w, rec.h, rec.components, rec.hs, rec.vs, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lemon_jpeg_reconstruct_host: bad record geometry")
+    return out
+
+
+def blocks_of(w, h, components, hs, vs):
+    """8x8 blocks of all components over the MCU-padded grid (csrc/jpeg_core.hpp::jpeg_geometry)."""
+    mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+    return mx * hs * my * vs + (2 * mx * my if components == 3 else 0)
+
+
+def _up(n, a=16):
+    return (n + a - 1) // a * a
+
+
+class BatchLayout:
+    """Layout of one device buffer [payload | aux | decoded RGB] for a chunk of images.  The payload (filled by the caller, `off`
+    bytes so far) holds PIL pixels and coefficient records at 16-byte aligned offsets; finish() appends the int64 aux table of
+    lemon_jpeg_decode to the payload and places every JPEG's pixels after it.  `desc` is the RaggedImages table (byte offset, H,
+    W, plan index) in the order the images were added."""
+
+    def __init__(self):
+        self.shapes, self.desc, self.records = {}, [], []
+
+    def add_pixels(self, off, h, w):
+        self.desc.append([off, h, w, self.shapes.setdefault((h, w), len(self.shapes))])
+
+    def add_record(self, off, rec):
+        self.records.append((len(self.desc), off, rec.w, rec.h, rec.components, rec.hs, rec.vs))
+        self.desc.append([-1, rec.h, rec.w, self.shapes.setdefault((rec.h, rec.w), len(self.shapes))])
+
+    def aux_bytes(self):
+        n = len(self.records)
+        return 8 * (8 * n + 2 * (n + 1)) if n else 0
+
+    def finish(self, off):
+        """`off`: end of the images' payload.  -> the aux table (int64, to be copied to payload offset self.aux_off)."""
+        n = len(self.records)
+        self.aux_off = _up(off)
+        self.payload_bytes = self.aux_off + self.aux_bytes()
+        out, work = _up(self.payload_bytes), 0
+        d8 = np.zeros((n, 8), np.int64)
+        apre, bpre = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        for j, (i, roff, w, h, nc, hs, vs) in enumerate(self.records):
+            nb = blocks_of(w, h, nc, hs, vs)
+            d8[j] = (roff, out, w, h, nc, hs, vs, work)
+            self.desc[i][0] = out
+            apre[j + 1] = apre[j] + -(-nb // IDCT_GROUP)
+            bpre[j + 1] = bpre[j] + -(-(h * -(-w // RGB_PIXELS)) // 256)
+            out = _up(out + h * w * 3)
+            work += nb * 64
+        self.decoded_off = _up(self.payload_bytes)
+        self.total_bytes, self.work_bytes = max(out, 1), max(work, 16)
+        self.idct_blocks, self.rgb_blocks, self.n_jpeg = int(apre[-1]), int(bpre[-1]), n
+        return np.concatenate([d8.ravel(), apre, bpre]) if n else np.zeros(0, np.int64)

@@ -7,6 +7,10 @@ lib/datasets/dataloader.py:167-198).  Here:
   * the parent packs a chunk of decoded images into a pinned buffer and copies it to the device as uint8 on a copy stream;
     the compute stream waits on the copy's event;
   * the GPU does resize, crop, normalise and the patch-operand packing of the ragged batch (data.gpu_transform_ragged).
+  * with device JPEG decoding on (LEMON_JPEG=gpu; the default is pil, see device_jpeg_default) a worker runs only the serial
+    half of a baseline JPEG's decode, the Huffman pass (csrc/jpeg_entropy.hpp), and hands over a coefficient record; the
+    records travel in the same pinned buffer and copy as the PIL pixels of the files it declines, and lemon_jpeg_decode
+    reconstructs bit-identical RGB pixels on the compute stream, in the same device buffer, before the ragged transform.
 The held decoded bytes are bounded by `ring_bytes` (one ring of ring_bytes / workers per worker; an image larger than a whole
 ring is decoded alone, when its worker's ring is empty)."""
 import os
@@ -16,6 +20,8 @@ import sys
 import uuid
 
 import numpy as np
+
+from .jpeg_host import BatchLayout, JpegRecord
 
 _WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_worker.py")
 DEFAULT_RING_BYTES = 1 << 30
@@ -35,6 +41,17 @@ def usable_cpus():
     return max(1, n)
 
 
+def device_jpeg_default():
+    """Whether file batches decode baseline JPEGs on the GPU: LEMON_JPEG=gpu / pil.  Default pil: the end-to-end comparison
+    that would turn it on has not been recorded yet; results are identical either way."""
+    env = os.environ.get("LEMON_JPEG", "").strip().lower()
+    if env == "gpu":
+        return True
+    if env in ("", "pil"):
+        return False
+    raise ValueError(f"LEMON_JPEG={env!r}: expected 'gpu' or 'pil'")
+
+
 def default_workers(world=1):
     """LEMON_DECODE_WORKERS when set (0 = the in-process thread path), else min(8, usable_cpus() // world), at least 1."""
     env = os.environ.get("LEMON_DECODE_WORKERS", "").strip()
@@ -49,11 +66,14 @@ class DecodeError(RuntimeError):
 
 class DecodePool:
     """`workers` decode processes over `paths`; images(lo, hi) yields (i, uint8 [H, W, 3] view of shared memory) in order, each
-    view valid until the next item is requested."""
+    view valid until the next item is requested.  With records=True a baseline JPEG the host pass accepts is yielded as
+    (i, JpegRecord) instead -- its coefficient record, `data` a view of shared memory under the same rule -- and every other
+    file as pixels."""
 
-    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1):
+    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False):
         self.paths = list(paths)
         self.n_workers = default_workers(world) if workers is None else int(workers)
+        self.records = bool(records)
         assert self.n_workers >= 1
         self.cap = max(1 << 20, int(ring_bytes) // self.n_workers)
         self.ring_bytes = self.cap * self.n_workers
@@ -73,7 +93,7 @@ class DecodePool:
                 os.ftruncate(fd, self.cap)
                 self.rings.append(np.frombuffer(mmap.mmap(fd, self.cap), np.uint8))
                 os.close(fd)
-                self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap)], stdin=subprocess.PIPE,
+                self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap), "1" if self.records else "0"], stdin=subprocess.PIPE,
                                                    stdout=subprocess.PIPE, close_fds=True))
             for p in self.procs:
                 msg = self._read(p, "worker start")
@@ -108,9 +128,9 @@ class DecodePool:
             msg = self._read(self.procs[k], self.paths[i])
             if msg[0] == "err":
                 raise DecodeError(f"cannot decode image {msg[2]}: {msg[3]}")
-            _, seq, off, h, w, consumed, big = msg
+            _, seq, off, h, w, consumed, big, kind, n, meta = msg
             assert seq == i, (seq, i)
-            n = h * w * 3
+            assert kind == 1 or n == h * w * 3, (kind, n, h, w)
             if big is not None:
                 import mmap
                 fd = os.open(big, os.O_RDONLY)
@@ -122,7 +142,7 @@ class DecodePool:
                 self.held += consumed
                 self.peak_held = max(self.peak_held, self.held)
             last = (k, consumed, big)
-            yield i, arr.reshape(h, w, 3)
+            yield i, (JpegRecord(arr, w, h, *meta) if kind == 1 else arr.reshape(h, w, 3))
         if last is not None:
             self._release(*last)
 
@@ -170,14 +190,19 @@ class DecodePool:
             pass
 
 
-def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, stats=None, slots=3):
+def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, stats=None, slots=3,
+                   device_jpeg=None):
     """Yield (s, e, RaggedImages of paths[s:e]) over paths[lo:hi] in chunks of `chunk` images, decoded by a DecodePool.
 
     A packing thread copies each chunk's decoded images out of the workers' rings into one of `slots` pinned staging buffers
     while the caller embeds the previous chunk; a buffer is refilled only after its last H2D copy has completed.  The copy runs
     as uint8 on a copy stream, into memory allocated on that stream, and only the current stream waits on the copy's event:
     copies overlap the compute already queued.  `stats` (a dict) collects the copies' timing events and bytes
-    ("h2d": [(start, end, bytes)]) and the packing thread's seconds ("pack_s").  The pool closes (workers exit, segments
+    ("h2d": [(start, end, bytes)]) and the packing thread's seconds ("pack_s").  `device_jpeg` (None: device_jpeg_default()):
+    the workers deliver coefficient records for the JPEGs their host pass accepts; the chunk's records, PIL pixels and the aux
+    table of lemon_jpeg_decode are packed into the same pinned buffer and copied once into a device buffer laid out
+    [copied payload | decoded RGB]; lemon_jpeg_decode runs on the current stream after the copy's event, and the RaggedImages
+    offsets point into the payload (PIL images) or the decoded region (JPEGs).  The pool closes (workers exit, segments
     unlinked) when the generator ends, is closed early or raises."""
     import queue
     import threading
@@ -185,7 +210,9 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
 
     import torch
 
-    from .data import RaggedImages, RaggedPlans
+    from .data import RaggedImages, RaggedPlans, launch_jpeg_decode
+    if device_jpeg is None:
+        device_jpeg = device_jpeg_default()
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -226,30 +253,42 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                 k, buf, ev = slot
                 if ev is not None:
                     ev.synchronize()                 # the buffer's previous H2D copy has completed
-                desc, shapes, off = [], {}, 0
-                for _ in range(s, e):
-                    _, a = next(it)                  # (a view of the worker's ring, valid until the next image is asked for)
-                    t1 = time.perf_counter()
-                    h, w = a.shape[:2]
-                    need = off + a.nbytes
+                lay, off = BatchLayout(), 0
+
+                def room(buf, off, need):
                     if buf is None or buf.numel() < need:
                         size = (max(need * 2, 64 << 20) + 15) & ~15      # a multiple of 16: holds the rounded `off` below
                         grown = torch.empty((size,), dtype=torch.uint8).pin_memory()
                         if buf is not None and off:
                             grown[:off].copy_(buf[:off])
                         buf = grown
-                    np.copyto(buf.numpy()[off:need], a.reshape(-1))
-                    desc.append((off, h, w, shapes.setdefault((h, w), len(shapes))))
+                    return buf
+
+                for _ in range(s, e):
+                    _, a = next(it)                  # (a view of the worker's ring, valid until the next image is asked for)
+                    t1 = time.perf_counter()
+                    src = a.data if isinstance(a, JpegRecord) else a.reshape(-1)
+                    need = off + src.nbytes
+                    buf = room(buf, off, need)
+                    np.copyto(buf.numpy()[off:need], src)
+                    if isinstance(a, JpegRecord):
+                        lay.add_record(off, a)
+                    else:
+                        lay.add_pixels(off, a.shape[0], a.shape[1])
                     off = (need + 15) & ~15
                     if stats is not None:
                         stats["pack_s"] += time.perf_counter() - t1
-                if not put(ready, (s, e, k, buf, off, desc, shapes)):
+                aux = lay.finish(off)
+                if aux.size:
+                    buf = room(buf, off, lay.payload_bytes)
+                    np.copyto(buf.numpy()[lay.aux_off:lay.payload_bytes], aux.view(np.uint8))
+                if not put(ready, (s, e, k, buf, lay)):
                     return
             put(ready, None)
         except BaseException as exc:                 # noqa: BLE001  (re-raised by the consumer)
             put(ready, exc)
 
-    with DecodePool(paths, workers, ring_bytes, world) as pool:
+    with DecodePool(paths, workers, ring_bytes, world, records=device_jpeg) as pool:
         th = threading.Thread(target=pack, args=(pool,), daemon=True)
         th.start()
         try:
@@ -259,16 +298,17 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     break
                 if isinstance(item, BaseException):
                     raise item
-                s, e, k, buf, off, desc, shapes = item
+                s, e, k, buf, lay = item
+                off = lay.payload_bytes
                 n = max(off, 1)
                 cur = torch.cuda.current_stream(device)
                 timed = stats is not None
                 with torch.cuda.stream(copy_stream):
-                    data = torch.empty((n,), dtype=torch.uint8, device=device)
+                    data = torch.empty((max(lay.total_bytes, n),), dtype=torch.uint8, device=device)
                     if timed:
                         t0 = torch.cuda.Event(enable_timing=True)
                         t0.record(copy_stream)
-                    data.copy_(buf[:n], non_blocking=True)
+                    data[:n].copy_(buf[:n], non_blocking=True)
                     ev = torch.cuda.Event(enable_timing=timed)
                     ev.record(copy_stream)
                 data.record_stream(cur)                  # freed only after the compute stream is done with it
@@ -276,7 +316,9 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                 free.put((k, buf, ev))
                 if timed:
                     stats.setdefault("h2d", []).append((t0, ev, off))
-                yield s, e, RaggedImages(data, np.array(desc, np.int64).reshape(-1, 4), RaggedPlans(shapes))
+                    stats["jpeg_images"] = stats.get("jpeg_images", 0) + lay.n_jpeg
+                launch_jpeg_decode(data, lay)            # (on the current stream, after the copy's event; nothing without records)
+                yield s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
         finally:
             stop.set()
             th.join()

@@ -10,6 +10,8 @@ Writes N seeded JPEGs (PIL, quality 90, 4:2:0) per size mix to a temp dir and pr
   warm_ring_images_per_s   from files, timed only after the pool has decoded as far ahead as it may
   pack_images_per_s        the packing thread's copies out of the rings into pinned memory
   threads_path_images_per_s  LEMON_DECODE_WORKERS=0 (in-process PIL decode + CPU transform), first <= 512 images
+  --jpeg gpu|pil           from-files and pool figures with baseline JPEGs decoded on the GPU (the workers run only the Huffman
+                           pass) or by PIL in the workers (LEMON_JPEG); default: the library's default
 Every timed region is bracketed by a device synchronise.  Needs a HIP device.
 
   python tools/file_pipeline_time.py --arch vit-b-16 --n 2048 --out profiles/r6/file_pipeline.jsonl
@@ -31,7 +33,7 @@ MIXES = {
 }
 
 
-def write_jpegs(d, mix, n, seed=0):
+def write_jpegs(d, mix, n, seed=0, reuse=False):
     from PIL import Image
     rng = np.random.default_rng(seed)
     paths = []
@@ -45,6 +47,9 @@ def write_jpegs(d, mix, n, seed=0):
         base = 128 + 90 * np.sin(yy[..., None] / rng.uniform(5, 40) + xx[..., None] / rng.uniform(5, 40) + np.arange(3))
         px = np.clip(base + rng.normal(0, 12, (h, w, 1)), 0, 255).astype(np.uint8)
         p = os.path.join(d, f"{mix}_{i:05d}.jpg")
+        if reuse and os.path.exists(p):          # (the random draws above still advance: file i is the same in every run)
+            paths.append(p)
+            continue
         Image.fromarray(px).save(p, quality=90, subsampling=2)
         paths.append(p)
     return paths
@@ -58,8 +63,13 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--mixes", default="mscoco,cars")
     ap.add_argument("--workers", type=int, default=None)
+    ap.add_argument("--jpeg", choices=("gpu", "pil"), default=None)
+    ap.add_argument("--skip_threads", action="store_true", help="leave out the LEMON_DECODE_WORKERS=0 figure")
+    ap.add_argument("--keep_dir", default=None, help="write the JPEGs here and keep them; files already there are reused")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
+    if a.jpeg:
+        os.environ["LEMON_JPEG"] = a.jpeg
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("file_pipeline_time.py needs a HIP device")
@@ -74,20 +84,30 @@ def main(argv=None):
     torch.manual_seed(0)
     emb = Embedder(LemonCLIP(cfg), dev, batch_size=a.batch)
     workers = a.workers if a.workers is not None else loader.default_workers(1)
+    jpeg_gpu = loader.device_jpeg_default()
     lines = []
+    if a.keep_dir:
+        os.makedirs(a.keep_dir, exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
+        tmp = a.keep_dir or tmp
         for mix in a.mixes.split(","):
             n = a.n if mix == "mscoco" else a.n_cars
             t0 = time.perf_counter()
-            paths = write_jpegs(tmp, mix, n)
+            paths = write_jpegs(tmp, mix, n, reuse=bool(a.keep_dir))
             write_s = time.perf_counter() - t0
-            # decode pool alone
+            # decode pool alone (pixels: what the resident figure needs)
             t0 = time.perf_counter()
             decoded = []
             with loader.DecodePool(paths, workers) as pool:
                 for _, img in pool.images():
                     decoded.append(img.copy())
-            decode_s = time.perf_counter() - t0
+            decode_s = pixels_decode_s = time.perf_counter() - t0
+            if jpeg_gpu:                             # ... and as the from-files path runs it: coefficient records
+                t0 = time.perf_counter()
+                with loader.DecodePool(paths, workers, records=True) as pool:
+                    n_rec = sum(isinstance(x, loader.JpegRecord) for _, x in pool.images())
+                decode_s = time.perf_counter() - t0
+                assert n_rec == n, (n_rec, n)
             # resident: pre-decoded uint8 in HBM
             chunks = [RaggedImages.from_arrays(decoded[s:s + a.batch], dev) for s in range(0, n, a.batch)]
             del decoded
@@ -133,7 +153,7 @@ def main(argv=None):
                 warm = ahead / (time.perf_counter() - t0)
             # the in-process thread path (LEMON_DECODE_WORKERS=0): PIL decode + CPU generic_transform, float32 across PCIe
             from lemon_amd.data import ImageLabelSet
-            nt = min(n, 512)
+            nt = 0 if a.skip_threads else min(n, 512)
             old = os.environ.get("LEMON_DECODE_WORKERS")
             os.environ["LEMON_DECODE_WORKERS"] = "0"
             try:
@@ -156,13 +176,16 @@ def main(argv=None):
                        h2d_MB_per_image=h2d_bytes / n / 1e6, ragged_us_per_image=ragged_us,
                        tower_us_per_image=resident_s * 1e6 / n, write_s=write_s,
                        warm_ring_images=ahead, warm_ring_images_per_s=warm, pack_images_per_s=n / max(stats["pack_s"], 1e-9),
-                       threads_path_images_per_s=nt / threads_s, threads_path_images=nt,
+                       threads_path_images_per_s=nt / threads_s if nt else None, threads_path_images=nt,
+                       jpeg="gpu" if jpeg_gpu else "pil", pil_pool_images_per_s=n / pixels_decode_s,
+                       jpeg_images=stats.get("jpeg_images", 0),
                        device=torch.cuda.get_device_name(0))
             rec["ratio_vs_min"] = rec["from_files_images_per_s"] / min(rec["resident_images_per_s"], rec["decode_images_per_s"])
             print(json.dumps(rec), flush=True)
             lines.append(rec)
-            for p in paths:
-                os.unlink(p)
+            if not a.keep_dir:
+                for p in paths:
+                    os.unlink(p)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
