@@ -530,6 +530,41 @@ int lemon_jpeg_reconstruct_host(const uint8_t *record, int64_t record_bytes, int
 int lemon_jpeg_decode(const uint8_t *rec_dev, int64_t rec_bytes, int64_t batch, const int64_t *aux_dev, int64_t idct_blocks,
                       int64_t rgb_blocks, uint8_t *work_dev, int64_t work_bytes, uint8_t *out_dev, int64_t out_bytes, void *stream);
 
+/* ---- the Huffman pass on the device: files cross PCIe compressed.  The decode workers of lib/datasets/dataloader.py:167-198's
+ * call site then only read the file, parse its markers and strip the byte stuffing (lemon_jpeg_pack); the device decodes the
+ * entropy-coded segment in parallel WITHIN every image (lemon_jpeg_entropy_device; scheme and packet: csrc/jpeg_par.hpp) into the
+ * records lemon_jpeg_decode reads, bit for bit what lemon_jpeg_entropy writes.  lemon_jpeg_pack and lemon_jpeg_entropy_par_host
+ * are also exported by liblemon_jpeg_host.so. */
+#define LEMON_JPEG_SYNC 16                /* status: the lanes' states had not settled under the round cap; decode with PIL */
+#define LEMON_JPEG_PACKET_BOUND 2752      /* packet_cap = n + n / 8192 + this always suffices (n + this without restart markers) */
+#define LEMON_JPEG_SUBSEQ_MIN 16          /* smallest subseq_bytes; a multiple of 4 up to 4096 */
+#define LEMON_JPEG_PAR_GROUP 256          /* lanes per workgroup */
+/* Host, no GPU (lib/datasets/dataloader.py:167-198, in the workers): runs lemon_jpeg_info's header pass -- and declines exactly
+ * what it declines --, then writes the scan packet into packet[0, packet_cap): geometry, quantisers, the Huffman table
+ * specifications and selectors, the restart interval, the entropy-coded segment with FF 00 -> FF and the restart markers
+ * removed, and the byte count of every restart interval.  While copying it verifies the marker structure (fill bytes, RSTn
+ * exactly where expected counting modulo 8, EOI after the last interval, no other marker): a violation is LEMON_JPEG_STREAM.
+ * Every read is bounds-checked.  *packet_bytes receives the packet's size (a multiple of 16).  Returns info->status. */
+int lemon_jpeg_pack(const uint8_t *data, int64_t n, uint8_t *packet, int64_t packet_cap, LemonJpegInfo *info, int64_t *packet_bytes);
+/* Device Huffman pass for a batch (lib/datasets/dataloader.py:167-198 per image; run_lemon.py:129-131,199-201 per loader batch).
+ * packets_dev[0, packets_bytes) holds the packets, rec_dev[0, rec_bytes) receives the records (both 16-byte aligned).  desc_dev
+ * (int64 [batch, 8]): packet offset and bytes, record offset (multiples of 16), restart intervals of the packet, first workgroup,
+ * first interval slot, workgroups, 0 -- where an image with scan_bytes of entropy-coded data in `intervals` intervals is given
+ * ceil((ceil(scan_bytes / subseq) + intervals) / 256) workgroups; total_groups and total_intervals are the sums.  subseq_bytes:
+ * bytes per lane, 0 = the default (256).  status_dev int32 [batch]: 0, a LemonJpegStatus code, LEMON_JPEG_SYNC, or
+ * LEMON_JPEG_BUFFER for an image whose packet, record or workspace share would leave its buffer (neither read nor written).
+ * ws_dev: lemon_jpeg_entropy_workspace_bytes(batch, total_groups, total_intervals) bytes, 16-byte aligned.  A declined image's
+ * record is unspecified. */
+int lemon_jpeg_entropy_device(const uint8_t *packets_dev, int64_t packets_bytes, int64_t batch, const int64_t *desc_dev,
+                              int64_t total_groups, int64_t total_intervals, int32_t subseq_bytes, uint8_t *rec_dev,
+                              int64_t rec_bytes, int32_t *status_dev, void *ws_dev, int64_t ws_bytes, void *stream);
+int64_t lemon_jpeg_entropy_workspace_bytes(int64_t batch, int64_t total_groups, int64_t total_intervals); /* < 0: LEMON_E_* */
+/* lemon_jpeg_entropy_device's algorithm with the lanes looped on the host -- the same functions, workgroups and rounds, so the
+ * same record and the same status.  Test support for lib/datasets/dataloader.py:167-198's decode where there is no GPU; no
+ * product path calls it.  Returns 0 unless an argument is invalid; *status as status_dev above. */
+int lemon_jpeg_entropy_par_host(const uint8_t *packet, int64_t packet_bytes, int32_t subseq_bytes, uint8_t *record,
+                                int64_t record_cap, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

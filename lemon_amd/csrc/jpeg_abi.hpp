@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "jpeg_entropy.hpp"
+#include "jpeg_par.hpp"
 
 extern "C" int lemon_jpeg_info(const uint8_t *data, int64_t n, LemonJpegInfo *info) {
     if (!info) return LEMON_JPEG_BUFFER;
@@ -13,6 +14,20 @@ extern "C" int lemon_jpeg_info(const uint8_t *data, int64_t n, LemonJpegInfo *in
 extern "C" int lemon_jpeg_entropy(const uint8_t *data, int64_t n, uint8_t *record, int64_t record_cap, LemonJpegInfo *info) {
     if (!info) return LEMON_JPEG_BUFFER;
     return lemon_jpeg_entropy_impl(data, n, record, record_cap, info);
+}
+
+// The workers' share of the device Huffman pass: header + the scan packet of jpeg_par.hpp.
+extern "C" int lemon_jpeg_pack(const uint8_t *data, int64_t n, uint8_t *packet, int64_t packet_cap, LemonJpegInfo *info,
+                               int64_t *packet_bytes) {
+    if (!info) return LEMON_JPEG_BUFFER;
+    return lemon_jpeg_pack_impl(data, n, packet, packet_cap, info, packet_bytes);
+}
+
+// The device's Huffman kernels (jpeg_entropy.hip) with the lanes looped on the host: packet -> record + status.  For tests and
+// the sanitizer fuzzer; no product path calls it.
+extern "C" int lemon_jpeg_entropy_par_host(const uint8_t *packet, int64_t packet_bytes, int32_t subseq_bytes, uint8_t *record,
+                                           int64_t record_cap, int32_t *status) {
+    return lemon_jpeg_entropy_par_host_impl(packet, packet_bytes, subseq_bytes, record, record_cap, status);
 }
 
 // The device's arithmetic (jpeg_core.hpp) on the host: a record -> packed uint8 RGB [h, w, 3].  For tests and for pinning the

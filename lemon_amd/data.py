@@ -306,38 +306,83 @@ def launch_jpeg_decode(data, layout, poison=None):
             work.fill_(poison)
             data[layout.decoded_off:].fill_(poison)
         base, vp = data.data_ptr(), ctypes.c_void_p
-        _lib.check(_lib.load().lemon_jpeg_decode(vp(base), layout.payload_bytes, layout.n_jpeg, vp(base + layout.aux_off),
+        _lib.check(_lib.load().lemon_jpeg_decode(vp(base), layout.rec_end, layout.n_jpeg, vp(base + layout.aux_off),
                                                  layout.idct_blocks, layout.rgb_blocks, vp(work.data_ptr()), work.numel(), vp(base),
                                                  data.numel(), stream_ptr(dev)), "lemon_jpeg_decode")
 
 
-def decode_jpegs(files, device, fallback=False, poison=None):
+def launch_jpeg_entropy(data, layout, poison=None, return_workspace=False):
+    """Enqueue lemon_jpeg_entropy_device on the current stream for the scan packets of a device buffer `data` laid out by a
+    jpeg_host.BatchLayout: their coefficient records appear in the buffer's device-only region, where launch_jpeg_decode (to be
+    called after this) reads them.  Returns the int32 device tensor of the packets' statuses, in the order of layout.packets (None
+    without packets).  `poison` (a byte, for tests) pre-fills the records' region and the workspace.  return_workspace=True (for
+    tools/jpeg_entropy_time.py) returns (statuses, the workspace tensor), whose first int32 [n_packets, 4] hold diagnostics
+    (csrc/jpeg_entropy.hip::JentWs)."""
+    from . import _lib
+    import ctypes
+    from .ops import stream_ptr
+    if not getattr(layout, "n_packets", 0):
+        return (None, None) if return_workspace else None
+    assert data.is_cuda and data.dtype == torch.uint8 and data.numel() >= layout.total_bytes
+    dev = data.device
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        need = lib.lemon_jpeg_entropy_workspace_bytes(layout.n_packets, layout.groups, layout.intervals)
+        if need < 0:
+            raise _lib.LemonHipError(f"lemon_jpeg_entropy_workspace_bytes: {layout.groups} workgroups, {layout.intervals} intervals")
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        status = torch.empty((layout.n_packets,), dtype=torch.int32, device=dev)
+        if poison is not None:
+            ws.fill_(poison)
+            status.fill_(poison)
+            data[layout.payload_bytes:layout.decoded_off].fill_(poison)
+        base, vp = data.data_ptr(), ctypes.c_void_p
+        _lib.check(lib.lemon_jpeg_entropy_device(vp(base), layout.payload_bytes, layout.n_packets, vp(base + layout.edesc_off),
+                                                 layout.groups, layout.intervals, layout.subseq, vp(base), layout.rec_end,
+                                                 vp(status.data_ptr()), vp(ws.data_ptr()), ws.numel(), stream_ptr(dev)),
+                   "lemon_jpeg_entropy_device")
+    return (status, ws) if return_workspace else status
+
+
+def decode_jpegs(files, device, fallback=False, poison=None, entropy="host"):
     """Decode JPEG files on the GPU -> RaggedImages of `Image.open(f).convert("RGB")`'s pixels, bit for bit.  `files`: paths or
-    bytes objects.  The Huffman pass runs here on the host (csrc/jpeg_entropy.hpp), everything after it in lemon_jpeg_decode.
-    A file the host pass declines (progressive, CMYK, not a JPEG, corrupt, ...) raises ValueError, or with fallback=True is
+    bytes objects.  entropy="host": the Huffman pass runs here on the host (csrc/jpeg_entropy.hpp), everything after it in
+    lemon_jpeg_decode.  entropy="device": the host only strips the files down to scan packets (lemon_jpeg_pack), the Huffman pass
+    runs in lemon_jpeg_entropy_device and the statuses are read back once before
+    returning.  A file that is declined (progressive, CMYK, not a JPEG, corrupt, ...) raises ValueError, or with fallback=True is
     decoded by PIL (whose own exception a corrupt file then raises).  The result carries `layout` (jpeg_host.BatchLayout)."""
     import io
     from PIL import Image
     from . import jpeg_host
+    if entropy not in ("host", "device"):
+        raise ValueError(f"entropy={entropy!r}: expected 'host' or 'device'")
     device = torch.device(device)
     if device.type != "cuda":
         raise TypeError("decode_jpegs needs a CUDA/HIP device: there is no CPU path")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    lay, items, off = jpeg_host.BatchLayout(), [], 0
+    lay, items, off, sources = jpeg_host.BatchLayout(), [], 0, []
+    declined = lambda what, status: ValueError(f"{what}: not decodable on the GPU ({jpeg_host.STATUS.get(status, status)})")
     for f in files:
         raw = f if isinstance(f, (bytes, bytearray, memoryview)) else open(f, "rb").read()
-        rec, info = jpeg_host.decode_record(bytes(raw))
+        what = "<bytes>" if raw is f else f
+        if entropy == "device":
+            rec, info = jpeg_host.pack(bytes(raw))
+        else:
+            rec, info = jpeg_host.decode_record(bytes(raw))
         if rec is None:
-            what = "<bytes>" if raw is f else f
             if not fallback:
-                raise ValueError(f"{what}: not decodable on the GPU ({jpeg_host.STATUS.get(info.status, info.status)})")
+                raise declined(what, info.status)
             px = np.asarray(Image.open(io.BytesIO(raw)).convert("RGB"), dtype=np.uint8)
             lay.add_pixels(off, px.shape[0], px.shape[1])
             items.append((off, px.reshape(-1)))
             off = (off + px.nbytes + 15) & ~15
         else:
-            lay.add_record(off, rec)
+            if entropy == "device":
+                lay.add_packet(off, rec)
+                sources.append((what, raw))
+            else:
+                lay.add_record(off, rec)
             items.append((off, rec.data))
             off = (off + rec.data.nbytes + 15) & ~15
     aux = lay.finish(off)
@@ -349,7 +394,19 @@ def decode_jpegs(files, device, fallback=False, poison=None):
         flat[lay.aux_off:lay.payload_bytes] = aux.view(np.uint8)
     data = torch.empty((max(lay.total_bytes, buf.numel()),), dtype=torch.uint8, device=device)
     data[:buf.numel()].copy_(buf, non_blocking=True)
+    status = launch_jpeg_entropy(data, lay, poison)
     launch_jpeg_decode(data, lay, poison)
+    if status is not None:
+        st = status.cpu().numpy()                                 # (the one read-back)
+        for k in np.flatnonzero(st):                              # (rare: the scan itself is corrupt)
+            what, raw = sources[k]
+            if not fallback:
+                raise declined(what, int(st[k]))
+            px = np.asarray(Image.open(io.BytesIO(raw)).convert("RGB"), dtype=np.uint8)
+            o, h, w, _ = lay.desc[lay.records[lay.packets[k][0]][0]]
+            if px.shape != (h, w, 3):
+                raise declined(what, int(st[k]))
+            data[o:o + px.size].copy_(torch.from_numpy(px.reshape(-1).copy()))
     out = RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
     out.layout = lay
     return out
@@ -397,7 +454,7 @@ class ImageLabelSet:
       * float32 [N,...] in memory: pixel tensors that are ALREADY what the model consumes (a preprocessed cache);
         passed through unchanged;
       * a list of file paths: with a CUDA device, decoded by worker processes and transformed on the GPU as RaggedImages
-        batches (lemon_amd/loader.py), with LEMON_JPEG=gpu baseline JPEGs with the device half of their decode on the GPU (default pil: all by PIL); otherwise (or with LEMON_DECODE_WORKERS=0) PIL decode + generic_transform in a thread pool.
+        batches (lemon_amd/loader.py), with LEMON_JPEG=gpu baseline JPEGs with the device half of their decode on the GPU, with LEMON_JPEG=device their Huffman pass too (default pil: all by PIL); otherwise (or with LEMON_DECODE_WORKERS=0) PIL decode + generic_transform in a thread pool.
     Labels are ints (class datasets) or strings (captions)."""
 
     def __init__(self, images, clean, noisy, image_size=224, workers=8):

@@ -5,7 +5,9 @@ the HIP library, never the GPU) and decodes exactly `Image.open(p).convert("RGB"
 With RECORDS = 1 a file that starts with FF D8 goes through the JPEG host pass instead (jpeg_host.py -> liblemon_jpeg_host.so,
 which links no HIP runtime): its Huffman decoding runs straight into the ring and the ring receives the coefficient record that
 lemon_jpeg_decode turns into the same pixels on the GPU.  A file the host pass declines (progressive, CMYK, corrupt, ...) is
-decoded with PIL exactly as without RECORDS, PIL's own exception for a corrupt file included.
+decoded with PIL exactly as without RECORDS, PIL's own exception for a corrupt file included.  With RECORDS = 2 the worker
+does not even decode Huffman codes: it writes the file's scan packet (lemon_jpeg_pack: markers parsed, byte stuffing removed)
+into the ring, and lemon_jpeg_entropy_device decodes it on the GPU; a file whose header the packer declines goes to PIL.
 
 Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS]`), so that not even the lemon_amd package is imported.
 Protocol (pickled frames on stdin / stdout, in order):
@@ -13,7 +15,8 @@ Protocol (pickled frames on stdin / stdout, in order):
   worker -> parent: ("hello", pid, torch_imported)
                     ("ok", seq, offset, h, w, consumed, oversize_path or None, kind, nbytes, (components, hs, vs) or None)
                     | ("err", seq, path, message)
-`kind` 0: nbytes = h * w * 3 of RGB pixels; `kind` 1: nbytes of coefficient record.
+`kind` 0: nbytes = h * w * 3 of RGB pixels; `kind` 1: nbytes of coefficient record; `kind` 2: nbytes of scan packet, with
+(components, hs, vs, intervals, scan_bytes).
 The ring is a circular byte buffer of CAPACITY bytes.  An image is written at `offset` once `consumed` bytes (its own plus the
 unused tail skipped when it wraps) are free; the parent returns them with "free" after it has copied the image, in the order
 the results came.  An image larger than the whole ring waits until the ring is empty and goes to a one-off segment
@@ -35,7 +38,8 @@ def main(argv):
     from PIL import Image
     shm_path, cap = argv[0], int(argv[1])
     records = len(argv) > 2 and argv[2] == "1"
-    if records:
+    packets = len(argv) > 2 and argv[2] == "2"
+    if records or packets:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import jpeg_host
     inp, out = sys.stdin.buffer, sys.stdout.buffer
@@ -76,6 +80,28 @@ def main(argv):
                 return 0
             continue
         _, seq, path = tasks.popleft()
+        if packets:
+            # the scan packet, straight into the ring: its capacity is known from the file size, its size after the call; only
+            # the bytes it took are committed
+            data = None
+            try:
+                with open(path, "rb") as fh:
+                    data = fh.read()
+            except OSError:
+                pass                    # (PIL below reports it)
+            if data is not None and data[:2] == b"\xff\xd8" and jpeg_host.packet_cap(len(data)) + 15 <= cap:
+                need = jpeg_host.packet_cap(len(data)) + 15
+                off, consumed = reserve(need)
+                at = (off + 15) & ~15
+                pk, full = jpeg_host.pack(data, view[at:at + need - 15])
+                if pk is not None:
+                    took = at - off + pk.data.nbytes
+                    head = off + took
+                    used += consumed - (need - took)
+                    _send(out, ("ok", seq, at, full.height, full.width, consumed - (need - took), None, 2, pk.data.nbytes,
+                                (full.components, full.hs, full.vs, pk.intervals, pk.scan_bytes)))
+                    continue
+            del data
         if records:
             # the host pass, straight into the ring: the record size is known after the frame header.  Nothing is committed
             # (head, used) until the pass has accepted the file; a declined file falls through to PIL below

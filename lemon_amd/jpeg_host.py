@@ -17,7 +17,9 @@ STATUS = {0: "ok", 1: "not a JPEG", 2: "truncated header", 3: "progressive / ari
           5: "not 1 or 3 components", 6: "unsupported sampling factors", 7: "not YCbCr (Adobe marker or component ids)",
           8: "bad or unsupported table", 9: "not one interleaved scan", 10: "bad Huffman code or coefficient",
           11: "bit stream ends early or runs past its last MCU", 12: "outside the arithmetic envelope", 13: "record buffer too small",
-          14: "zero dimension", 15: "unexpected marker"}
+          14: "zero dimension", 15: "unexpected marker", 16: "parallel Huffman states did not settle"}
+PACKET_BOUND = 2752      # include/lemon_hip.h: LEMON_JPEG_PACKET_BOUND
+SUBSEQ_MIN, SUBSEQ_DEFAULT, PAR_GROUP = 16, 256, 256      # bytes per lane (smallest, default), lanes per workgroup (csrc/jpeg_par.hpp)
 
 
 class Info(ctypes.Structure):
@@ -29,6 +31,9 @@ class Info(ctypes.Structure):
 
 # a coefficient record of one accepted file: `data` uint8 [record_bytes] (a view; copy it to keep it)
 JpegRecord = namedtuple("JpegRecord", "data w h components hs vs")
+
+# the scan packet of one file whose header pass accepts it (csrc/jpeg_par.hpp): `data` uint8 [packet bytes] (a view)
+JpegPacket = namedtuple("JpegPacket", "data w h components hs vs intervals scan_bytes")
 
 _lib = None
 
@@ -43,6 +48,8 @@ def load():
         lib.lemon_jpeg_info.argtypes = [ctypes.c_char_p, c_i64, ctypes.POINTER(Info)]
         lib.lemon_jpeg_entropy.argtypes = [ctypes.c_char_p, c_i64, vp, c_i64, ctypes.POINTER(Info)]
         lib.lemon_jpeg_reconstruct_host.argtypes = [vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, vp]
+        lib.lemon_jpeg_pack.argtypes = [ctypes.c_char_p, c_i64, vp, c_i64, ctypes.POINTER(Info), ctypes.POINTER(c_i64)]
+        lib.lemon_jpeg_entropy_par_host.argtypes = [vp, c_i64, c_i32, vp, c_i64, ctypes.POINTER(c_i32)]
         _lib = lib
     return _lib
 
@@ -74,6 +81,43 @@ def decode_record(data):
     return JpegRecord(rec, full.width, full.height, full.components, full.hs, full.vs), full
 
 
+def packet_cap(n):
+    """A capacity that holds the packet of any n-byte file."""
+    return n + n // 8192 + PACKET_BOUND + 16
+
+
+def pack(data, out=None):
+    """Header pass + scan packet of the bytes of a file -> (JpegPacket or None when declined, Info).  `out`: a writable
+    contiguous uint8 array of at least packet_cap(len(data)) bytes, 16-byte aligned, to write into (default: a new one)."""
+    if out is None:
+        out = np.empty(packet_cap(len(data)), np.uint8)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable
+    head, nbytes = Info(), ctypes.c_int64(0)
+    load().lemon_jpeg_pack(data, len(data), out.ctypes.data, out.size, ctypes.byref(head), ctypes.byref(nbytes))
+    if head.status != 0:
+        return None, head
+    pk = out[:nbytes.value]
+    meta = pk[:64].view(np.int32)          # (csrc/jpeg_par.hpp: kPkIntervals = 7, kPkScanBytes = 8)
+    return JpegPacket(pk, head.width, head.height, head.components, head.hs, head.vs, int(meta[7]), int(meta[8])), head
+
+
+def entropy_par_host(packet, record, subseq=0):
+    """The device's parallel Huffman pass with its lanes looped on the host: packet (uint8 array) -> `record`, returns the
+    status.  For tests."""
+    packet = np.ascontiguousarray(packet)
+    assert record.dtype == np.uint8 and record.flags.c_contiguous and record.flags.writeable
+    st = ctypes.c_int32(-1)
+    if load().lemon_jpeg_entropy_par_host(packet.ctypes.data, packet.size, subseq, record.ctypes.data, record.size, ctypes.byref(st)) != 0:
+        raise ValueError("lemon_jpeg_entropy_par_host: bad arguments")
+    return st.value
+
+
+def groups_of(scan_bytes, intervals, subseq=0):
+    """Workgroups lemon_jpeg_entropy_device needs for a packet (include/lemon_hip.h)."""
+    s = subseq or SUBSEQ_DEFAULT
+    return -(-(-(-scan_bytes // s) + intervals) // PAR_GROUP)
+
+
 def reconstruct(rec):
     """The device arithmetic on the host (csrc/jpeg_core.hpp): JpegRecord -> uint8 [h, w, 3].  For tests."""
     out = np.empty((rec.h, rec.w, 3), np.uint8)
@@ -95,13 +139,20 @@ def _up(n, a=16):
 
 
 class BatchLayout:
-    """Layout of one device buffer [payload | aux | decoded RGB] for a chunk of images.  The payload (filled by the caller, `off`
-    bytes so far) holds PIL pixels and coefficient records at 16-byte aligned offsets; finish() appends the int64 aux table of
-    lemon_jpeg_decode to the payload and places every JPEG's pixels after it.  `desc` is the RaggedImages table (byte offset, H,
-    W, plan index) in the order the images were added."""
+    """Layout of one device buffer [payload: packets, PIL pixels, records, aux | records of the packets | decoded RGB] for a chunk
+    of images.  The payload (filled by the caller, `off` bytes so far) holds PIL pixels, coefficient records and scan packets at
+    16-byte aligned offsets; finish() appends the int64 aux tables of lemon_jpeg_decode and lemon_jpeg_entropy_device to the
+    payload, gives every packet a record in the device-only region after it (written by lemon_jpeg_entropy_device) and places
+    every JPEG's pixels after that.  `desc` is the RaggedImages table (byte offset, H, W, plan index) in the order the images
+    were added.  `subseq`: bytes per lane of the device Huffman pass (0 = its default)."""
 
-    def __init__(self):
-        self.shapes, self.desc, self.records = {}, [], []
+    def __init__(self, subseq=0):
+        self.shapes, self.desc, self.records, self.packets, self.subseq = {}, [], [], [], subseq
+
+    def add_packet(self, off, pk):
+        """A scan packet at payload offset `off`: its record lies in the device-only region (offset known after finish())."""
+        self.packets.append((len(self.records), off, pk.data.nbytes, pk.intervals, pk.scan_bytes))
+        self.add_record(-1, pk)
 
     def add_pixels(self, off, h, w):
         self.desc.append([off, h, w, self.shapes.setdefault((h, w), len(self.shapes))])
@@ -112,14 +163,28 @@ class BatchLayout:
 
     def aux_bytes(self):
         n = len(self.records)
-        return 8 * (8 * n + 2 * (n + 1)) if n else 0
+        return 8 * (8 * n + 2 * (n + 1)) + 64 * len(self.packets) if n else 0
 
     def finish(self, off):
         """`off`: end of the images' payload.  -> the aux table (int64, to be copied to payload offset self.aux_off)."""
         n = len(self.records)
         self.aux_off = _up(off)
         self.payload_bytes = self.aux_off + self.aux_bytes()
-        out, work = _up(self.payload_bytes), 0
+        # records of the packets: device-only, after the copied payload
+        rec = _up(self.payload_bytes)
+        self.edesc_off = self.aux_off + 8 * (8 * n + 2 * (n + 1))
+        edesc = np.zeros((len(self.packets), 8), np.int64)
+        groups = intervals = 0
+        for k, (j, poff, pbytes, nivl, scan_bytes) in enumerate(self.packets):
+            i, _, w, h, nc, hs, vs = self.records[j]
+            self.records[j] = (i, rec, w, h, nc, hs, vs)
+            ng = groups_of(scan_bytes, nivl, self.subseq)
+            edesc[k] = (poff, pbytes, rec, nivl, groups, intervals, ng, 0)
+            groups, intervals = groups + ng, intervals + nivl
+            rec += QUANT_BYTES + 128 * blocks_of(w, h, nc, hs, vs)
+        self.rec_end = rec if self.packets else self.payload_bytes
+        self.n_packets, self.groups, self.intervals = len(self.packets), groups, intervals
+        out, work = _up(self.rec_end), 0
         d8 = np.zeros((n, 8), np.int64)
         apre, bpre = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
         for j, (i, roff, w, h, nc, hs, vs) in enumerate(self.records):
@@ -130,7 +195,7 @@ class BatchLayout:
             bpre[j + 1] = bpre[j] + -(-(h * -(-w // RGB_PIXELS)) // 256)
             out = _up(out + h * w * 3)
             work += nb * 64
-        self.decoded_off = _up(self.payload_bytes)
+        self.decoded_off = _up(self.rec_end)
         self.total_bytes, self.work_bytes = max(out, 1), max(work, 16)
         self.idct_blocks, self.rgb_blocks, self.n_jpeg = int(apre[-1]), int(bpre[-1]), n
-        return np.concatenate([d8.ravel(), apre, bpre]) if n else np.zeros(0, np.int64)
+        return np.concatenate([d8.ravel(), apre, bpre, edesc.ravel()]) if n else np.zeros(0, np.int64)

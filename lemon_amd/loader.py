@@ -11,6 +11,11 @@ lib/datasets/dataloader.py:167-198).  Here:
     half of a baseline JPEG's decode, the Huffman pass (csrc/jpeg_entropy.hpp), and hands over a coefficient record; the
     records travel in the same pinned buffer and copy as the PIL pixels of the files it declines, and lemon_jpeg_decode
     reconstructs bit-identical RGB pixels on the compute stream, in the same device buffer, before the ragged transform.
+  * with LEMON_JPEG=device the workers do not decode at all: they strip a baseline JPEG down to its scan packet (lemon_jpeg_pack),
+    the file crosses PCIe compressed, and lemon_jpeg_entropy_device runs the Huffman pass on the GPU in front of
+    lemon_jpeg_decode.  The statuses come back through pinned memory behind an event; a chunk is handed out after it, one chunk
+    behind the one being enqueued, so the wait falls into the previous chunk's embedding.  The rare image the device declines is
+    decoded with PIL in the parent and copied into its slot.
 The held decoded bytes are bounded by `ring_bytes` (one ring of ring_bytes / workers per worker; an image larger than a whole
 ring is decoded alone, when its worker's ring is empty)."""
 import os
@@ -21,7 +26,7 @@ import uuid
 
 import numpy as np
 
-from .jpeg_host import BatchLayout, JpegRecord
+from .jpeg_host import BatchLayout, JpegPacket, JpegRecord
 
 _WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_worker.py")
 DEFAULT_RING_BYTES = 1 << 30
@@ -42,14 +47,17 @@ def usable_cpus():
 
 
 def device_jpeg_default():
-    """Whether file batches decode baseline JPEGs on the GPU: LEMON_JPEG=gpu / pil.  Default pil: the end-to-end comparison
-    that would turn it on has not been recorded yet; results are identical either way."""
+    """How file batches decode baseline JPEGs: LEMON_JPEG=pil (False: all by PIL in the workers), gpu (True: Huffman pass in the
+    workers, the rest on the GPU) or device ("device": the Huffman pass on the GPU too).  Default pil: the recorded end-to-end
+    comparison does not yet justify another default; results are identical in all three."""
     env = os.environ.get("LEMON_JPEG", "").strip().lower()
     if env == "gpu":
         return True
+    if env == "device":
+        return "device"
     if env in ("", "pil"):
         return False
-    raise ValueError(f"LEMON_JPEG={env!r}: expected 'gpu' or 'pil'")
+    raise ValueError(f"LEMON_JPEG={env!r}: expected 'pil', 'gpu' or 'device'")
 
 
 def default_workers(world=1):
@@ -68,12 +76,13 @@ class DecodePool:
     """`workers` decode processes over `paths`; images(lo, hi) yields (i, uint8 [H, W, 3] view of shared memory) in order, each
     view valid until the next item is requested.  With records=True a baseline JPEG the host pass accepts is yielded as
     (i, JpegRecord) instead -- its coefficient record, `data` a view of shared memory under the same rule -- and every other
-    file as pixels."""
+    file as pixels.  With packets=True a baseline JPEG whose header the packer accepts is yielded as (i, JpegPacket): its scan
+    packet for lemon_jpeg_entropy_device."""
 
-    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False):
+    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False, packets=False):
         self.paths = list(paths)
         self.n_workers = default_workers(world) if workers is None else int(workers)
-        self.records = bool(records)
+        self.records, self.packets = bool(records) and not packets, bool(packets)
         assert self.n_workers >= 1
         self.cap = max(1 << 20, int(ring_bytes) // self.n_workers)
         self.ring_bytes = self.cap * self.n_workers
@@ -93,7 +102,7 @@ class DecodePool:
                 os.ftruncate(fd, self.cap)
                 self.rings.append(np.frombuffer(mmap.mmap(fd, self.cap), np.uint8))
                 os.close(fd)
-                self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap), "1" if self.records else "0"], stdin=subprocess.PIPE,
+                self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap), "2" if self.packets else "1" if self.records else "0"], stdin=subprocess.PIPE,
                                                    stdout=subprocess.PIPE, close_fds=True))
             for p in self.procs:
                 msg = self._read(p, "worker start")
@@ -130,7 +139,7 @@ class DecodePool:
                 raise DecodeError(f"cannot decode image {msg[2]}: {msg[3]}")
             _, seq, off, h, w, consumed, big, kind, n, meta = msg
             assert seq == i, (seq, i)
-            assert kind == 1 or n == h * w * 3, (kind, n, h, w)
+            assert kind in (1, 2) or n == h * w * 3, (kind, n, h, w)
             if big is not None:
                 import mmap
                 fd = os.open(big, os.O_RDONLY)
@@ -142,7 +151,7 @@ class DecodePool:
                 self.held += consumed
                 self.peak_held = max(self.peak_held, self.held)
             last = (k, consumed, big)
-            yield i, (JpegRecord(arr, w, h, *meta) if kind == 1 else arr.reshape(h, w, 3))
+            yield i, (JpegRecord(arr, w, h, *meta) if kind == 1 else JpegPacket(arr, w, h, *meta) if kind == 2 else arr.reshape(h, w, 3))
         if last is not None:
             self._release(*last)
 
@@ -198,11 +207,18 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
     while the caller embeds the previous chunk; a buffer is refilled only after its last H2D copy has completed.  The copy runs
     as uint8 on a copy stream, into memory allocated on that stream, and only the current stream waits on the copy's event:
     copies overlap the compute already queued.  `stats` (a dict) collects the copies' timing events and bytes
-    ("h2d": [(start, end, bytes)]) and the packing thread's seconds ("pack_s").  `device_jpeg` (None: device_jpeg_default()):
+    ("h2d": [(start, end, bytes)]), the packing thread's seconds copying ("pack_s") and waiting for the workers ("pool_wait_s"),
+    the caller's seconds waiting for a packed chunk ("ready_wait_s") and for the statuses of the device Huffman pass
+    ("status_wait_s").  `device_jpeg` (None: device_jpeg_default()):
     the workers deliver coefficient records for the JPEGs their host pass accepts; the chunk's records, PIL pixels and the aux
     table of lemon_jpeg_decode are packed into the same pinned buffer and copied once into a device buffer laid out
     [copied payload | decoded RGB]; lemon_jpeg_decode runs on the current stream after the copy's event, and the RaggedImages
-    offsets point into the payload (PIL images) or the decoded region (JPEGs).  The pool closes (workers exit, segments
+    offsets point into the payload (PIL images) or the decoded region (JPEGs).  device_jpeg="device": the workers deliver scan
+    packets, lemon_jpeg_entropy_device, lemon_jpeg_decode and an asynchronous copy of the statuses to (reused) pinned memory are
+    enqueued behind the chunk's copy on a stream of their own, and the chunk is handed out after its status event, when the
+    compute stream joins that stream, while the next chunk is already enqueued; an
+    image the device declines is read again from its path, decoded by PIL here and copied into its RGB slot (a file PIL cannot
+    decode raises DecodeError as in pil mode).  The pool closes (workers exit, segments
     unlinked) when the generator ends, is closed early or raises."""
     import queue
     import threading
@@ -210,9 +226,10 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
 
     import torch
 
-    from .data import RaggedImages, RaggedPlans, launch_jpeg_decode
+    from .data import RaggedImages, RaggedPlans, launch_jpeg_decode, launch_jpeg_entropy
     if device_jpeg is None:
         device_jpeg = device_jpeg_default()
+    packets = device_jpeg == "device"
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -265,13 +282,18 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     return buf
 
                 for _ in range(s, e):
+                    t0 = time.perf_counter()
                     _, a = next(it)                  # (a view of the worker's ring, valid until the next image is asked for)
                     t1 = time.perf_counter()
-                    src = a.data if isinstance(a, JpegRecord) else a.reshape(-1)
+                    if stats is not None:
+                        stats["pool_wait_s"] = stats.get("pool_wait_s", 0.0) + t1 - t0
+                    src = a.data if isinstance(a, (JpegRecord, JpegPacket)) else a.reshape(-1)
                     need = off + src.nbytes
                     buf = room(buf, off, need)
                     np.copyto(buf.numpy()[off:need], src)
-                    if isinstance(a, JpegRecord):
+                    if isinstance(a, JpegPacket):
+                        lay.add_packet(off, a)
+                    elif isinstance(a, JpegRecord):
                         lay.add_record(off, a)
                     else:
                         lay.add_pixels(off, a.shape[0], a.shape[1])
@@ -288,12 +310,40 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
         except BaseException as exc:                 # noqa: BLE001  (re-raised by the consumer)
             put(ready, exc)
 
-    with DecodePool(paths, workers, ring_bytes, world, records=device_jpeg) as pool:
+    def finished(s, e, data, lay, status, ev):
+        """The chunk once its statuses have arrived: the images the device declined are decoded by PIL into their slots."""
+        torch.cuda.current_stream(device).wait_event(ev)
+        if status is not None:
+            t0 = time.perf_counter()
+            ev.synchronize()
+            if stats is not None:
+                stats["status_wait_s"] = stats.get("status_wait_s", 0.0) + time.perf_counter() - t0
+            for k in np.flatnonzero(status.numpy()):
+                from PIL import Image
+                i = lay.records[lay.packets[k][0]][0]
+                o, h, w, _ = lay.desc[i]
+                try:
+                    px = np.asarray(Image.open(paths[s + i]).convert("RGB"), dtype=np.uint8)
+                except Exception as exc:             # noqa: BLE001  (what the worker reports in pil mode)
+                    raise DecodeError(f"cannot decode image {paths[s + i]}: {type(exc).__name__}: {exc}") from None
+                if px.shape != (h, w, 3):
+                    raise DecodeError(f"cannot decode image {paths[s + i]}: PIL reads {px.shape}, its header says {(h, w, 3)}")
+                data[o:o + px.size].copy_(torch.from_numpy(px.reshape(-1).copy()))
+                if stats is not None:
+                    stats["jpeg_fallback"] = stats.get("jpeg_fallback", 0) + 1
+        return s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
+
+    with DecodePool(paths, workers, ring_bytes, world, records=bool(device_jpeg), packets=packets) as pool:
         th = threading.Thread(target=pack, args=(pool,), daemon=True)
         th.start()
+        pending, n_chunks, pinned_status = None, 0, [None, None, None]
+        jpeg_stream = torch.cuda.Stream(device) if packets else None
         try:
             while True:
+                t_wait = time.perf_counter()
                 item = ready.get()
+                if stats is not None:
+                    stats["ready_wait_s"] = stats.get("ready_wait_s", 0.0) + time.perf_counter() - t_wait
                 if item is None:
                     break
                 if isinstance(item, BaseException):
@@ -317,8 +367,33 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                 if timed:
                     stats.setdefault("h2d", []).append((t0, ev, off))
                     stats["jpeg_images"] = stats.get("jpeg_images", 0) + lay.n_jpeg
-                launch_jpeg_decode(data, lay)            # (on the current stream, after the copy's event; nothing without records)
-                yield s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
+                if not packets:
+                    launch_jpeg_decode(data, lay)        # (on the current stream, after the copy's event; nothing without records)
+                    yield s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
+                    continue
+                # the Huffman pass, the rest of the decode and the statuses' way back run on a stream of their own, behind the
+                # copy only: they overlap the embedding queued on the compute stream, and waiting for the statuses waits for
+                # nothing else.  The compute stream joins when the chunk is handed out (finished()).
+                status = sev = None
+                with torch.cuda.stream(jpeg_stream):
+                    jpeg_stream.wait_event(ev)
+                    status_dev = launch_jpeg_entropy(data, lay)
+                    launch_jpeg_decode(data, lay)
+                    if status_dev is not None:
+                        if pinned_status[n_chunks % 3] is None or pinned_status[n_chunks % 3].numel() < status_dev.numel():
+                            pinned_status[n_chunks % 3] = torch.empty((max(chunk, status_dev.numel()),), dtype=torch.int32).pin_memory()
+                        status = pinned_status[n_chunks % 3][:status_dev.numel()]      # (at most two chunks are in flight)
+                        status.copy_(status_dev, non_blocking=True)
+                    sev = torch.cuda.Event()
+                    sev.record(jpeg_stream)
+                data.record_stream(jpeg_stream)
+                n_chunks += 1
+                # hand out the chunk enqueued before this one: its statuses arrived while this one was being packed
+                if pending is not None:
+                    yield finished(*pending)
+                pending = (s, e, data, lay, status, sev)
+            if pending is not None:
+                yield finished(*pending)
         finally:
             stop.set()
             th.join()

@@ -9,9 +9,12 @@ Writes N seeded JPEGs (PIL, quality 90, 4:2:0) per size mix to a temp dir and pr
   ragged_us_per_image      lemon_preprocess_ragged alone (operand form), device events
   warm_ring_images_per_s   from files, timed only after the pool has decoded as far ahead as it may
   pack_images_per_s        the packing thread's copies out of the rings into pinned memory
+  pool_wait_s, ready_wait_s, status_wait_s   of the from-files run's from_files_s: the packing thread waiting for the workers,
+                           the caller waiting for a packed chunk, the caller waiting for the device Huffman pass's statuses
   threads_path_images_per_s  LEMON_DECODE_WORKERS=0 (in-process PIL decode + CPU transform), first <= 512 images
-  --jpeg gpu|pil           from-files and pool figures with baseline JPEGs decoded on the GPU (the workers run only the Huffman
-                           pass) or by PIL in the workers (LEMON_JPEG); default: the library's default
+  --jpeg gpu|pil|device    from-files and pool figures with baseline JPEGs decoded on the GPU (gpu: the workers run only the
+                           Huffman pass; device: the workers only write scan packets, the Huffman pass runs on the GPU too) or
+                           by PIL in the workers (LEMON_JPEG); default: the library's default
 Every timed region is bracketed by a device synchronise.  Needs a HIP device.
 
   python tools/file_pipeline_time.py --arch vit-b-16 --n 2048 --out profiles/r6/file_pipeline.jsonl
@@ -63,7 +66,7 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--mixes", default="mscoco,cars")
     ap.add_argument("--workers", type=int, default=None)
-    ap.add_argument("--jpeg", choices=("gpu", "pil"), default=None)
+    ap.add_argument("--jpeg", choices=("gpu", "pil", "device"), default=None)
     ap.add_argument("--skip_threads", action="store_true", help="leave out the LEMON_DECODE_WORKERS=0 figure")
     ap.add_argument("--keep_dir", default=None, help="write the JPEGs here and keep them; files already there are reused")
     ap.add_argument("--out", default=None)
@@ -104,8 +107,8 @@ def main(argv=None):
             decode_s = pixels_decode_s = time.perf_counter() - t0
             if jpeg_gpu:                             # ... and as the from-files path runs it: coefficient records
                 t0 = time.perf_counter()
-                with loader.DecodePool(paths, workers, records=True) as pool:
-                    n_rec = sum(isinstance(x, loader.JpegRecord) for _, x in pool.images())
+                with loader.DecodePool(paths, workers, records=True, packets=jpeg_gpu == "device") as pool:
+                    n_rec = sum(isinstance(x, (loader.JpegRecord, loader.JpegPacket)) for _, x in pool.images())
                 decode_s = time.perf_counter() - t0
                 assert n_rec == n, (n_rec, n)
             # resident: pre-decoded uint8 in HBM
@@ -177,8 +180,10 @@ def main(argv=None):
                        tower_us_per_image=resident_s * 1e6 / n, write_s=write_s,
                        warm_ring_images=ahead, warm_ring_images_per_s=warm, pack_images_per_s=n / max(stats["pack_s"], 1e-9),
                        threads_path_images_per_s=nt / threads_s if nt else None, threads_path_images=nt,
-                       jpeg="gpu" if jpeg_gpu else "pil", pil_pool_images_per_s=n / pixels_decode_s,
-                       jpeg_images=stats.get("jpeg_images", 0),
+                       jpeg="device" if jpeg_gpu == "device" else "gpu" if jpeg_gpu else "pil", pil_pool_images_per_s=n / pixels_decode_s,
+                       jpeg_images=stats.get("jpeg_images", 0), jpeg_fallback=stats.get("jpeg_fallback", 0),
+                       from_files_s=files_s, pool_wait_s=stats.get("pool_wait_s"), ready_wait_s=stats.get("ready_wait_s"),
+                       status_wait_s=stats.get("status_wait_s", 0.0), pack_s=stats["pack_s"],
                        device=torch.cuda.get_device_name(0))
             rec["ratio_vs_min"] = rec["from_files_images_per_s"] / min(rec["resident_images_per_s"], rec["decode_images_per_s"])
             print(json.dumps(rec), flush=True)
