@@ -71,12 +71,17 @@ int lemon_paired_distance(int metric, const float *a_dev, const float *b_dev, in
 /* DistanceEvaluator.our_metric, lib/metrics/distance_metrics.py:48-73 (used by
  * lib/baselines/run_clip_sim.py:235-248): paired distance of row i of a and row i of b WITHOUT
  * assuming normalised inputs.  kind 0: cosine 1 - <a,b>/(|a||b|); 1: euclidean (NOT squared);
- * 2: manhattan.  The reference takes the diagonal of the full n x n pairwise matrix. */
+ * 2: manhattan.  The reference takes the diagonal of the full n x n pairwise matrix.  Sums run in float64 and the result is
+ * rounded once to float32 (sklearn's euclidean and manhattan distances are float64 values); a row of norm zero has cosine
+ * similarity 0 to everything, hence distance exactly 1, as sklearn.metrics.pairwise.cosine_similarity gives. */
 int lemon_paired_metric(int kind, const float *a_dev, const float *b_dev, int64_t n, int d,
                         float *out_dev, void *stream);
 
 /* --normalize_d1, run_lemon.py:244-248: d1[i] = softmax_c(dist(img_i, cls_txt_c))[noisy_label[i]].
- * cls_txt_dev [C,d] (run_lemon.py:180-190), noisy_label_dev [n] int32. */
+ * cls_txt_dev [C,d] (run_lemon.py:180-190), noisy_label_dev [n] int32.  0 < C <= 1024, anything else is refused with
+ * LEMON_E_INVALID and d1_dev is not written.  The labels live on the device and are NOT checked: a label outside [0, C)
+ * matches no class and gives d1 = 0 (the reference raises IndexError for a label >= C and wraps a negative one round).  A
+ * caller that cannot vouch for its labels checks them on the host first, as lemon_amd.ops.d1_normalized does. */
 int lemon_d1_normalized(int metric, const float *q_img_dev, int64_t n, int d,
                         const float *cls_txt_dev, int C, const int32_t *noisy_label_dev,
                         float *d1_dev, void *stream);
@@ -84,7 +89,10 @@ int lemon_d1_normalized(int metric, const float *q_img_dev, int64_t n, int d,
 /* Zero-shot "CLIP logits" baseline, lib/baselines/train_zero_shot_clip_baseline.py:207-224: per image,
  * conf[i] = softmax_c(1 - dist(cls_txt_c, img_i))[noisy_label[i]] with dist = DistanceEvaluator.our_metric
  * (lib/metrics/distance_metrics.py:48-73) on UN-normalised embeddings: kind 0 = 1 - cosine similarity,
- * 1 = euclidean (not squared), 2 = manhattan.  img_dev [n,d], cls_txt_dev [C,d], C <= 1024. */
+ * 1 = euclidean (not squared), 2 = manhattan.  img_dev [n,d], cls_txt_dev [C,d], 0 < C <= 1024 (anything else: LEMON_E_INVALID,
+ * conf_dev not written).  Distances, softmax and quotient are computed in float64 and rounded once to float32.  A zero image
+ * or class row has cosine distance 1 (similarity 0, as sklearn gives), never NaN.  Labels are not checked, as in
+ * lemon_d1_normalized: one outside [0, C) gives conf = 0; lemon_amd.baselines.clip_logits_confidence checks on the host. */
 int lemon_class_confidence(int kind, const float *img_dev, int64_t n, int d, const float *cls_txt_dev, int C,
                            const int32_t *noisy_label_dev, float *conf_dev, void *stream);
 
@@ -172,7 +180,11 @@ int lemon_layernorm_f32(const float *x_dev, const float *weight_dev, const float
  *     patch-embedding GEMM's output, y_dev [batch, n_tokens, width]; ln_weight_dev = ln_bias_dev = NULL: no LayerNorm (timm's
  *     VisionTransformer._pos_embed has none: norm_pre is the identity in BiomedCLIP's vit_base_patch16_224);
  *   text (token + position embedding, chexzero_clip.py:363-365): y[b,t] = tok_emb[ids[b,t]] + pos[t] for t < seq_len;
- *     ids_dev int64 with row pitch ids_pitch >= seq_len (the caller's [batch, context] id matrix, truncated in place). */
+ *     ids_dev int64 with row pitch ids_pitch >= seq_len (the caller's [batch, context] id matrix, truncated in place; columns
+ *     from seq_len on are never read).  An id outside [0, vocab) is CLAMPED to the nearest valid row (id < 0 -> row 0,
+ *     id >= vocab -> row vocab - 1), so that no id can make the lookup leave tok_emb_dev; torch's embedding raises instead.
+ *   width a multiple of 4 (vision: <= 2048, n_tokens >= 2, LayerNorm weight and bias both given or both NULL); every pointer
+ *   16-byte aligned (float4 accesses); a refused call (LEMON_E_INVALID) writes nothing. */
 int lemon_vision_tokens_ln(const float *patches_dev, const float *cls_dev, const float *pos_dev,
                            const float *ln_weight_dev, const float *ln_bias_dev, float eps, int64_t batch,
                            int n_tokens, int width, float *y_dev, void *stream);

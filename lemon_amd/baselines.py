@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .index import IndexFlatIP
-from .ops import dev_f32, normalize_vectors, our_metric, ptr, stream_ptr
+from .ops import checked_labels, dev_f32, normalize_vectors, our_metric, ptr, stream_ptr
 
 
 def discrepancy_scores(db, q_img, q_txt, k, method, is_train=False):
@@ -46,7 +46,7 @@ def clip_logits_confidence(img_embeds, class_text_embeds, noisy_label, dist="cos
         raise NotImplementedError(dist)
     q, c = dev_f32(img_embeds, "img_embeds"), dev_f32(class_text_embeds, "class_text_embeds")
     assert q.dim() == 2 and c.dim() == 2 and q.shape[1] == c.shape[1]
-    lab = torch.as_tensor(noisy_label).to(device=q.device, dtype=torch.int32).contiguous()
+    lab = checked_labels(noisy_label, q.shape[0], c.shape[0], q.device)      # ValueError for a label outside [0, C)
     out = torch.empty(q.shape[0], dtype=torch.float32, device=q.device)
     lib = _lib.load()
     with torch.cuda.device(q.device):

@@ -50,15 +50,42 @@ __global__ __launch_bounds__(256) void k_normalize_rows(const float *__restrict_
 // contract).  MODE 0: dot(a,b)  MODE 1: 1 - dot(a,b)  MODE 2: sum (a-b)^2  MODE 3: sqrt(sum (a-b)^2)
 // MODE 4: sum |a-b|  MODE 5: 1 - dot(a,b)/(|a||b|)   (3-5: DistanceEvaluator.our_metric,
 // lib/metrics/distance_metrics.py:48-73, which takes the diagonal of a full pairwise matrix)
+// Modes 0-2 are the contract's single float32 chain, bit for bit.  Modes 3-5 have no chain to match: sklearn computes
+// euclidean and manhattan distances in float64 and rounds once, so a float32 chain over d = 512 terms is an order of
+// magnitude less accurate than the reference.  They sum in float64, in four independent partial sums (k mod 4) that are
+// added pairwise at the end, and round once to float32.
 // ---------------------------------------------------------------------------------
+struct Wide4 { double s[4], a[4], b[4]; };
+
+// one term of the float64 sums: KIND 0 dot and both squared norms, 1 squared difference, 2 absolute difference
+template <int KIND>
+__device__ __forceinline__ void wide_term(float fa, float fb, double &s, double &na, double &nb) {
+    const double a = (double)fa, b = (double)fb;
+    if (KIND == 0) { s = fma(a, b, s); na = fma(a, a, na); nb = fma(b, b, nb); }
+    else if (KIND == 1) { const double t = a - b; s = fma(t, t, s); }
+    else s += fabs(a - b);
+}
+
+__device__ __forceinline__ double sum4(const double *p) { return (p[0] + p[1]) + (p[2] + p[3]); }
+
+// 1 - cosine similarity the way sklearn.metrics.pairwise.cosine_similarity defines it: a row of norm zero is left as it is
+// by normalize(), so its similarity to anything is 0 and its distance 1 (a NaN still comes out as NaN)
+__device__ __forceinline__ double cosine_distance(double dot, double na, double nb) {
+    const double den = sqrt(na) * sqrt(nb);
+    return 1.0 - (den == 0.0 ? 0.0 : dot / den);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(64) void k_rowchain(const float *__restrict__ a, const float *__restrict__ b,
                                                  int64_t n, int d, float *__restrict__ out) {
     __shared__ float sa[64][65];
     __shared__ float sb[64][65];
+    constexpr bool WIDE = MODE >= 3;
+    constexpr int KIND = MODE == 5 ? 0 : (MODE == 3 ? 1 : 2);
     const int lane = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * 64;
-    float acc = 0.0f, na = 0.0f, nb = 0.0f;
+    float acc = 0.0f;
+    Wide4 w = {};
     for (int k0 = 0; k0 < d; k0 += 64) {
         // coalesced: for each of the 64 rows, 64 lanes read 64 consecutive floats
         for (int r = 0; r < 64; ++r) {
@@ -70,12 +97,19 @@ __global__ __launch_bounds__(64) void k_rowchain(const float *__restrict__ a, co
         }
         __syncthreads();
         const int kmax = (d - k0) < 64 ? (d - k0) : 64;
-        for (int k = 0; k < kmax; ++k) {
-            float va = sa[lane][k], vb = sb[lane][k];
-            if (MODE == 2 || MODE == 3) { float t = va - vb; acc = __builtin_fmaf(t, t, acc); }
-            else if (MODE == 4) acc += fabsf(va - vb);
-            else acc = __builtin_fmaf(va, vb, acc);
-            if (MODE == 5) { na = __builtin_fmaf(va, va, na); nb = __builtin_fmaf(vb, vb, nb); }
+        if (WIDE) {
+            // (k0 is a multiple of 4: partial sum p holds the terms with k mod 4 == p)
+            for (int k = 0; k < kmax; k += 4) {
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    if (k + p < kmax) wide_term<KIND>(sa[lane][k + p], sb[lane][k + p], w.s[p], w.a[p], w.b[p]);
+            }
+        } else {
+            for (int k = 0; k < kmax; ++k) {
+                float va = sa[lane][k], vb = sb[lane][k];
+                if (MODE == 2) { float t = va - vb; acc = __builtin_fmaf(t, t, acc); }
+                else acc = __builtin_fmaf(va, vb, acc);
+            }
         }
         __syncthreads();
     }
@@ -83,8 +117,9 @@ __global__ __launch_bounds__(64) void k_rowchain(const float *__restrict__ a, co
     if (row < n) {
         float r = acc;
         if (MODE == 1) r = 1.0f - acc;
-        if (MODE == 3) r = sqrtf(acc);
-        if (MODE == 5) r = 1.0f - acc / fmaxf(sqrtf(na) * sqrtf(nb), 1e-30f);
+        if (MODE == 3) r = (float)sqrt(sum4(w.s));
+        if (MODE == 4) r = (float)sum4(w.s);
+        if (MODE == 5) r = (float)cosine_distance(sum4(w.s), sum4(w.a), sum4(w.b));
         out[row] = r;
     }
 }
@@ -152,42 +187,43 @@ __global__ __launch_bounds__(64) void k_class_confidence(int kind, const float *
     if (i >= n) return;
     const float *v = img + i * (int64_t)d;
     const int mylab = lab[i];
-    float vv = 0.0f;
-    if (kind == 0) for (int k = 0; k < d; ++k) vv = __builtin_fmaf(v[k], v[k], vv);
-    float z[16];
-    float mx = -FLT_MAX, mine = 0.0f;
+    // distances, softmax and the quotient in float64 (the sums as in k_rowchain<3..5>: four partial sums, k mod 4), one
+    // rounding to float32 at the store: the reference's manhattan and euclidean distances are float64 values
+    double z[16];
+    double mx = -DBL_MAX, mine = 0.0;
     int nz = 0;
     for (int c = lane; c < C && nz < 16; c += 64, ++nz) {
         const float *t = cls + (int64_t)c * d;
-        float dist;
-        if (kind == 0) {
-            float dot = 0.0f, tt = 0.0f;
-            for (int k = 0; k < d; ++k) { dot = __builtin_fmaf(v[k], t[k], dot); tt = __builtin_fmaf(t[k], t[k], tt); }
-            dist = 1.0f - dot / (sqrtf(vv) * sqrtf(tt));
-        } else if (kind == 1) {
-            float acc = 0.0f;
-            for (int k = 0; k < d; ++k) { const float u = v[k] - t[k]; acc = __builtin_fmaf(u, u, acc); }
-            dist = sqrtf(acc);
-        } else {
-            float acc = 0.0f;
-            for (int k = 0; k < d; ++k) acc += fabsf(v[k] - t[k]);
-            dist = acc;
+        Wide4 w = {};
+        for (int k = 0; k < d; k += 4) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                if (k + p < d) {
+                    if (kind == 0) wide_term<0>(v[k + p], t[k + p], w.s[p], w.a[p], w.b[p]);
+                    else if (kind == 1) wide_term<1>(v[k + p], t[k + p], w.s[p], w.a[p], w.b[p]);
+                    else wide_term<2>(v[k + p], t[k + p], w.s[p], w.a[p], w.b[p]);
+                }
+            }
         }
-        z[nz] = 1.0f - dist;
-        mx = fmaxf(mx, z[nz]);
+        double dist;
+        if (kind == 0) dist = cosine_distance(sum4(w.s), sum4(w.a), sum4(w.b));
+        else if (kind == 1) dist = sqrt(sum4(w.s));
+        else dist = sum4(w.s);
+        z[nz] = 1.0 - dist;
+        mx = fmax(mx, z[nz]);
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-    float s = 0.0f;
+    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+    double s = 0.0;
     int j = 0;
     for (int c = lane; c < C && j < 16; c += 64, ++j) {
-        const float e = expf(z[j] - mx);
+        const double e = exp(z[j] - mx);
         s += e;
         if (c == mylab) mine = e;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); mine += __shfl_xor(mine, off); }
-    if (lane == 0) conf[i] = mine / s;
+    if (lane == 0) conf[i] = (float)(mine / s);
 }
 
 // ---------------------------------------------------------------------------------

@@ -656,9 +656,26 @@ def paired_distance(metric, a, b):
     return out
 
 
+def checked_labels(noisy_label, n, C, device):
+    """The noisy labels as an int32 tensor on `device`, checked first: the kernels compare them with class numbers and
+    quietly give 0 for one outside [0, C), where the reference's `softmax(...)[label]` raises (>= C) or wraps round (< 0).
+    Labels arrive on the host (run_lemon.py:244-248 reads them from the dataset's metadata), where the check is free; a
+    tensor that is already on a device is checked there (one read-back)."""
+    lab = torch.as_tensor(noisy_label)
+    if lab.dim() != 1 or lab.shape[0] != n:
+        raise ValueError(f"noisy_label: expected {n} labels, got shape {tuple(lab.shape)}")
+    if n and (lab.is_floating_point() or lab.dtype == torch.bool):
+        raise ValueError(f"noisy_label: expected integer class numbers, got {lab.dtype}")
+    if n and (int(lab.min()) < 0 or int(lab.max()) >= C):
+        raise ValueError(f"noisy_label: every label must lie in [0, {C}), got {int(lab.min())} .. {int(lab.max())}")
+    return lab.to(device=device, dtype=torch.int32).contiguous()
+
+
 def d1_normalized(metric, q_img, cls_txt, noisy_label):
     q, c = dev_f32(q_img, "q_img"), dev_f32(cls_txt, "cls_txt")
-    lab = noisy_label.to(device=q.device, dtype=torch.int32).contiguous()
+    if q.dim() != 2 or c.dim() != 2 or q.shape[1] != c.shape[1]:
+        raise ValueError(f"q_img {tuple(q.shape)} and cls_txt {tuple(c.shape)} must be [n, d] and [C, d] with the same d")
+    lab = checked_labels(noisy_label, q.shape[0], c.shape[0], q.device)
     out = torch.empty(q.shape[0], dtype=torch.float32, device=q.device)
     lib = _lib.load()
     with torch.cuda.device(q.device):
