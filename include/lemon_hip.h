@@ -577,6 +577,48 @@ int64_t lemon_jpeg_entropy_workspace_bytes(int64_t batch, int64_t total_groups, 
 int lemon_jpeg_entropy_par_host(const uint8_t *packet, int64_t packet_bytes, int32_t subseq_bytes, uint8_t *record,
                                 int64_t record_cap, int32_t *status);
 
+/* ---- progressive JPEG files (SOF2) on the same path, opt-in: lib/datasets/dataloader.py:167-198 decodes them with PIL like any
+ * other file, and web-scraped caption sets hold many.  A progressive file ends in the same coefficient record as a baseline one,
+ * so lemon_jpeg_decode and lemon_jpeg_reconstruct_host read it unchanged; only the Huffman pass differs: several scans, each
+ * with its own tables and restart interval (csrc/jpeg_prog.hpp, csrc/jpeg_prog_par.hpp).  lemon_jpeg_info, lemon_jpeg_entropy and
+ * lemon_jpeg_pack keep declining SOF2; these accept SOF2 only (a baseline file: status 3).  The host functions are also exported
+ * by liblemon_jpeg_host.so. */
+#define LEMON_JPEG_PROGRESSION 17         /* status: at EOI not every coefficient was sent down to bit 0 (libjpeg would smooth) */
+#define LEMON_JPEG_PROG_PACKET_BOUND 5424 /* packet_cap = n + 2 * (n / 3) + this always suffices (csrc/jpeg_prog_par.hpp) */
+#define LEMON_JPEG_PROG_ITEM 16           /* restart intervals of one scan that one wave decodes */
+/* Header pass of lib/datasets/dataloader.py:167-198's decode for a progressive file: markers up to the first SOS -> geometry and
+ * record size, or the reason it is declined.  Returns info->status.  Host only, no GPU. */
+int lemon_jpeg_prog_info(const uint8_t *data, int64_t n, LemonJpegInfo *info);
+/* The whole host pass for the same call site (lib/datasets/dataloader.py:167-198): all markers and all scans of a progressive
+ * file into `record` (the record of lemon_jpeg_entropy).  Declines whatever libjpeg would warn about and every file whose
+ * progression is incomplete at EOI (LEMON_JPEG_PROGRESSION), see csrc/jpeg_prog.hpp; max_abs and exact_blocks as
+ * lemon_jpeg_entropy.  Every read of `data` is bounds-checked.  Returns info->status.  Host only, no GPU. */
+int lemon_jpeg_prog_entropy(const uint8_t *data, int64_t n, uint8_t *record, int64_t record_cap, LemonJpegInfo *info);
+/* Host, no GPU (lib/datasets/dataloader.py:167-198, in the workers): all header and marker-structure checks of
+ * lemon_jpeg_prog_entropy -- it declines exactly what those decline --, then the packet of csrc/jpeg_prog_par.hpp into
+ * packet[0, packet_cap): geometry, quantisers, the scan table, the Huffman specifications the scans use and every scan's
+ * entropy-coded bytes with FF 00 -> FF and restart markers removed.  *packet_bytes receives its size (a multiple of 16); its head
+ * holds the scan, item and level counts that lemon_jpeg_prog_entropy_device's caller needs (int32 at bytes 24, 32, 36). */
+int lemon_jpeg_prog_pack(const uint8_t *data, int64_t n, uint8_t *packet, int64_t packet_cap, LemonJpegInfo *info,
+                         int64_t *packet_bytes);
+/* Device Huffman pass for a batch of progressive packets (lib/datasets/dataloader.py:167-198 per image;
+ * run_lemon.py:129-131,199-201 per loader batch).  packets_dev / rec_dev as lemon_jpeg_entropy_device.  desc_dev (int64
+ * [batch, 8]): packet offset and bytes, record offset (multiples of 16), first item slot, items of the packet (its head), 0, 0, 0;
+ * total_items is the sum, levels the largest level count of the packets' heads.  One wave decodes one item -- a scan's
+ * LEMON_JPEG_PROG_ITEM consecutive restart intervals --, one launch per level.  status_dev int32 [batch]: 0, a LemonJpegStatus
+ * code, or LEMON_JPEG_BUFFER for an image whose packet, record or item share would leave its buffer or whose scan table is
+ * inconsistent (neither read further nor written).  ws_dev: lemon_jpeg_prog_entropy_workspace_bytes(batch, total_items, levels)
+ * bytes, 16-byte aligned.  A declined image's record is unspecified. */
+int lemon_jpeg_prog_entropy_device(const uint8_t *packets_dev, int64_t packets_bytes, int64_t batch, const int64_t *desc_dev,
+                                   int64_t total_items, int32_t levels, uint8_t *rec_dev, int64_t rec_bytes, int32_t *status_dev,
+                                   void *ws_dev, int64_t ws_bytes, void *stream);
+int64_t lemon_jpeg_prog_entropy_workspace_bytes(int64_t batch, int64_t total_items, int32_t levels); /* < 0: LEMON_E_* */
+/* lemon_jpeg_prog_entropy_device's algorithm with the waves looped on the host -- the same items, levels and step functions, so
+ * the same record and status.  Test support for lib/datasets/dataloader.py:167-198's decode where there is no GPU; no product
+ * path calls it.  Returns 0 unless an argument is invalid. */
+int lemon_jpeg_prog_entropy_par_host(const uint8_t *packet, int64_t packet_bytes, uint8_t *record, int64_t record_cap,
+                                     int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

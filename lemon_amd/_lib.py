@@ -26,6 +26,8 @@ EXPORTS = [
     "lemon_kmeans_assign", "lemon_kmeans_update", "lemon_kmeans_split", "lemon_kmeans_train", "lemon_kmeans_workspace_bytes",
     "lemon_knn_label_disagreement", "lemon_jpeg_info", "lemon_jpeg_entropy", "lemon_jpeg_reconstruct_host", "lemon_jpeg_decode",
     "lemon_jpeg_pack", "lemon_jpeg_entropy_device", "lemon_jpeg_entropy_workspace_bytes", "lemon_jpeg_entropy_par_host",
+    "lemon_jpeg_prog_info", "lemon_jpeg_prog_entropy", "lemon_jpeg_prog_pack", "lemon_jpeg_prog_entropy_device",
+    "lemon_jpeg_prog_entropy_workspace_bytes", "lemon_jpeg_prog_entropy_par_host",
 ]
 
 
@@ -138,6 +140,13 @@ def load():
     lib.lemon_jpeg_entropy_workspace_bytes.argtypes = [c_i64, c_i64, c_i64]
     lib.lemon_jpeg_entropy_workspace_bytes.restype = c_i64
     lib.lemon_jpeg_entropy_par_host.argtypes = [vp, c_i64, ctypes.c_int32, vp, c_i64, ctypes.POINTER(ctypes.c_int32)]
+    lib.lemon_jpeg_prog_info.argtypes = [vp, c_i64, vp]
+    lib.lemon_jpeg_prog_entropy.argtypes = [vp, c_i64, vp, c_i64, vp]
+    lib.lemon_jpeg_prog_pack.argtypes = [vp, c_i64, vp, c_i64, vp, ctypes.POINTER(c_i64)]
+    lib.lemon_jpeg_prog_entropy_device.argtypes = [vp, c_i64, c_i64, vp, c_i64, ctypes.c_int32, vp, c_i64, vp, vp, c_i64, vp]
+    lib.lemon_jpeg_prog_entropy_workspace_bytes.argtypes = [c_i64, c_i64, ctypes.c_int32]
+    lib.lemon_jpeg_prog_entropy_workspace_bytes.restype = c_i64
+    lib.lemon_jpeg_prog_entropy_par_host.argtypes = [vp, c_i64, vp, c_i64, ctypes.POINTER(ctypes.c_int32)]
     _lib = lib
     return lib
 

@@ -5,6 +5,7 @@
 
 #include "jpeg_entropy.hpp"
 #include "jpeg_par.hpp"
+#include "jpeg_prog.hpp"
 
 extern "C" int lemon_jpeg_info(const uint8_t *data, int64_t n, LemonJpegInfo *info) {
     if (!info) return LEMON_JPEG_BUFFER;
@@ -57,4 +58,26 @@ extern "C" int lemon_jpeg_reconstruct_host(const uint8_t *record, int64_t record
                          jpeg_chroma_at(Cr, (int64_t)g.bwc * 8, g.dwc, g.dhc, hs, vs, x, y), o);
         }
     return 0;
+}
+
+// The progressive forms (jpeg_prog.hpp, jpeg_prog_par.hpp): SOF2 only.
+extern "C" int lemon_jpeg_prog_info(const uint8_t *data, int64_t n, LemonJpegInfo *info) {
+    if (!info) return LEMON_JPEG_BUFFER;
+    return lemon_jpeg_prog_info_impl(data, n, info);
+}
+
+extern "C" int lemon_jpeg_prog_entropy(const uint8_t *data, int64_t n, uint8_t *record, int64_t record_cap, LemonJpegInfo *info) {
+    if (!info) return LEMON_JPEG_BUFFER;
+    return lemon_jpeg_prog_entropy_impl(data, n, record, record_cap, info);
+}
+
+extern "C" int lemon_jpeg_prog_pack(const uint8_t *data, int64_t n, uint8_t *packet, int64_t packet_cap, LemonJpegInfo *info,
+                                    int64_t *packet_bytes) {
+    if (!info) return LEMON_JPEG_BUFFER;
+    return lemon_jpeg_prog_pack_impl(data, n, packet, packet_cap, info, packet_bytes);
+}
+
+extern "C" int lemon_jpeg_prog_entropy_par_host(const uint8_t *packet, int64_t packet_bytes, uint8_t *record, int64_t record_cap,
+                                                int32_t *status) {
+    return lemon_jpeg_prog_entropy_par_host_impl(packet, packet_bytes, record, record_cap, status);
 }

@@ -314,43 +314,58 @@ def launch_jpeg_decode(data, layout, poison=None):
 def launch_jpeg_entropy(data, layout, poison=None, return_workspace=False):
     """Enqueue lemon_jpeg_entropy_device on the current stream for the scan packets of a device buffer `data` laid out by a
     jpeg_host.BatchLayout: their coefficient records appear in the buffer's device-only region, where launch_jpeg_decode (to be
-    called after this) reads them.  Returns the int32 device tensor of the packets' statuses, in the order of layout.packets (None
-    without packets).  `poison` (a byte, for tests) pre-fills the records' region and the workspace.  return_workspace=True (for
+    called after this) reads them; progressive packets (layout.prog_packets) go through lemon_jpeg_prog_entropy_device behind the
+    baseline ones.  Returns the int32 device tensor of the packets' statuses, in the order of layout.packets then
+    layout.prog_packets (layout.status_record; None without packets).  `poison` (a byte, for tests) pre-fills the records' region and the workspace.  return_workspace=True (for
     tools/jpeg_entropy_time.py) returns (statuses, the workspace tensor), whose first int32 [n_packets, 4] hold diagnostics
     (csrc/jpeg_entropy.hip::JentWs)."""
     from . import _lib
     import ctypes
     from .ops import stream_ptr
-    if not getattr(layout, "n_packets", 0):
+    n_base, n_prog = getattr(layout, "n_packets", 0), getattr(layout, "n_prog", 0)
+    if not n_base and not n_prog:
         return (None, None) if return_workspace else None
     assert data.is_cuda and data.dtype == torch.uint8 and data.numel() >= layout.total_bytes
     dev = data.device
     with torch.cuda.device(dev):
         lib = _lib.load()
-        need = lib.lemon_jpeg_entropy_workspace_bytes(layout.n_packets, layout.groups, layout.intervals)
+        need = lib.lemon_jpeg_entropy_workspace_bytes(n_base, layout.groups, layout.intervals)
         if need < 0:
             raise _lib.LemonHipError(f"lemon_jpeg_entropy_workspace_bytes: {layout.groups} workgroups, {layout.intervals} intervals")
+        pneed = lib.lemon_jpeg_prog_entropy_workspace_bytes(n_prog, layout.prog_items, layout.prog_levels) if n_prog else 0
+        if pneed < 0:
+            raise _lib.LemonHipError(f"lemon_jpeg_prog_entropy_workspace_bytes: {layout.prog_items} items, {layout.prog_levels} levels")
         ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        status = torch.empty((layout.n_packets,), dtype=torch.int32, device=dev)
+        pws = torch.empty((max(pneed, 16),), dtype=torch.uint8, device=dev)
+        status = torch.empty((n_base + n_prog,), dtype=torch.int32, device=dev)
         if poison is not None:
             ws.fill_(poison)
+            pws.fill_(poison)
             status.fill_(poison)
             data[layout.payload_bytes:layout.decoded_off].fill_(poison)
         base, vp = data.data_ptr(), ctypes.c_void_p
-        _lib.check(lib.lemon_jpeg_entropy_device(vp(base), layout.payload_bytes, layout.n_packets, vp(base + layout.edesc_off),
-                                                 layout.groups, layout.intervals, layout.subseq, vp(base), layout.rec_end,
-                                                 vp(status.data_ptr()), vp(ws.data_ptr()), ws.numel(), stream_ptr(dev)),
-                   "lemon_jpeg_entropy_device")
+        if n_base:
+            _lib.check(lib.lemon_jpeg_entropy_device(vp(base), layout.payload_bytes, n_base, vp(base + layout.edesc_off),
+                                                     layout.groups, layout.intervals, layout.subseq, vp(base), layout.rec_end,
+                                                     vp(status.data_ptr()), vp(ws.data_ptr()), ws.numel(), stream_ptr(dev)),
+                       "lemon_jpeg_entropy_device")
+        if n_prog:                                   # the progressive packets, behind the baseline ones on the same stream
+            _lib.check(lib.lemon_jpeg_prog_entropy_device(vp(base), layout.payload_bytes, n_prog, vp(base + layout.pdesc_off),
+                                                          layout.prog_items, layout.prog_levels, vp(base), layout.rec_end,
+                                                          vp(status.data_ptr() + 4 * n_base), vp(pws.data_ptr()), pws.numel(),
+                                                          stream_ptr(dev)), "lemon_jpeg_prog_entropy_device")
     return (status, ws) if return_workspace else status
 
 
-def decode_jpegs(files, device, fallback=False, poison=None, entropy="host"):
+def decode_jpegs(files, device, fallback=False, poison=None, entropy="host", progressive=False):
     """Decode JPEG files on the GPU -> RaggedImages of `Image.open(f).convert("RGB")`'s pixels, bit for bit.  `files`: paths or
     bytes objects.  entropy="host": the Huffman pass runs here on the host (csrc/jpeg_entropy.hpp), everything after it in
     lemon_jpeg_decode.  entropy="device": the host only strips the files down to scan packets (lemon_jpeg_pack), the Huffman pass
     runs in lemon_jpeg_entropy_device and the statuses are read back once before
     returning.  A file that is declined (progressive, CMYK, not a JPEG, corrupt, ...) raises ValueError, or with fallback=True is
-    decoded by PIL (whose own exception a corrupt file then raises).  The result carries `layout` (jpeg_host.BatchLayout)."""
+    decoded by PIL (whose own exception a corrupt file then raises).  progressive=True: a progressive file is not declined but
+    takes the progressive Huffman pass, on the host (csrc/jpeg_prog.hpp) or on the device (csrc/jpeg_prog.hip) as `entropy`
+    says.  The result carries `layout` (jpeg_host.BatchLayout)."""
     import io
     from PIL import Image
     from . import jpeg_host
@@ -361,15 +376,15 @@ def decode_jpegs(files, device, fallback=False, poison=None, entropy="host"):
         raise TypeError("decode_jpegs needs a CUDA/HIP device: there is no CPU path")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    lay, items, off, sources = jpeg_host.BatchLayout(), [], 0, []
+    lay, items, off, sources = jpeg_host.BatchLayout(), [], 0, {}
     declined = lambda what, status: ValueError(f"{what}: not decodable on the GPU ({jpeg_host.STATUS.get(status, status)})")
     for f in files:
         raw = f if isinstance(f, (bytes, bytearray, memoryview)) else open(f, "rb").read()
         what = "<bytes>" if raw is f else f
         if entropy == "device":
-            rec, info = jpeg_host.pack(bytes(raw))
+            rec, info = jpeg_host.pack(bytes(raw), progressive=progressive)
         else:
-            rec, info = jpeg_host.decode_record(bytes(raw))
+            rec, info = jpeg_host.decode_record(bytes(raw), progressive=progressive)
         if rec is None:
             if not fallback:
                 raise declined(what, info.status)
@@ -380,7 +395,7 @@ def decode_jpegs(files, device, fallback=False, poison=None, entropy="host"):
         else:
             if entropy == "device":
                 lay.add_packet(off, rec)
-                sources.append((what, raw))
+                sources[len(lay.records) - 1] = (what, raw)
             else:
                 lay.add_record(off, rec)
             items.append((off, rec.data))
@@ -399,11 +414,11 @@ def decode_jpegs(files, device, fallback=False, poison=None, entropy="host"):
     if status is not None:
         st = status.cpu().numpy()                                 # (the one read-back)
         for k in np.flatnonzero(st):                              # (rare: the scan itself is corrupt)
-            what, raw = sources[k]
+            what, raw = sources[lay.status_record(k)]
             if not fallback:
                 raise declined(what, int(st[k]))
             px = np.asarray(Image.open(io.BytesIO(raw)).convert("RGB"), dtype=np.uint8)
-            o, h, w, _ = lay.desc[lay.records[lay.packets[k][0]][0]]
+            o, h, w, _ = lay.desc[lay.records[lay.status_record(k)][0]]
             if px.shape != (h, w, 3):
                 raise declined(what, int(st[k]))
             data[o:o + px.size].copy_(torch.from_numpy(px.reshape(-1).copy()))

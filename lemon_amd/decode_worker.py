@@ -9,14 +9,18 @@ decoded with PIL exactly as without RECORDS, PIL's own exception for a corrupt f
 does not even decode Huffman codes: it writes the file's scan packet (lemon_jpeg_pack: markers parsed, byte stuffing removed)
 into the ring, and lemon_jpeg_entropy_device decodes it on the GPU; a file whose header the packer declines goes to PIL.
 
-Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS]`), so that not even the lemon_amd package is imported.
+With PROGRESSIVE = 1 (beside RECORDS 1 or 2) a progressive file is not left to PIL: the progressive host pass writes its record
+(kind 3, the same record) or the progressive packer its packet (kind 4, lemon_jpeg_prog_pack) into the ring.
+
+Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS [PROGRESSIVE]]`), so that not even the lemon_amd package is imported.
 Protocol (pickled frames on stdin / stdout, in order):
   parent -> worker: ("task", seq, path) | ("free", nbytes) | ("stop",)
   worker -> parent: ("hello", pid, torch_imported)
                     ("ok", seq, offset, h, w, consumed, oversize_path or None, kind, nbytes, (components, hs, vs) or None)
                     | ("err", seq, path, message)
 `kind` 0: nbytes = h * w * 3 of RGB pixels; `kind` 1: nbytes of coefficient record; `kind` 2: nbytes of scan packet, with
-(components, hs, vs, intervals, scan_bytes).
+(components, hs, vs, intervals, scan_bytes); `kind` 3: a record from the progressive host pass; `kind` 4: nbytes of progressive
+packet, with (components, hs, vs, scans, items, levels).
 The ring is a circular byte buffer of CAPACITY bytes.  An image is written at `offset` once `consumed` bytes (its own plus the
 unused tail skipped when it wraps) are free; the parent returns them with "free" after it has copied the image, in the order
 the results came.  An image larger than the whole ring waits until the ring is empty and goes to a one-off segment
@@ -39,6 +43,7 @@ def main(argv):
     shm_path, cap = argv[0], int(argv[1])
     records = len(argv) > 2 and argv[2] == "1"
     packets = len(argv) > 2 and argv[2] == "2"
+    progressive = len(argv) > 3 and argv[3] == "1"
     if records or packets:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import jpeg_host
@@ -89,17 +94,19 @@ def main(argv):
                     data = fh.read()
             except OSError:
                 pass                    # (PIL below reports it)
-            if data is not None and data[:2] == b"\xff\xd8" and jpeg_host.packet_cap(len(data)) + 15 <= cap:
-                need = jpeg_host.packet_cap(len(data)) + 15
+            prog = progressive and data is not None and jpeg_host.info(data).status == 3
+            need = (jpeg_host.prog_packet_cap(len(data)) if prog else jpeg_host.packet_cap(len(data))) + 15 if data is not None else 0
+            if data is not None and data[:2] == b"\xff\xd8" and need <= cap:
                 off, consumed = reserve(need)
                 at = (off + 15) & ~15
-                pk, full = jpeg_host.pack(data, view[at:at + need - 15])
+                pk, full = (jpeg_host.prog_pack if prog else jpeg_host.pack)(data, view[at:at + need - 15])
                 if pk is not None:
                     took = at - off + pk.data.nbytes
                     head = off + took
                     used += consumed - (need - took)
-                    _send(out, ("ok", seq, at, full.height, full.width, consumed - (need - took), None, 2, pk.data.nbytes,
-                                (full.components, full.hs, full.vs, pk.intervals, pk.scan_bytes)))
+                    meta = (pk.scans, pk.items, pk.levels) if prog else (pk.intervals, pk.scan_bytes)
+                    _send(out, ("ok", seq, at, full.height, full.width, consumed - (need - took), None, 4 if prog else 2, pk.data.nbytes,
+                                (full.components, full.hs, full.vs) + meta))
                     continue
             del data
         if records:
@@ -113,15 +120,18 @@ def main(argv):
                 pass                    # (PIL below reports it)
             if data is not None and data[:2] == b"\xff\xd8":
                 head_info = jpeg_host.info(data)
+                prog = progressive and head_info.status == 3
+                if prog:
+                    head_info = jpeg_host.prog_info(data)
                 n = head_info.record_bytes
                 if head_info.status == 0 and n + 15 <= cap:
                     off, consumed = reserve(n + 15)         # (the record's int16 blocks start at a multiple of 16)
                     at = (off + 15) & ~15
-                    full = jpeg_host.entropy(data, view[at:at + n])
+                    full = (jpeg_host.prog_entropy if prog else jpeg_host.entropy)(data, view[at:at + n])
                     if full.status == 0:
                         head = off + n + 15
                         used += consumed
-                        _send(out, ("ok", seq, at, full.height, full.width, consumed, None, 1, n, (full.components, full.hs, full.vs)))
+                        _send(out, ("ok", seq, at, full.height, full.width, consumed, None, 3 if prog else 1, n, (full.components, full.hs, full.vs)))
                         continue
             del data
         try:

@@ -26,7 +26,7 @@ import uuid
 
 import numpy as np
 
-from .jpeg_host import BatchLayout, JpegPacket, JpegRecord
+from .jpeg_host import BatchLayout, JpegPacket, JpegProgPacket, JpegProgRecord, JpegRecord
 
 _WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_worker.py")
 DEFAULT_RING_BYTES = 1 << 30
@@ -60,6 +60,17 @@ def device_jpeg_default():
     raise ValueError(f"LEMON_JPEG={env!r}: expected 'pil', 'gpu' or 'device'")
 
 
+def progressive_default():
+    """Whether file batches send progressive JPEGs through the progressive Huffman pass: LEMON_JPEG_PROGRESSIVE=1 (default 0:
+    PIL decodes them in the workers).  Ignored under LEMON_JPEG=pil."""
+    env = os.environ.get("LEMON_JPEG_PROGRESSIVE", "").strip()
+    if env in ("", "0"):
+        return False
+    if env == "1":
+        return True
+    raise ValueError(f"LEMON_JPEG_PROGRESSIVE={env!r}: expected '0' or '1'")
+
+
 def default_workers(world=1):
     """LEMON_DECODE_WORKERS when set (0 = the in-process thread path), else min(8, usable_cpus() // world), at least 1."""
     env = os.environ.get("LEMON_DECODE_WORKERS", "").strip()
@@ -77,10 +88,12 @@ class DecodePool:
     view valid until the next item is requested.  With records=True a baseline JPEG the host pass accepts is yielded as
     (i, JpegRecord) instead -- its coefficient record, `data` a view of shared memory under the same rule -- and every other
     file as pixels.  With packets=True a baseline JPEG whose header the packer accepts is yielded as (i, JpegPacket): its scan
-    packet for lemon_jpeg_entropy_device."""
+    packet for lemon_jpeg_entropy_device.  progressive=True (with records or packets): a progressive JPEG is not left to PIL
+    but yielded as (i, JpegProgRecord) -- the same record, from the progressive host pass -- or (i, JpegProgPacket)."""
 
-    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False, packets=False):
+    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False, packets=False, progressive=False):
         self.paths = list(paths)
+        self.progressive = bool(progressive)
         self.n_workers = default_workers(world) if workers is None else int(workers)
         self.records, self.packets = bool(records) and not packets, bool(packets)
         assert self.n_workers >= 1
@@ -102,7 +115,8 @@ class DecodePool:
                 os.ftruncate(fd, self.cap)
                 self.rings.append(np.frombuffer(mmap.mmap(fd, self.cap), np.uint8))
                 os.close(fd)
-                self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap), "2" if self.packets else "1" if self.records else "0"], stdin=subprocess.PIPE,
+                self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap), "2" if self.packets else "1" if self.records else "0",
+                                                    "1" if self.progressive else "0"], stdin=subprocess.PIPE,
                                                    stdout=subprocess.PIPE, close_fds=True))
             for p in self.procs:
                 msg = self._read(p, "worker start")
@@ -139,7 +153,7 @@ class DecodePool:
                 raise DecodeError(f"cannot decode image {msg[2]}: {msg[3]}")
             _, seq, off, h, w, consumed, big, kind, n, meta = msg
             assert seq == i, (seq, i)
-            assert kind in (1, 2) or n == h * w * 3, (kind, n, h, w)
+            assert kind in (1, 2, 3, 4) or n == h * w * 3, (kind, n, h, w)
             if big is not None:
                 import mmap
                 fd = os.open(big, os.O_RDONLY)
@@ -151,7 +165,8 @@ class DecodePool:
                 self.held += consumed
                 self.peak_held = max(self.peak_held, self.held)
             last = (k, consumed, big)
-            yield i, (JpegRecord(arr, w, h, *meta) if kind == 1 else JpegPacket(arr, w, h, *meta) if kind == 2 else arr.reshape(h, w, 3))
+            made = {1: JpegRecord, 2: JpegPacket, 3: JpegProgRecord, 4: JpegProgPacket}.get(kind)
+            yield i, (made(arr, w, h, *meta) if made else arr.reshape(h, w, 3))
         if last is not None:
             self._release(*last)
 
@@ -200,7 +215,7 @@ class DecodePool:
 
 
 def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, stats=None, slots=3,
-                   device_jpeg=None):
+                   device_jpeg=None, progressive=None):
     """Yield (s, e, RaggedImages of paths[s:e]) over paths[lo:hi] in chunks of `chunk` images, decoded by a DecodePool.
 
     A packing thread copies each chunk's decoded images out of the workers' rings into one of `slots` pinned staging buffers
@@ -218,7 +233,9 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
     enqueued behind the chunk's copy on a stream of their own, and the chunk is handed out after its status event, when the
     compute stream joins that stream, while the next chunk is already enqueued; an
     image the device declines is read again from its path, decoded by PIL here and copied into its RGB slot (a file PIL cannot
-    decode raises DecodeError as in pil mode).  The pool closes (workers exit, segments
+    decode raises DecodeError as in pil mode).  `progressive` (None: LEMON_JPEG_PROGRESSIVE=1; ignored in pil mode): progressive
+    files are not left to PIL in the workers but take the progressive Huffman pass, in the workers (gpu) or on the device behind
+    the baseline pass (device); stats["jpeg_progressive"] counts them.  The pool closes (workers exit, segments
     unlinked) when the generator ends, is closed early or raises."""
     import queue
     import threading
@@ -230,6 +247,9 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
     if device_jpeg is None:
         device_jpeg = device_jpeg_default()
     packets = device_jpeg == "device"
+    if progressive is None:
+        progressive = progressive_default()
+    progressive = bool(progressive) and bool(device_jpeg)
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -287,13 +307,13 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     t1 = time.perf_counter()
                     if stats is not None:
                         stats["pool_wait_s"] = stats.get("pool_wait_s", 0.0) + t1 - t0
-                    src = a.data if isinstance(a, (JpegRecord, JpegPacket)) else a.reshape(-1)
+                    src = a.data if isinstance(a, (JpegRecord, JpegPacket, JpegProgRecord, JpegProgPacket)) else a.reshape(-1)
                     need = off + src.nbytes
                     buf = room(buf, off, need)
                     np.copyto(buf.numpy()[off:need], src)
-                    if isinstance(a, JpegPacket):
+                    if isinstance(a, (JpegPacket, JpegProgPacket)):
                         lay.add_packet(off, a)
-                    elif isinstance(a, JpegRecord):
+                    elif isinstance(a, (JpegRecord, JpegProgRecord)):
                         lay.add_record(off, a)
                     else:
                         lay.add_pixels(off, a.shape[0], a.shape[1])
@@ -320,7 +340,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                 stats["status_wait_s"] = stats.get("status_wait_s", 0.0) + time.perf_counter() - t0
             for k in np.flatnonzero(status.numpy()):
                 from PIL import Image
-                i = lay.records[lay.packets[k][0]][0]
+                i = lay.records[lay.status_record(k)][0]
                 o, h, w, _ = lay.desc[i]
                 try:
                     px = np.asarray(Image.open(paths[s + i]).convert("RGB"), dtype=np.uint8)
@@ -333,7 +353,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     stats["jpeg_fallback"] = stats.get("jpeg_fallback", 0) + 1
         return s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
 
-    with DecodePool(paths, workers, ring_bytes, world, records=bool(device_jpeg), packets=packets) as pool:
+    with DecodePool(paths, workers, ring_bytes, world, records=bool(device_jpeg), packets=packets, progressive=progressive) as pool:
         th = threading.Thread(target=pack, args=(pool,), daemon=True)
         th.start()
         pending, n_chunks, pinned_status = None, 0, [None, None, None]
@@ -367,6 +387,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                 if timed:
                     stats.setdefault("h2d", []).append((t0, ev, off))
                     stats["jpeg_images"] = stats.get("jpeg_images", 0) + lay.n_jpeg
+                    stats["jpeg_progressive"] = stats.get("jpeg_progressive", 0) + lay.n_progressive
                 if not packets:
                     launch_jpeg_decode(data, lay)        # (on the current stream, after the copy's event; nothing without records)
                     yield s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))

@@ -15,6 +15,9 @@ Writes N seeded JPEGs (PIL, quality 90, 4:2:0) per size mix to a temp dir and pr
   --jpeg gpu|pil|device    from-files and pool figures with baseline JPEGs decoded on the GPU (gpu: the workers run only the
                            Huffman pass; device: the workers only write scan packets, the Huffman pass runs on the GPU too) or
                            by PIL in the workers (LEMON_JPEG); default: the library's default
+  --progressive K          every K-th file is written progressive (1 = all, 4 = one in four); --progressive_switch 0|1 sets
+                           LEMON_JPEG_PROGRESSIVE for the run (0: those files are decoded by PIL in the workers, as before the
+                           switch existed); the line then carries progressive_files, jpeg_progressive and the switch
 Every timed region is bracketed by a device synchronise.  Needs a HIP device.
 
   python tools/file_pipeline_time.py --arch vit-b-16 --n 2048 --out profiles/r6/file_pipeline.jsonl
@@ -36,7 +39,7 @@ MIXES = {
 }
 
 
-def write_jpegs(d, mix, n, seed=0, reuse=False):
+def write_jpegs(d, mix, n, seed=0, reuse=False, progressive_every=0):
     from PIL import Image
     rng = np.random.default_rng(seed)
     paths = []
@@ -49,11 +52,12 @@ def write_jpegs(d, mix, n, seed=0, reuse=False):
         yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
         base = 128 + 90 * np.sin(yy[..., None] / rng.uniform(5, 40) + xx[..., None] / rng.uniform(5, 40) + np.arange(3))
         px = np.clip(base + rng.normal(0, 12, (h, w, 1)), 0, 255).astype(np.uint8)
-        p = os.path.join(d, f"{mix}_{i:05d}.jpg")
+        prog = bool(progressive_every) and i % progressive_every == 0
+        p = os.path.join(d, f"{mix}_{i:05d}{'_p' if prog else ''}.jpg")
         if reuse and os.path.exists(p):          # (the random draws above still advance: file i is the same in every run)
             paths.append(p)
             continue
-        Image.fromarray(px).save(p, quality=90, subsampling=2)
+        Image.fromarray(px).save(p, quality=90, subsampling=2, progressive=prog)
         paths.append(p)
     return paths
 
@@ -67,12 +71,16 @@ def main(argv=None):
     ap.add_argument("--mixes", default="mscoco,cars")
     ap.add_argument("--workers", type=int, default=None)
     ap.add_argument("--jpeg", choices=("gpu", "pil", "device"), default=None)
+    ap.add_argument("--progressive", type=int, default=0, help="every K-th file is progressive (0: none)")
+    ap.add_argument("--progressive_switch", choices=("0", "1"), default=None, help="LEMON_JPEG_PROGRESSIVE for this run")
     ap.add_argument("--skip_threads", action="store_true", help="leave out the LEMON_DECODE_WORKERS=0 figure")
     ap.add_argument("--keep_dir", default=None, help="write the JPEGs here and keep them; files already there are reused")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if a.jpeg:
         os.environ["LEMON_JPEG"] = a.jpeg
+    if a.progressive_switch is not None:
+        os.environ["LEMON_JPEG_PROGRESSIVE"] = a.progressive_switch
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("file_pipeline_time.py needs a HIP device")
@@ -88,6 +96,7 @@ def main(argv=None):
     emb = Embedder(LemonCLIP(cfg), dev, batch_size=a.batch)
     workers = a.workers if a.workers is not None else loader.default_workers(1)
     jpeg_gpu = loader.device_jpeg_default()
+    prog_on = bool(jpeg_gpu) and loader.progressive_default()
     lines = []
     if a.keep_dir:
         os.makedirs(a.keep_dir, exist_ok=True)
@@ -96,7 +105,8 @@ def main(argv=None):
         for mix in a.mixes.split(","):
             n = a.n if mix == "mscoco" else a.n_cars
             t0 = time.perf_counter()
-            paths = write_jpegs(tmp, mix, n, reuse=bool(a.keep_dir))
+            paths = write_jpegs(tmp, mix, n, reuse=bool(a.keep_dir), progressive_every=a.progressive)
+            n_prog = len(range(0, n, a.progressive)) if a.progressive else 0
             write_s = time.perf_counter() - t0
             # decode pool alone (pixels: what the resident figure needs)
             t0 = time.perf_counter()
@@ -107,10 +117,10 @@ def main(argv=None):
             decode_s = pixels_decode_s = time.perf_counter() - t0
             if jpeg_gpu:                             # ... and as the from-files path runs it: coefficient records
                 t0 = time.perf_counter()
-                with loader.DecodePool(paths, workers, records=True, packets=jpeg_gpu == "device") as pool:
-                    n_rec = sum(isinstance(x, (loader.JpegRecord, loader.JpegPacket)) for _, x in pool.images())
+                with loader.DecodePool(paths, workers, records=True, packets=jpeg_gpu == "device", progressive=prog_on) as pool:
+                    n_rec = sum(not isinstance(x, np.ndarray) for _, x in pool.images())
                 decode_s = time.perf_counter() - t0
-                assert n_rec == n, (n_rec, n)
+                assert n_rec == (n if prog_on else n - n_prog), (n_rec, n, n_prog)
             # resident: pre-decoded uint8 in HBM
             chunks = [RaggedImages.from_arrays(decoded[s:s + a.batch], dev) for s in range(0, n, a.batch)]
             del decoded
@@ -182,6 +192,7 @@ def main(argv=None):
                        threads_path_images_per_s=nt / threads_s if nt else None, threads_path_images=nt,
                        jpeg="device" if jpeg_gpu == "device" else "gpu" if jpeg_gpu else "pil", pil_pool_images_per_s=n / pixels_decode_s,
                        jpeg_images=stats.get("jpeg_images", 0), jpeg_fallback=stats.get("jpeg_fallback", 0),
+                       progressive_files=n_prog, progressive_switch=int(prog_on), jpeg_progressive=stats.get("jpeg_progressive", 0),
                        from_files_s=files_s, pool_wait_s=stats.get("pool_wait_s"), ready_wait_s=stats.get("ready_wait_s"),
                        status_wait_s=stats.get("status_wait_s", 0.0), pack_s=stats["pack_s"],
                        device=torch.cuda.get_device_name(0))
