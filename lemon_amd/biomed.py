@@ -196,7 +196,8 @@ class BertTextTower(nn.Module):
 
     def _masked(self, ids):
         """HF's own formulation (key mask = ids != pad), plain PyTorch: the CPU / autograd path, and on the GPU only rows with
-        padding INSIDE the caption (no tokenizer produces them)."""
+        padding INSIDE the caption (a literal "[PAD]" in the text: tokenizer.BertWordPiece keeps it as the pad id; forward() finds
+        them itself, pipeline.Embedder -- which passes `lengths` -- keeps them out of those calls and hands them over here)."""
         B, L = ids.shape
         x = self.emb_ln(self.tok(ids) + self.type_emb[0] + self.pos[:L])
         key_ok = (ids != self.pad_token_id)[:, None, None, :]
@@ -229,7 +230,8 @@ class BertTextTower(nn.Module):
 
     def forward(self, input_ids, seq_len=None, lengths=None):
         """input_ids [B, ctx] -> [B, embed_dim].  lengths: per-row token counts on the HOST when the caller has them
-        (pipeline.Embedder), saving the device read here; seq_len: accepted for the CLIP towers' signature (their bucketed length)."""
+        (pipeline.Embedder), saving the device read here -- the caller then vouches that no row has padding inside;
+        seq_len: accepted for the CLIP towers' signature (their bucketed length)."""
         fused = input_ids.is_cuda and self.pos.dtype == torch.float32 and not torch.is_grad_enabled() and self.pos.shape[-1] % 4 == 0
         if not fused:
             L = int(self.last_token_index(input_ids).max()) + 1 if input_ids.shape[0] else 1

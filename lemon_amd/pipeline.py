@@ -236,13 +236,13 @@ class Embedder:
 
     @torch.no_grad()
     def embed_texts(self, input_ids):
-        eot = None if input_ids.is_cuda else self._last_token(input_ids)    # host ids: EOT positions without a sync
+        eot, inner = (None, None) if input_ids.is_cuda else self._caption_marks(input_ids)    # host ids: EOT positions without a sync
         input_ids = input_ids.to(self.device)
         if self.text_dedup:
             uniq, inv = torch.unique(input_ids, dim=0, return_inverse=True)
             e = self._embed_texts(uniq)[inv]
         else:
-            e = self._embed_texts(input_ids, eot)
+            e = self._embed_texts(input_ids, eot, inner)
         return ops.normalize_vectors(self._note(e)) if e.shape[0] else e              # :163 / :230-232
 
     def _last_token(self, ids):
@@ -251,14 +251,40 @@ class Embedder:
         tower = getattr(self.model, "text", None)
         return tower.last_token_index(ids) if hasattr(tower, "last_token_index") else ids.argmax(dim=-1)
 
-    def _embed_texts(self, ids, eot=None):
+    def _caption_marks(self, ids):
+        """-> (eot, inner) on the HOST, in one transfer when ids are on the device: per row the index of the last token and, for
+        a tower that runs every caption un-padded at its own length (biomed.BertTextTower: no key mask in the attention kernels),
+        whether a pad id lies INSIDE the caption -- a literal "[PAD]" in the text is tokenised to it.  inner is None for the
+        other towers."""
+        tower = getattr(self.model, "text", None)
+        last = self._last_token(ids)
+        if not (getattr(tower, "exact_lengths", False) and hasattr(tower, "pad_token_id")):
+            return last.cpu(), None
+        marks = torch.stack([last, (ids != tower.pad_token_id).sum(-1)]).cpu()
+        return marks[0], marks[1] != marks[0] + 1
+
+    def _embed_texts(self, ids, eot=None, inner=None):
         """ids on the device; eot = per-row EOT position on the HOST (one transfer for the whole array instead of a
-        device sync per micro-batch) from which each micro-batch's bucketed token count is taken."""
+        device sync per micro-batch) from which each micro-batch's bucketed token count is taken; inner = per-row "padding
+        inside the caption" on the host (_caption_marks), taken together with eot when eot is not given."""
         if ids.shape[0] == 0:
             return torch.empty((0, self.model.cfg.embed_dim), device=self.device)
         tower = getattr(self.model, "text", None)
         if eot is None and hasattr(tower, "seq_len_for"):
-            eot = self._last_token(ids).cpu()
+            eot, inner = self._caption_marks(ids)
+        if inner is not None and bool(inner.any()):
+            # such a caption must not run un-padded at "its length" (the pad would be attended to like a word): it takes the
+            # tower's key-masked formulation, the clean captions are grouped and batched exactly as if it were not there
+            held, clean = inner.nonzero().flatten(), (~inner).nonzero().flatten()
+            out = torch.empty((ids.shape[0], self.model.cfg.embed_dim), dtype=torch.float32, device=ids.device)
+            if clean.numel():
+                out[clean.to(ids.device)] = self._embed_texts(ids[clean.to(ids.device)], eot[clean], inner[clean]).float()
+            for i in range(0, held.numel(), self.text_batch_size):
+                sel = held[i:i + self.text_batch_size]
+                L = tower.seq_len_for(int(eot[sel].max()))
+                self.text_tokens_run += int(L) * int(sel.numel())
+                out[sel.to(ids.device)] = tower._masked(ids[sel.to(ids.device)][:, :L]).float()
+            return out
         bucketed = eot is not None and hasattr(tower, "seq_len_for")
         # a tower without a padding mask in its kernels (BERT: bidirectional attention) runs every caption at exactly its own
         # length: its micro-batches must be single-length groups, so its captions are always sorted

@@ -118,3 +118,39 @@ def test_embedder_groups_captions_by_exact_length(monkeypatch):
     assert [s for s, _ in seen] == [2, 4, 9, 9, 24] and all(set(l) == {s} for s, l in seen) and [len(l) for _, l in seen] == [1, 2, 3, 2, 1]
     assert emb.text_tokens_run == sum(lens)
     assert (out - real(ids)).abs().max() < 1e-5
+
+
+def test_embedder_keeps_captions_with_padding_inside_out_of_the_length_groups(monkeypatch):
+    """A caption with a pad id inside never reaches encode_text(lengths=...) -- that call runs rows un-padded, the pad would be
+    attended to like a word --: it takes the tower's key-masked formulation, its tokens are counted once, and the clean captions
+    are grouped exactly as if it were not there."""
+    from lemon_amd.pipeline import Embedder
+    _, _, ours = hf_pair("tiny", seed=7)
+    emb = Embedder.__new__(Embedder)
+    emb.model, emb.device, emb.text_batch_size, emb.length_bucketing, emb.range_fallback, emb.text_tokens_run = ours, torch.device("cpu"), 3, False, False, 0
+    emb.text_token_budget = None
+    lens = [9, 4, 9, 2, 9, 9, 4, 24, 9, 12]
+    ids = caption_ids(ours.cfg, lens)
+    ids[2, 3] = ids[7, 1] = ids[9, 4] = ids[9, 8] = ours.cfg.pad_token_id
+    eot, inner = emb._caption_marks(ids)
+    assert eot.tolist() == [n - 1 for n in lens] and inner.tolist() == [r in (2, 7, 9) for r in range(len(lens))]
+    seen, masked = [], []
+    real, real_masked = ours.encode_text, ours.text._masked
+
+    def spy(rows, seq_len=None, lengths=None, **kw):
+        assert bool(((rows != ours.cfg.pad_token_id).sum(-1) == lengths).all())
+        seen.append((int(seq_len), lengths.tolist()))
+        return real(rows)
+
+    def spy_masked(rows):
+        masked.append(tuple(rows.shape))
+        return real_masked(rows)
+
+    monkeypatch.setattr(ours, "encode_text", spy)
+    monkeypatch.setattr(ours.text, "_masked", spy_masked)
+    out = emb._embed_texts(ids)
+    assert [s for s, _ in seen] == [2, 4, 9, 9] and [len(l) for _, l in seen] == [1, 2, 3, 1]
+    assert masked[-1] == (3, 24) and len(masked) == len(seen) + 1         # (on the CPU every group ends in _masked: one call more)
+    assert emb.text_tokens_run == sum(lens[r] for r in (0, 1, 3, 4, 5, 6, 8)) + 3 * 24
+    monkeypatch.undo()
+    assert (out - ours.text._masked(ids[:, :24])).abs().max() < 1e-5

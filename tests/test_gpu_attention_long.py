@@ -11,11 +11,9 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from .attention_ref import OUT_FILL, TAIL, TM, _arith, _reference64, _tiled_index
 
-TAIL = 1024                   # canary words (4 KB) behind every output
-OUT_FILL = 0x7FF17FF1         # an fp32 NaN = two fp16 NaNs = two bf16 NaNs
-TM = 128
+pytestmark = pytest.mark.gpu
 
 LONG_SHAPES = [(1, 289, 3, False), (2, 577, 16, False), (1, 577, 12, True), (2, 512, 8, True), (1, 1025, 12, False),
                (1, 2049, 2, True), (1, 4096, 1, False)]
@@ -35,28 +33,6 @@ def _p(t):
 
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class _arith:
-    """with _arith(f16): the attention arithmetic of the calling thread, restored on exit"""
-
-    def __init__(self, f16):
-        self.f16 = f16
-
-    def __enter__(self):
-        self.prev = _lib().lemon_attention_set_f16(self.f16)
-
-    def __exit__(self, *a):
-        _lib().lemon_attention_set_f16(self.prev)
-
-
-def _reference64(qkv, H, causal):
-    B, L, _ = qkv.shape
-    q, k, v = qkv.double().view(B, L, 3, H, 64).permute(2, 0, 3, 1, 4)
-    s = q @ k.transpose(-1, -2) / 8.0
-    if causal:
-        s = s.masked_fill(torch.ones(L, L, dtype=torch.bool).triu(1), float("-inf"))
-    return (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B, L, 64 * H)
 
 
 # ---- 1. float64 reference beyond 288 tokens --------------------------------------------------------------------------------
@@ -115,15 +91,6 @@ def test_streaming_output_forms_equal_split_of_attention(hip, B, L, H, causal, f
 
 
 # ---- 4. nothing outside the result is written, nothing depends on neighbours -------------------------------------------------
-def _tiled_index(m, width):
-    """[m, width] offsets (in halves) of the hi part of every element of a tile-major activation operand (split3.hpp tiled_off);
-    the lo part sits TM * 16 halves further"""
-    r = torch.arange(m, device="cuda", dtype=torch.int64)[:, None]
-    c = torch.arange(width, device="cuda", dtype=torch.int64)[None, :]
-    tile, rr = r // TM, r % TM
-    return ((tile * (width >> 4) + (c >> 4)) * 2) * (TM * 16) + (rr >> 5) * 512 + ((c >> 3) & 1) * 256 + (rr & 31) * 8 + (c & 7)
-
-
 @pytest.mark.parametrize("f16", [1, 0])
 @pytest.mark.parametrize("B,L,H,causal", [(3, 577, 2, False), (2, 300, 3, True), (1, 1025, 1, True)])
 def test_streaming_attention_writes_exactly_its_result(hip, B, L, H, causal, f16):

@@ -150,6 +150,44 @@ def test_embedder_runs_every_caption_at_its_own_length(hip):
     assert float((emb.embed_images(u8).cpu() - ref_i).abs().max()) <= 1e-5
 
 
+def _captions_with_inner_pads(cfg):
+    """20 captions of mixed lengths; rows 3, 8, 12 and 17 carry the pad id INSIDE (a literal "[PAD]" in the text): two at lengths
+    that clean captions have too, one with two pads, one with the pad right behind [CLS]"""
+    lens = [9, 4, 17, 9, 2, 30, 17, 12, 17, 40, 5, 9, 23, 12, 7, 30, 4, 6, 21, 12]
+    ids = caption_ids(cfg, lens, seed=11)
+    pad = cfg.pad_token_id
+    ids[3, 4] = pad                   # 9 tokens, like rows 0 and 11
+    ids[8, 10] = pad                  # 17 tokens, like rows 2 and 6
+    ids[12, 5] = ids[12, 14] = pad    # two pads
+    ids[17, 1] = pad                  # at position 1
+    return ids, lens, [3, 8, 12, 17]
+
+
+def test_embedder_masks_padding_inside_a_caption_like_hf(hip):
+    # the attention kernels take no key mask: a caption with a pad id inside must not run un-padded "at its length" on the
+    # Embedder path (which hands the tower host-side lengths), it takes the tower's key-masked formulation
+    from lemon_amd.pipeline import Embedder
+    vit, bert, ours = hf_pair("mid", seed=3)
+    ids, lens, held = _captions_with_inner_pads(ours.cfg)
+    ref = torch.nn.functional.normalize(hf_text_features(bert, ours, ids), dim=1)
+    emb = Embedder(ours, torch.device("cuda"), batch_size=4, text_batch_size=6)
+    got = emb.embed_texts(ids).cpu()
+    emb.raise_if_nonfinite()
+    # (the four run as one key-masked micro-batch at the longest one's length: counted once, as the rows they ran)
+    assert emb.text_tokens_run == sum(lens[r] for r in range(len(lens)) if r not in held) + len(held) * max(lens[r] for r in held)
+    assert emb.fallback_rows == 0 and emb.fold_fallback_rows == 0
+    diff = (got - ref).abs().amax(dim=1)
+    print("embedder inner pads: unit-norm max abs diff per caption", [f"{float(d):.2e}" for d in diff], "rows with pads inside:", held)
+    assert float(diff.max()) <= 1e-5, diff
+    clean = [r for r in range(len(lens)) if r not in held]
+    for on_device in (False, True):                     # host ids and device ids find the rows the same way
+        emb2 = Embedder(ours, torch.device("cuda"), batch_size=4, text_batch_size=6)
+        alone = emb2.embed_texts(ids[clean].cuda() if on_device else ids[clean]).cpu()
+        assert emb2.text_tokens_run == sum(lens[r] for r in clean)
+        assert torch.equal(got[clean], alone), on_device
+    assert torch.equal(emb.embed_texts(ids.cuda()).cpu(), got)
+
+
 def test_cli_runs_biomed_clip_on_the_synthetic_mimic_stand_in(hip, tmp_path):
     from lemon_amd.run_lemon import main
     out = str(tmp_path / "run")
