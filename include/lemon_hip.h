@@ -142,7 +142,7 @@ int lemon_preprocess_ragged(const uint8_t *data_dev, int64_t data_bytes, int64_t
  * lib/models/chexzero_clip.py:191-212 with the causal mask of :348-354 for text).
  * qkv_dev [batch, seq_len, 3, heads, head_dim] float32 = the fused q/k/v projection output;
  * out_dev [batch, seq_len, heads*head_dim] = softmax(q k^T / sqrt(head_dim) [+ causal]) v with heads
- * concatenated, ready for the output projection.  head_dim must be 64, seq_len <= LEMON_ATTENTION_MAX_SEQ.
+ * concatenated, ready for the output projection.  head_dim must be 64 (72 .. 128 behind lemon_attention_set_head_dims), seq_len <= LEMON_ATTENTION_MAX_SEQ.
  * seq_len <= 288: one workgroup per (batch, head), K and V of the head staged in LDS once.  Beyond 288 (the 577 tokens of
  * ViT-L/14@336, 1025 at 448 px, long text contexts): the streaming kernels -- query tiles dealt to several workgroups per
  * (batch, head), the keys passing through LDS in blocks of 128 -- with the same arithmetic per key tile, in every output form.
@@ -162,6 +162,18 @@ int lemon_attention_set_f16(int on);
  * kernels hold), accepted 64 .. 288 (anything else: LEMON_E_INVALID, nothing changes); returns the previous value.  The two
  * families give the same bits; the switch exists for the test of that and for A/B timing. */
 int lemon_attention_set_stream_min(int seq_len);
+/* Head dims other than 64, for the calling thread (opt-in; $LEMON_ATTN_HEAD_DIMS = 1 or 2 starts every thread there, default 0):
+ *   0  head_dim must be 64: every lemon_attention_* entry point refuses anything else and writes nothing;
+ *   1  head_dim a multiple of 8 in 72 .. 128 (ViT-H/14: 80, g/14: 88, bigG/14: 104) is accepted by all four entry points and
+ *      runs one streaming kernel for every seq_len <= LEMON_ATTENTION_MAX_SEQ -- fp32 arithmetic (v_mfma_f32_32x32x2_f32)
+ *      under BOTH selections of lemon_attention_set_f16, no input range limit; 64 * 3 * heads * head_dim * 4 < 2^32.  The
+ *      split and tile-major output forms have heads*head_dim columns.  head_dim 64 keeps its kernels and their bits;
+ *   2  as 1, and head_dim 64 runs that kernel too (bit-identical to the fp32-arithmetic kernels; for the test of that and
+ *      for A/B timing).
+ * Any other mode: LEMON_E_INVALID, nothing changes.  Returns the previous mode. */
+int lemon_attention_set_head_dims(int mode);
+/* The calling thread's current mode. */
+int lemon_attention_get_head_dims(void);
 /* The same attention with the result written as the 3-way bf16 split activation operand of lemon_linear_bf16x6 (below):
  * out6_dev [batch*seq_len, 6*heads*64] bf16, 16-byte aligned.  The fp32 result is split at the store, not recomputed. */
 int lemon_attention_split3(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,

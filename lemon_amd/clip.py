@@ -47,6 +47,7 @@ class ClipConfig:
     context_length: int = 77
     eos_token_id: int = 49407
     layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"      # the MLP activation of both towers: 'quick_gelu' (OpenAI's CLIP) or 'gelu' (LAION's checkpoints)
 
     @staticmethod
     def named(name):
@@ -66,6 +67,10 @@ class ClipConfig:
                               text=TowerConfig(768, 12, 12, 3072))
         if name in ("vit-b-16-384", "vit-base-patch16-384", "b16-384"):
             return ClipConfig(image_size=384, patch_size=16)
+        # head_dim 80: ops.attention_supported
+        if name in ("vit-h-14", "vit-huge-patch14", "h14"):
+            return ClipConfig(embed_dim=1024, patch_size=14, vision=TowerConfig(1280, 32, 16, 5120),
+                              text=TowerConfig(1024, 24, 16, 4096), hidden_act="gelu")
         if name in ("chexzero-scratch-256", "mimic-clip-from-scratch", "scratch-b16-256"):
             # lib/models/chexzero_clip.py:458-470 load_clip(): ViT-B/16 vision, 512-wide text, 768-d, context 256
             return ClipConfig(embed_dim=768, patch_size=16, context_length=256)
@@ -79,7 +84,13 @@ class ClipConfig:
     @staticmethod
     def from_hf_dict(c):
         v, t = c["vision_config"], c["text_config"]
+        act, act_t = v.get("hidden_act", "quick_gelu"), t.get("hidden_act", "quick_gelu")
+        if act != act_t:
+            raise ValueError(f"vision hidden_act {act!r} and text hidden_act {act_t!r} differ: one activation serves both towers")
+        if act not in ("quick_gelu", "gelu"):
+            raise ValueError(f"hidden_act {act!r}: expected quick_gelu or gelu")
         return ClipConfig(
+            hidden_act=act,
             embed_dim=c.get("projection_dim", 512), image_size=v.get("image_size", 224),
             patch_size=v.get("patch_size", 32),
             vision=TowerConfig(v.get("hidden_size", 768), v.get("num_hidden_layers", 12),
@@ -92,7 +103,9 @@ class ClipConfig:
     @staticmethod
     def from_openai_state_dict(sd):
         """Architecture of an OpenAI-format CLIP state dict, read off the tensor shapes the way
-        lib/models/chexzero_clip.py:411-441 (build_model) does.  ViT visual towers only."""
+        lib/models/chexzero_clip.py:411-441 (build_model) does.  ViT visual towers only.  The format does not store the head
+        count: heads = width // 64 as build_model has it, so a tower with another head dim (ViT-H/14: 80) needs its
+        configuration from elsewhere (ClipConfig.named, from_hf_dict)."""
         if "visual.proj" not in sd:
             raise NotImplementedError("ResNet visual towers (ModifiedResNet, chexzero_clip.py:94-174) are not on LEMoN's path")
         vw = sd["visual.conv1.weight"].shape[0]
@@ -149,11 +162,11 @@ class Block(nn.Module):
             from . import ops
             mode = ops.gemm_mode()
             ops.select_attention_arithmetic(mode)
-            if W % 4 == 0 and W <= 1024 and mode != "f32":
+            if W % 4 == 0 and W <= ops.fused_width_max() and mode != "f32":
                 return self._forward_split(x, causal, rows, ops, mode, carry)
             ln = lambda m, t: ops.layer_norm(t, m.weight, m.bias, m.eps) if t.shape[-1] % 4 == 0 else m(t)
             qkv = ops.linear(ln(self.ln1, x), self.qkv.weight, self.qkv.bias)
-            if W == 64 * self.heads and L <= ops.ATTENTION_MAX_SEQ:
+            if ops.attention_supported(W, self.heads, L):
                 a = ops.attention(qkv, self.heads, causal)
             else:
                 a = self._sdpa(qkv, B, L, W, causal)
@@ -245,7 +258,7 @@ class Block(nn.Module):
         else:
             w, a_ = self._w_split("qkv", ops, mode)
             qkv = ops.linear_split(ops.layer_norm_split(x, self.ln1.weight, self.ln1.bias, self.ln1.eps, mode), w, self.qkv.bias, alpha=a_)
-        hip_attn = W == 64 * self.heads and L <= ops.ATTENTION_MAX_SEQ
+        hip_attn = ops.attention_supported(W, self.heads, L)
         if hip_attn and rows is None:
             a6 = ops.attention_split(qkv, self.heads, causal, mode)      # the attention kernel stores the split operand itself
         else:
@@ -293,7 +306,8 @@ class Block(nn.Module):
             ok = True
         else:
             B, L, W = x.shape
-            ok = (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and W % 32 == 0 and mlp % 32 == 0 and W <= 1024
+            ok = (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and W % 32 == 0 and mlp % 32 == 0
+                  and W <= ops.fused_width_max()
                   and ops.gemm_mode() == "f16x3" and ops.mlp_mode() == "block" and ops.ln_fold_enabled()
                   and ops.block_fused_supported(W, mlp, self.heads, L))
         if not ok:
@@ -417,13 +431,13 @@ class VisionTower(nn.Module):
 
 
 class TextTower(nn.Module):
-    def __init__(self, cfg: ClipConfig):
+    def __init__(self, cfg: ClipConfig, act="quick_gelu"):
         super().__init__()
         t = cfg.text
         self.eos_token_id = cfg.eos_token_id
         self.tok = nn.Embedding(cfg.vocab_size, t.width)
         self.pos = nn.Parameter(torch.zeros(cfg.context_length, t.width))
-        self.blocks = nn.ModuleList([Block(t, cfg.layer_norm_eps) for _ in range(t.layers)])
+        self.blocks = nn.ModuleList([Block(t, cfg.layer_norm_eps, act) for _ in range(t.layers)])
         self.final_ln = nn.LayerNorm(t.width, eps=cfg.layer_norm_eps)
         self.proj = nn.Linear(t.width, cfg.embed_dim, bias=False)
 
@@ -468,8 +482,8 @@ class LemonCLIP(nn.Module):
     def __init__(self, cfg: ClipConfig = None):
         super().__init__()
         self.cfg = cfg or ClipConfig()
-        self.vision = VisionTower(self.cfg)
-        self.text = TextTower(self.cfg)
+        self.vision = VisionTower(self.cfg, act=self.cfg.hidden_act)
+        self.text = TextTower(self.cfg, act=self.cfg.hidden_act)
         self.logit_scale = math.log(1 / 0.07)          # CLIP's temperature parameter (log scale), chexzero_clip.py:319
         self.reset_parameters()
 

@@ -1156,6 +1156,27 @@ extern "C" int lemon_attention_set_stream_min(int seq_len) {
     return prev;
 }
 
+// Head dims other than 64 (attention_hd.hip), per calling thread: 0 = head_dim must be 64 (the default), 1 = multiples of 8 in
+// 72 .. 128 go to k_attention_hdx_stream, 2 = head_dim 64 goes there as well (the equality test, A/B timing);
+// $LEMON_ATTN_HEAD_DIMS starts every thread with its value
+static int attn_head_dims_default() {
+    static const int v = [] { const char *e = getenv("LEMON_ATTN_HEAD_DIMS"); return (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : 0; }();
+    return v;
+}
+static thread_local int g_attn_head_dims = attn_head_dims_default();
+
+extern "C" int lemon_attention_set_head_dims(int mode) {
+    if (mode < 0 || mode > 2) {
+        lemon_set_error("lemon_attention_set_head_dims: mode must be 0, 1 or 2");
+        return LEMON_E_INVALID;
+    }
+    const int prev = g_attn_head_dims;
+    g_attn_head_dims = mode;
+    return prev;
+}
+
+extern "C" int lemon_attention_get_head_dims(void) { return g_attn_head_dims; }
+
 // seq_len > g_attn_stream_min (> 64): grid (batch * heads, query blocks), see k_attention_hd64_stream
 template <int SPLIT>
 static int attention_stream(const float *qkv_dev, int64_t batch, int seq_len, int heads, int causal, float *out_dev, void *stream) {
@@ -1193,12 +1214,14 @@ template <int SPLIT>
 static int attention_impl(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                           int causal, float *out_dev, void *stream) {
     LEMON_REQUIRE(batch >= 0 && seq_len > 0 && heads > 0, "batch >= 0, seq_len > 0, heads > 0");
-    LEMON_REQUIRE(head_dim == HD, "head_dim must be 64");
+    const bool hdx = g_attn_head_dims != 0 && head_dim % 8 == 0 && head_dim <= 128 && (head_dim > HD || (head_dim == HD && g_attn_head_dims == 2));
+    LEMON_REQUIRE(head_dim == HD || hdx, "head_dim must be 64");
     LEMON_REQUIRE(seq_len <= LEMON_ATTENTION_MAX_SEQ, "seq_len <= LEMON_ATTENTION_MAX_SEQ = 4096");
     if (batch == 0) return LEMON_OK;
     LEMON_REQUIRE(qkv_dev && out_dev, "null pointer");
     LEMON_REQUIRE((((uintptr_t)qkv_dev) & 15) == 0 && (((uintptr_t)out_dev) & 15) == 0, "16-byte alignment");
     LEMON_REQUIRE(batch * heads < (int64_t)1 << 31, "batch * heads < 2^31");
+    if (hdx) return lemon_attention_hdx(qkv_dev, batch, seq_len, heads, head_dim, causal, out_dev, SPLIT, (hipStream_t)stream);
     const int tj = (seq_len + 31) / 32;
     static const bool short_off = [] { const char *e = getenv("LEMON_ATTN_SHORT"); return e && e[0] == '0'; }();   // tuning knob
     const dim3 grid((unsigned)(batch * heads));

@@ -153,3 +153,6 @@ int lemon_dedup_queries(lemon_index_t *idx, const float *q_dev, int64_t nq, hipS
 int lemon_gather_query_rows(const float *q_dev, const int *rep_dev, int64_t U, int d, float *out_dev, hipStream_t stream);
 int lemon_expand_results(const float *Dr, const int64_t *Ir, const int *group_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
                          hipStream_t stream);
+// attention at head dims 64 .. 128 (attention_hd.hip), called by attention_impl (attention.hip) after its argument checks
+int lemon_attention_hdx(const float *qkv_dev, int64_t batch, int seq_len, int heads, int hd, int causal, float *out_dev, int split,
+                        hipStream_t stream);

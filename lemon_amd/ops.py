@@ -309,9 +309,38 @@ def mlp_fused_supported(width, mlp):
     return width % 256 == 0 and mlp % 256 == 0
 
 
+def attention_head_dims():
+    """The calling thread's head-dim mode (lemon_attention_get_head_dims): 0 = head_dim 64 only, 1 / 2 = multiples of 8 up to 128."""
+    return int(_lib.load().lemon_attention_get_head_dims())
+
+
+def set_attention_head_dims(mode):
+    """lemon_attention_set_head_dims for the calling thread (initially $LEMON_ATTN_HEAD_DIMS, default 0) -> the previous mode."""
+    lib = _lib.load()
+    prev = lib.lemon_attention_get_head_dims()
+    rc = lib.lemon_attention_set_head_dims(int(mode))
+    if rc < 0:
+        _lib.check(rc, "lemon_attention_set_head_dims")
+    return int(prev)
+
+
+def attention_supported(width, heads, seq_len):
+    """Do the HIP attention kernels take this tower?  head_dim 64 always; multiples of 8 in 72 .. 128 with the head-dim mode on."""
+    if heads <= 0 or width % heads or seq_len > ATTENTION_MAX_SEQ:
+        return False
+    hd = width // heads
+    return hd == 64 or (attention_head_dims() != 0 and hd % 8 == 0 and 64 < hd <= 128)
+
+
+def fused_width_max():
+    """Widest residual stream the split-GEMM paths of a block take: 1024, or 2048 (what the LayerNorm and row-statistics kernels
+    hold) with the head-dim mode on -- the towers beyond 1024 are the ones with head dims beyond 64."""
+    return 2048 if attention_head_dims() != 0 else 1024
+
+
 def block_fused_supported(width, mlp, heads, seq_len):
     """all four GEMMs of a block in the hand-written kernel: additionally 3 * width a multiple of 256 and the HIP attention"""
-    return mlp_fused_supported(width, mlp) and (3 * width) % 256 == 0 and width == 64 * heads and seq_len <= ATTENTION_MAX_SEQ
+    return mlp_fused_supported(width, mlp) and (3 * width) % 256 == 0 and attention_supported(width, heads, seq_len)
 
 
 def _tiled_rows(m):
@@ -540,15 +569,18 @@ def gemm_profile_read():
 
 
 def attention_t(qkv, heads, causal=False):
-    """attention() whose output is the tile-major fp16 activation operand of lemon_linear_f16x3t (rows = B*L, k = heads*64)."""
+    """attention() whose output is the tile-major fp16 activation operand of lemon_linear_f16x3t (rows = B*L, k = W = heads*head_dim,
+    a multiple of 16)."""
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3
     qkv = qkv.contiguous()
     B, L, W3 = qkv.shape
-    assert W3 == 3 * heads * 64 and L <= ATTENTION_MAX_SEQ
-    out = torch.empty((_tiled_rows(B * L) * heads * 64 * 2,), dtype=torch.float16, device=qkv.device)
+    W = W3 // 3
+    hd = W // heads
+    assert W3 == 3 * W and W == heads * hd and W % 16 == 0 and L <= ATTENTION_MAX_SEQ
+    out = torch.empty((_tiled_rows(B * L) * W * 2,), dtype=torch.float16, device=qkv.device)
     lib = _lib.load()
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.lemon_attention_f16x3t(ptr(qkv), B, L, heads, 64, int(bool(causal)), ptr(out), stream_ptr(qkv.device)),
+        _lib.check(lib.lemon_attention_f16x3t(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out), stream_ptr(qkv.device)),
                    "lemon_attention_f16x3t")
     return out
 
@@ -611,15 +643,16 @@ def linear_dump_tuned(path):
 
 def attention(qkv, heads, causal=False):
     """Fused self-attention on the packed projection output qkv [B, L, 3*W] (float32, contiguous,
-    W = heads*64) -> [B, L, W]; the HIP kernel behind LemonCLIP's blocks."""
+    W = heads*head_dim; head_dim 64, or see attention_supported) -> [B, L, W]; the HIP kernel behind LemonCLIP's blocks."""
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.dim() == 3
     B, L, W3 = qkv.shape
     W = W3 // 3
-    assert W3 == 3 * W and W == heads * 64 and L <= ATTENTION_MAX_SEQ
+    hd = W // heads
+    assert W3 == 3 * W and W == heads * hd and L <= ATTENTION_MAX_SEQ
     out = torch.empty((B, L, W), dtype=torch.float32, device=qkv.device)
     lib = _lib.load()
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.lemon_attention_f32(ptr(qkv), B, L, heads, 64, int(bool(causal)), ptr(out),
+        _lib.check(lib.lemon_attention_f32(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out),
                                            stream_ptr(qkv.device)), "lemon_attention_f32")
     return out
 
@@ -631,12 +664,14 @@ def attention_split(qkv, heads, causal=False, mode="bf16x6"):
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3
     qkv = qkv.contiguous()
     B, L, W3 = qkv.shape
-    assert W3 == 3 * heads * 64 and L <= ATTENTION_MAX_SEQ
-    out = torch.empty((B, L, seg * heads * 64), dtype=dtype, device=qkv.device)
+    W = W3 // 3
+    hd = W // heads
+    assert W3 == 3 * W and W == heads * hd and L <= ATTENTION_MAX_SEQ
+    out = torch.empty((B, L, seg * W), dtype=dtype, device=qkv.device)
     lib = _lib.load()
     fn = lib.lemon_attention_split3 if mode == "bf16x6" else lib.lemon_attention_f16x3
     with torch.cuda.device(qkv.device):
-        _lib.check(fn(ptr(qkv), B, L, heads, 64, int(bool(causal)), ptr(out), stream_ptr(qkv.device)), "lemon_attention_" + mode)
+        _lib.check(fn(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out), stream_ptr(qkv.device)), "lemon_attention_" + mode)
     return out
 
 
