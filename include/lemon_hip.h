@@ -178,6 +178,23 @@ int lemon_attention_get_head_dims(void);
  * out6_dev [batch*seq_len, 6*heads*64] bf16, 16-byte aligned.  The fp32 result is split at the store, not recomputed. */
 int lemon_attention_split3(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                            int causal, uint16_t *out6_dev, void *stream);
+/* Bidirectional attention with a key length PER SEQUENCE: the padding mask of a BERT text tower whose captions are padded
+ * behind their last token (HF BertSelfAttention called with attention_mask = ids != pad, behind lib/models/utils.py:72-78).
+ * The four entry points take the arguments of their plain siblings without `causal`, and lengths_dev [batch] int32 on the
+ * device; n_b = clamp(lengths[b], 1, seq_len), clamped on the device.
+ *   rows t <  n_b of sequence b: attention of query t over keys 0 .. n_b - 1 only;
+ *   rows n_b <= t < seq_len:     zeros (hi and lo parts 0 in the split forms; the tile-major form's padded tile rows are not
+ *                                written, as in the plain call);
+ *   qkv rows t >= n_b are never loaded: NaN, Inf or values beyond the fp16 range there reach no output row t < n_b.
+ * head_dim 64 (in every lemon_attention_set_head_dims mode) and 1 <= seq_len <= 288; both arithmetic selections of
+ * lemon_attention_set_f16; heads < 19 418.  Anything else: LEMON_E_INVALID, nothing is written.  lengths_dev == NULL: the plain
+ * entry point with causal = 0.  Kernel layout, tile walk and summation order are the plain kernels' at the same seq_len: with
+ * lengths[b] = seq_len the bits are the plain call's, and a row t < n_b has the bits of the plain call on qkv[b, :n_b] wherever
+ * ceil(n_b / 32) = ceil(seq_len / 32).  A key tile or a wave of queries entirely beyond n_b skips its products. */
+int lemon_attention_f32_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
+                               const int32_t *lengths_dev, float *out_dev, void *stream);
+int lemon_attention_split3_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
+                                  const int32_t *lengths_dev, uint16_t *out6_dev, void *stream);
 
 /* LayerNorm over the last dimension, float32: y = (x - mean) / sqrt(var + eps) * weight + bias (biased variance, like
  * torch.nn.LayerNorm) -- layer_norm1/2, pre_layrnorm, post_layernorm, final_layer_norm of the towers behind
@@ -266,6 +283,8 @@ int lemon_layernorm_f16x3(const float *x_dev, const float *weight_dev, const flo
                           int width, uint16_t *y3_dev, void *stream);
 int lemon_attention_f16x3(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                           int causal, uint16_t *out3_dev, void *stream);
+int lemon_attention_f16x3_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
+                                 const int32_t *lengths_dev, uint16_t *out3_dev, void *stream);   /* see lemon_attention_f32_varlen */
 /* The MLP of a transformer block (fc1 -> QuickGELU -> fc2; lib/models/downstream_models.py:37-41 via HF CLIPMLP, in-tree twin
  * lib/models/chexzero_clip.py:171-183) with the arithmetic of lemon_linear_f16x3 in a HAND-WRITTEN gfx950 kernel whose operands
  * are tile-major in MFMA fragment order:
@@ -333,6 +352,8 @@ int lemon_linear_f16x3t_profile_read(int64_t *launches, double *kernel_ms, doubl
  * projection then runs in the hand-written GEMM too (with QKV: all four GEMMs of a block). */
 int lemon_attention_f16x3t(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                            int causal, uint16_t *outt_dev, void *stream);
+int lemon_attention_f16x3t_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
+                                  const int32_t *lengths_dev, uint16_t *outt_dev, void *stream);  /* see lemon_attention_f32_varlen */
 /* Recorded solution choices: a "# lemon_linear hipblaslt=<version> arch=<gfx name>" stamp line followed by
  * "m,n,k,epilogue,residual,index,usec" lines.  load returns the number of keys taken -- 0 when the stamp
  * does not match this process's hipBLASLt version / device arch (the file is then ignored) -- and dump the

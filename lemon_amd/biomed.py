@@ -18,10 +18,12 @@ importable here, seeded random weights, tests/test_biomed.py), the call sites ag
 LongTensor, model.encode_text(tokens), model.encode_image(pixels)).  Real-weight parity needs a local checkpoint directory.
 
 MI355X-first: the vision tower IS lemon_amd.clip.VisionTower (same hand-written GEMM chain, with the GELU operand epilogue and
-the convolution bias riding on the position embedding).  The text tower's padding mask never reaches a kernel: captions are
-grouped by their exact token count and every group runs un-padded (for bidirectional attention a key mask over trailing pads
+the convolution bias riding on the position embedding).  By default the text tower's padding mask never reaches a kernel: captions
+are grouped by their exact token count and every group runs un-padded (for bidirectional attention a key mask over trailing pads
 and truncation to the caption's own length are the same function) -- pipeline.Embedder sorts captions by length so that a
-micro-batch is one group.  The post-LN layers reuse the LayerNorm fold of the hand-written GEMMs: the output projection / fc2
+micro-batch is one group.  With BertTextTower.length_bucket = n > 0 ($LEMON_BERT_BUCKET, opt-in) captions are grouped by their
+token count rounded up to a multiple of n instead, and the attention kernels take every caption's own key count
+(lemon_attention_*_varlen: HF BertSelfAttention's attention_mask for pads behind the caption).  The post-LN layers reuse the LayerNorm fold of the hand-written GEMMs: the output projection / fc2
 write the pre-norm sum y as fp32, as the next GEMM's operand and as row statistics (EMIT); fc1 / the next layer's QKV take y with
 the LayerNorm folded into their weights (FOLD); the LayerNorm kernel only makes the fp32 residual.
 """
@@ -86,7 +88,9 @@ class BiomedConfig:
 class BertLayer(Block):
     """One HF BertLayer (attention.self + attention.output + intermediate + output): x1 = LN1(x + out(attn(qkv(x)))),
     x2 = LN2(x1 + fc2(gelu(fc1(x1)))).  Parameter names follow clip.Block (ln1 = attention.output.LayerNorm, ln2 =
-    output.LayerNorm); no mask: the caller hands over captions without padding."""
+    output.LayerNorm).  lengths = None: no mask, the caller hands over captions without padding; lengths = int32 CUDA [B]: the
+    key count of every caption (pads behind it), handed to the attention kernels -- rows beyond a caption's count carry finite or
+    non-finite filler through the row-wise operations and are read by nobody."""
 
     def __init__(self, cfg: TowerConfig, eps):
         super().__init__(cfg, eps, act="gelu")
@@ -98,8 +102,10 @@ class BertLayer(Block):
         w, a_ = split_weight_cached(self, name, lin.weight, ops, mode)
         return ops.linear_split(ops.split_operand(t, mode), w, lin.bias, residual=residual, act=act, alpha=a_)
 
-    def forward(self, x, causal=False, rows=None, carry=None):
+    def forward(self, x, causal=False, rows=None, carry=None, lengths=None):
         B, L, W = x.shape
+        if lengths is not None and not (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
+            raise ValueError("BertLayer: per-caption lengths exist on the fused GPU path only")
         if x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled():
             # every GEMM through the library entry points of the current mode (lemon_linear_f32 / _bf16x6 / _f16x3), LayerNorm and
             # attention kernels: the form the fallbacks and the A/B modes run
@@ -107,7 +113,9 @@ class BertLayer(Block):
             mode = ops.gemm_mode()
             ops.select_attention_arithmetic(mode)
             qkv = self._gemm(x, "qkv", ops, mode)
-            if W == 64 * self.heads and L <= ops.ATTENTION_MAX_SEQ:
+            if lengths is not None:                    # (ops.attention raises where the kernels take no lengths: never unmasked)
+                a = ops.attention(qkv, self.heads, False, lengths=lengths)
+            elif W == 64 * self.heads and L <= ops.ATTENTION_MAX_SEQ:
                 a = ops.attention(qkv, self.heads, False)
             else:
                 a = self._sdpa(qkv, B, L, W, False)
@@ -130,7 +138,7 @@ class BertLayer(Block):
                 and ops.gemm_mode() == "f16x3" and ops.mlp_mode() == "block" and ops.ln_fold_enabled()
                 and ops.block_fused_supported(W, mlp, self.heads, L))
 
-    def forward_chain(self, x, carry, last=False):
+    def forward_chain(self, x, carry, last=False, lengths=None):
         """x = LN_prev(y_prev) in fp32; carry = (y_prev as the tile-major operand, its rows' (rstd, -mean rstd), LN_prev): QKV
         folds LN_prev.  -> (x_out, carry_out); `last`: -> ([B, W] rows of the [CLS] token, None)."""
         from . import ops
@@ -143,13 +151,13 @@ class BertLayer(Block):
         if last:
             # the tower reads the [CLS] row only: attention still sees every token's keys and values, the output projection and
             # the MLP (3/4 of the layer's GEMM work, all row-wise) run for that row alone -- in the library form, B rows
-            a = ops.attention(qkv, self.heads, False)[:, 0].contiguous()
+            a = ops.attention(qkv, self.heads, False, lengths=lengths)[:, 0].contiguous()
             x = x[:, 0].contiguous()
             x = ops.layer_norm(self._gemm(a, "out", ops, "f16x3", residual=x), self.ln1.weight, self.ln1.bias, self.ln1.eps)
             h = self._gemm(x, "fc1", ops, "f16x3", act="gelu")
             return ops.layer_norm(self._gemm(h, "fc2", ops, "f16x3", residual=x), self.ln2.weight, self.ln2.bias, self.ln2.eps), None
         wo, ao = self._w_tiled("out", ops)
-        y, yt, st = ops.linear_t_ln(ops.attention_t(qkv, self.heads, False), wo, m, W, W, self.out.bias, residual=x, alpha=ao,
+        y, yt, st = ops.linear_t_ln(ops.attention_t(qkv, self.heads, False, lengths=lengths), wo, m, W, W, self.out.bias, residual=x, alpha=ao,
                                     out_shape=x.shape, emit=True)
         x = ops.layer_norm(y, self.ln1.weight, self.ln1.bias, self.ln1.eps)          # (the residual of the MLP half)
         w1, a1, cs1, b1 = self._w_tiled_ln("fc1", self.ln1, ops, 1.0)
@@ -160,13 +168,26 @@ class BertLayer(Block):
                 (yt, ops.ln_finalize(st, m, W, self.ln2.eps), self.ln2))
 
 
-class BertTextTower(nn.Module):
-    exact_lengths = True      # pipeline.Embedder: micro-batches must not mix caption lengths (no padding mask in the kernels)
+def _length_bucket(value, what="length_bucket"):
+    """0 (captions grouped by exact token count) or a positive multiple of 8"""
+    try:
+        n = int(str(value).strip())
+    except ValueError:
+        n = -1
+    if n < 0 or n % 8:
+        raise ValueError(f"{what} must be 0 or a positive multiple of 8, not {value!r}")
+    return n
 
+
+class BertTextTower(nn.Module):
     def __init__(self, cfg: BiomedConfig):
         super().__init__()
         t = cfg.text
         self.pad_token_id = cfg.pad_token_id
+        self.context_length = cfg.context_length
+        # 0: captions run un-padded in groups of one exact token count (no padding mask in any kernel); n > 0: in groups of one
+        # token count rounded up to a multiple of n, every caption's own count going to the attention kernels (opt-in)
+        self.length_bucket = _length_bucket(os.environ.get("LEMON_BERT_BUCKET", "0"), "LEMON_BERT_BUCKET")
         self.tok = nn.Embedding(cfg.vocab_size, t.width)
         self.pos = nn.Parameter(torch.zeros(cfg.max_positions, t.width))
         self.type_emb = nn.Parameter(torch.zeros(cfg.type_vocab_size, t.width))
@@ -181,8 +202,17 @@ class BertTextTower(nn.Module):
         nz = input_ids != self.pad_token_id
         return (nz * torch.arange(1, input_ids.shape[1] + 1, device=input_ids.device)).amax(dim=-1) - 1
 
+    @property
+    def exact_lengths(self):
+        """pipeline.Embedder: micro-batches must not mix caption lengths (no padding mask in the kernels)"""
+        return _length_bucket(self.length_bucket) == 0
+
     def seq_len_for(self, last):
-        return max(1, min(self.pos.shape[0], int(last) + 1))
+        L = max(1, min(self.pos.shape[0], int(last) + 1))
+        n = _length_bucket(self.length_bucket)
+        if n:
+            L = min((L + n - 1) // n * n, max(L, min(self.pos.shape[0], self.context_length)))
+        return L
 
     def _pos_type0(self):
         """position + token-type-0 embedding (open_clip passes no token_type_ids: all zero), once per parameter version"""
@@ -209,8 +239,9 @@ class BertTextTower(nn.Module):
             x = b.ln2(x + b.fc2(F.gelu(b.fc1(x))))
         return self.proj2(F.gelu(self.proj1(x[:, 0])))
 
-    def _unpadded(self, ids, L):
-        """ids [B, >= L], every row exactly L tokens long: the fused GPU path"""
+    def _unpadded(self, ids, L, lengths=None):
+        """ids [B, >= L]: the fused GPU path.  lengths None: every row exactly L tokens long; else int32 CUDA [B], every row's
+        token count <= L with pads behind it (the attention kernels mask them)"""
         from . import ops
         ids = ids if ids.dtype == torch.int64 and ids.stride(1) == 1 else ids.long().contiguous()
         e = ops.text_tokens(ids, L, self.tok.weight, self._pos_type0())
@@ -220,18 +251,21 @@ class BertTextTower(nn.Module):
         if self.blocks[0].chain_supported(x):
             carry = ops.rowstats_t(e, ln.eps) + (ln,)
             for i, b in enumerate(self.blocks):
-                x, carry = b.forward_chain(x, carry, last=i == n - 1)
+                x, carry = b.forward_chain(x, carry, last=i == n - 1, lengths=lengths)
         else:
             for b in self.blocks[:-1]:
-                x = b(x)
+                x = b(x, lengths=lengths)
             batch = torch.arange(x.shape[0], device=x.device)
-            x = self.blocks[-1](x, rows=(batch, torch.zeros_like(batch)))       # [CLS] rows of the last layer
+            x = self.blocks[-1](x, rows=(batch, torch.zeros_like(batch)), lengths=lengths)       # [CLS] rows of the last layer
         return ops.linear(ops.linear(x, self.proj1.weight, act="gelu"), self.proj2.weight)
 
     def forward(self, input_ids, seq_len=None, lengths=None):
         """input_ids [B, ctx] -> [B, embed_dim].  lengths: per-row token counts on the HOST when the caller has them
         (pipeline.Embedder), saving the device read here -- the caller then vouches that no row has padding inside;
-        seq_len: accepted for the CLIP towers' signature (their bucketed length)."""
+        seq_len: the token count to run with length_bucket > 0 (the callers' bucketed length, >= every row's count; None: the
+        bucket of the longest row) -- the rows without inner padding then run the fused path ONCE at seq_len with their counts
+        on the device, where the attention kernels take them (ops.attention_varlen_supported), and in exact-length groups where
+        not.  With length_bucket = 0 it is accepted for the CLIP towers' signature only."""
         fused = input_ids.is_cuda and self.pos.dtype == torch.float32 and not torch.is_grad_enabled() and self.pos.shape[-1] % 4 == 0
         if not fused:
             L = int(self.last_token_index(input_ids).max()) + 1 if input_ids.shape[0] else 1
@@ -245,6 +279,23 @@ class BertTextTower(nn.Module):
             lengths, inner = torch.as_tensor(lengths).cpu(), torch.zeros(input_ids.shape[0], dtype=torch.bool)
         out = torch.empty((input_ids.shape[0], self.proj2.weight.shape[0]), dtype=torch.float32, device=input_ids.device)
         lengths = lengths.clamp(min=1)
+        if _length_bucket(self.length_bucket) and bool((~inner).any()):
+            from . import ops
+            Lb = self.seq_len_for(int(lengths[~inner].max()) - 1)
+            if seq_len is not None:
+                Lb = max(Lb, int(seq_len))
+            Lb = min(Lb, input_ids.shape[1], self.pos.shape[0])
+            if Lb >= int(lengths[~inner].max()) and ops.attention_varlen_supported(self.pos.shape[-1], self.blocks[0].heads, Lb):
+                whole = not bool(inner.any())
+                sel = None if whole else (~inner).nonzero().flatten()
+                rows = input_ids if whole else input_ids[sel.to(input_ids.device)]
+                e = self._unpadded(rows, Lb, ops.attention_lengths(lengths if whole else lengths[sel], rows.shape[0], input_ids.device))
+                if whole:
+                    return e
+                out[sel.to(out.device)] = e
+                sel = inner.nonzero().flatten().to(input_ids.device)
+                out[sel] = self._masked(input_ids[sel][:, :int(lengths[inner].max())])
+                return out
         for L in torch.unique(lengths[~inner]).tolist():
             sel = ((lengths == L) & ~inner).nonzero().flatten()
             rows = input_ids if sel.numel() == input_ids.shape[0] else input_ids[sel.to(input_ids.device)]

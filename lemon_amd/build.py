@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 SO = os.path.join(HERE, "liblemon_hip.so")
-SOURCES = ["api.hip", "rowwise.hip", "knn_f32.hip", "knn_bf16.hip", "attention.hip", "attention_hd.hip", "linear.hip", "preprocess.hip",
+SOURCES = ["api.hip", "rowwise.hip", "knn_f32.hip", "knn_bf16.hip", "attention.hip", "attention_hd.hip", "attention_varlen.hip", "linear.hip", "preprocess.hip",
            "gridf1.hip", "dedup.hip", "encoder.hip", "gemm_f16x3.hip", "kmeans.hip", "jpeg.hip", "jpeg_entropy.hip", "jpeg_prog.hip"]
 HEADERS = ["common.hpp", "knn_common.hpp", "split3.hpp", "scan_plan.hpp", "jpeg_core.hpp", "jpeg_entropy.hpp", "jpeg_par.hpp", "jpeg_abi.hpp",
            "jpeg_prog.hpp", "jpeg_prog_par.hpp", os.path.join("..", "..", "include", "lemon_hip.h")]

@@ -1143,6 +1143,9 @@ extern "C" int lemon_attention_set_f16(int on) {
     return prev;
 }
 
+// the calling thread's selection as lemon_attention_set_f16 took it (0 / 1 / 2), for attention_varlen.hip
+int lemon_attention_f16_mode() { return g_attn_f16 ? (g_attn_old_general ? 2 : 1) : 0; }
+
 // Sequences longer than this take the streaming kernels (per calling thread, like the arithmetic switch)
 static thread_local int g_attn_stream_min = 288;
 

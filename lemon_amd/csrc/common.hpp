@@ -156,3 +156,5 @@ int lemon_expand_results(const float *Dr, const int64_t *Ir, const int *group_de
 // attention at head dims 64 .. 128 (attention_hd.hip), called by attention_impl (attention.hip) after its argument checks
 int lemon_attention_hdx(const float *qkv_dev, int64_t batch, int seq_len, int heads, int hd, int causal, float *out_dev, int split,
                         hipStream_t stream);
+// the calling thread's lemon_attention_set_f16 selection, 0 / 1 / 2 (attention.hip), read by attention_varlen.hip
+int lemon_attention_f16_mode();

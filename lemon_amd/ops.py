@@ -568,9 +568,37 @@ def gemm_profile_read():
     return {"launches": int(n.value), "kernel_ms": float(ms.value), "flops": float(fl.value)}
 
 
-def attention_t(qkv, heads, causal=False):
+ATTENTION_VARLEN_MAX_SEQ = 288     # the one-workgroup kernels: the streaming kernels take no per-sequence lengths
+
+
+def attention_varlen_supported(width, heads, seq_len):
+    """Do the lemon_attention_*_varlen entry points (a key length per sequence) take this tower at this token count?"""
+    return heads > 0 and width == 64 * heads and 1 <= seq_len <= ATTENTION_VARLEN_MAX_SEQ
+
+
+def attention_lengths(lengths, batch, device):
+    """-> int32 [batch] on `device`: a CUDA tensor as it is (converted if need be), a host sequence / tensor through a pinned
+    staging buffer and a non-blocking copy -- no synchronisation either way."""
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        t = lengths.to(device=device, dtype=torch.int32).contiguous()
+    else:
+        host = torch.as_tensor(lengths).to(torch.int32).reshape(-1).contiguous()
+        t = host.pin_memory().to(device, non_blocking=True)
+    assert t.dim() == 1 and t.shape[0] == batch, (tuple(t.shape), batch)
+    return t
+
+
+def _varlen_args(lengths, causal, B, L, heads, hd, device):
+    assert not causal, "per-sequence lengths: bidirectional attention only (padding behind a caption is invisible under a causal mask)"
+    if not (hd == 64 and L <= ATTENTION_VARLEN_MAX_SEQ):
+        raise ValueError(f"attention with per-sequence lengths: head_dim 64 and seq_len <= {ATTENTION_VARLEN_MAX_SEQ} "
+                         f"(got head_dim {hd}, seq_len {L}); see ops.attention_varlen_supported")
+    return attention_lengths(lengths, B, device)
+
+
+def attention_t(qkv, heads, causal=False, lengths=None):
     """attention() whose output is the tile-major fp16 activation operand of lemon_linear_f16x3t (rows = B*L, k = W = heads*head_dim,
-    a multiple of 16)."""
+    a multiple of 16).  lengths: see attention()."""
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3
     qkv = qkv.contiguous()
     B, L, W3 = qkv.shape
@@ -580,6 +608,11 @@ def attention_t(qkv, heads, causal=False):
     out = torch.empty((_tiled_rows(B * L) * W * 2,), dtype=torch.float16, device=qkv.device)
     lib = _lib.load()
     with torch.cuda.device(qkv.device):
+        if lengths is not None:
+            ln = _varlen_args(lengths, causal, B, L, heads, hd, qkv.device)
+            _lib.check(lib.lemon_attention_f16x3t_varlen(ptr(qkv), B, L, heads, hd, ptr(ln), ptr(out), stream_ptr(qkv.device)),
+                       "lemon_attention_f16x3t_varlen")
+            return out
         _lib.check(lib.lemon_attention_f16x3t(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out), stream_ptr(qkv.device)),
                    "lemon_attention_f16x3t")
     return out
@@ -641,9 +674,12 @@ def linear_dump_tuned(path):
     return _lib.load().lemon_linear_dump_tuned(str(path).encode())
 
 
-def attention(qkv, heads, causal=False):
+def attention(qkv, heads, causal=False, lengths=None):
     """Fused self-attention on the packed projection output qkv [B, L, 3*W] (float32, contiguous,
-    W = heads*head_dim; head_dim 64, or see attention_supported) -> [B, L, W]; the HIP kernel behind LemonCLIP's blocks."""
+    W = heads*head_dim; head_dim 64, or see attention_supported) -> [B, L, W]; the HIP kernel behind LemonCLIP's blocks.
+    lengths: None, or the key count of every sequence -- an int32 CUDA tensor [B], or a host sequence (uploaded without a
+    synchronisation): sequence b attends to its first clamp(lengths[b], 1, L) tokens only and its rows beyond them come out as
+    zeros (lemon_attention_*_varlen: bidirectional, head_dim 64, L <= 288, see attention_varlen_supported)."""
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.dim() == 3
     B, L, W3 = qkv.shape
     W = W3 // 3
@@ -652,14 +688,19 @@ def attention(qkv, heads, causal=False):
     out = torch.empty((B, L, W), dtype=torch.float32, device=qkv.device)
     lib = _lib.load()
     with torch.cuda.device(qkv.device):
+        if lengths is not None:
+            ln = _varlen_args(lengths, causal, B, L, heads, hd, qkv.device)
+            _lib.check(lib.lemon_attention_f32_varlen(ptr(qkv), B, L, heads, hd, ptr(ln), ptr(out), stream_ptr(qkv.device)),
+                       "lemon_attention_f32_varlen")
+            return out
         _lib.check(lib.lemon_attention_f32(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out),
                                            stream_ptr(qkv.device)), "lemon_attention_f32")
     return out
 
 
-def attention_split(qkv, heads, causal=False, mode="bf16x6"):
+def attention_split(qkv, heads, causal=False, mode="bf16x6", lengths=None):
     """attention() whose output is the split activation operand of `mode`: [B, L, 6*W] bf16 (lemon_attention_split3) or
-    [B, L, 3*W] fp16 (lemon_attention_f16x3)."""
+    [B, L, 3*W] fp16 (lemon_attention_f16x3).  lengths: see attention()."""
     dtype, seg = _SCHEMES[mode]
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3
     qkv = qkv.contiguous()
@@ -671,6 +712,11 @@ def attention_split(qkv, heads, causal=False, mode="bf16x6"):
     lib = _lib.load()
     fn = lib.lemon_attention_split3 if mode == "bf16x6" else lib.lemon_attention_f16x3
     with torch.cuda.device(qkv.device):
+        if lengths is not None:
+            ln = _varlen_args(lengths, causal, B, L, heads, hd, qkv.device)
+            fnv = lib.lemon_attention_split3_varlen if mode == "bf16x6" else lib.lemon_attention_f16x3_varlen
+            _lib.check(fnv(ptr(qkv), B, L, heads, hd, ptr(ln), ptr(out), stream_ptr(qkv.device)), "lemon_attention_" + mode + "_varlen")
+            return out
         _lib.check(fn(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out), stream_ptr(qkv.device)), "lemon_attention_" + mode)
     return out
 

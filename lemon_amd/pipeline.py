@@ -97,6 +97,12 @@ def all_gather_rows(t, n_total, group=None, log=None, name="rows", force=False):
     return out
 
 
+def _length_grouped(tower):
+    """A text tower whose micro-batches are cut by the captions' own token counts and that takes them as `lengths`
+    (biomed.BertTextTower): groups of one exact count, or -- with its length_bucket > 0 -- of one count rounded up to the bucket."""
+    return bool(getattr(tower, "exact_lengths", False)) or int(getattr(tower, "length_bucket", 0) or 0) > 0
+
+
 class Embedder:
     """HOT LOOP 1/2 of run_lemon.py (:137-161, :202-233) without the D2H copies.
 
@@ -134,7 +140,7 @@ class Embedder:
         # row tiles come out in whole rounds of the chip for every GEMM width: with a fixed caption count the n = width GEMMs of a
         # 512-wide tower (two tile columns) ran 1.3 ... 6.2 rounds by bucket (65 ... 97 % full).  None: text_batch_size captions.
         # Towers that need single-length groups (biomed.BertTextTower) default to the image micro-batch's row count.
-        if text_token_budget is None and getattr(getattr(self.model, "text", None), "exact_lengths", False):
+        if text_token_budget is None and _length_grouped(getattr(self.model, "text", None)):
             cfg = getattr(self.model, "cfg", None)
             if cfg is not None and hasattr(cfg, "patch_size"):
                 text_token_budget = batch_size * ((cfg.image_size // cfg.patch_size) ** 2 + 1)
@@ -258,7 +264,7 @@ class Embedder:
         other towers."""
         tower = getattr(self.model, "text", None)
         last = self._last_token(ids)
-        if not (getattr(tower, "exact_lengths", False) and hasattr(tower, "pad_token_id")):
+        if not (_length_grouped(tower) and hasattr(tower, "pad_token_id")):
             return last.cpu(), None
         marks = torch.stack([last, (ids != tower.pad_token_id).sum(-1)]).cpu()
         return marks[0], marks[1] != marks[0] + 1
@@ -287,8 +293,10 @@ class Embedder:
             return out
         bucketed = eot is not None and hasattr(tower, "seq_len_for")
         # a tower without a padding mask in its kernels (BERT: bidirectional attention) runs every caption at exactly its own
-        # length: its micro-batches must be single-length groups, so its captions are always sorted
-        exact = bucketed and getattr(tower, "exact_lengths", False)
+        # length: its micro-batches must be single-length groups, so its captions are always sorted.  With the tower's
+        # length_bucket on, seq_len_for() rounds up to the bucket: the groups are single-BUCKET groups, cut by the same rule, and
+        # the captions' own counts travel along as `lengths` (the attention kernels mask the pads behind each caption)
+        exact = bucketed and _length_grouped(tower)
 
         perm = spans = None
         if bucketed and (exact or (self.length_bucketing and ids.shape[0] > self.text_batch_size)):
