@@ -15,6 +15,11 @@
  *     comment says otherwise;
  *   - return value: 0 = ok, <0 = error (LEMON_E_*); lemon_last_error() returns a
  *     thread-local description of the last failure;
+ *   - row alignment: the query and embedding rows handed to lemon_index_search, lemon_neighbors and lemon_discrepancy
+ *     must start on a 16-byte boundary when d % 4 == 0 (kernels behind the search read such rows 16 bytes at a time);
+ *     a pointer that does not is refused with LEMON_E_INVALID before anything is launched.  With d % 4 != 0 any float
+ *     pointer is accepted.  The row-wise helpers (lemon_normalize_rows, lemon_paired_distance, lemon_paired_metric)
+ *     take any float pointer at every d;
  *   - caller owns every output buffer; the library owns only what is inside a
  *     lemon_index handle; one handle per thread.  The ONLY process-wide state is
  *     lemon_linear_f32's hipBLASLt handle + workspace + solution cache (one set per
@@ -389,7 +394,8 @@ const float *lemon_index_data(const lemon_index_t *idx);
  * Grows an internal workspace on first use of a larger (nq,k): that first call is not
  * graph-capturable; later calls with nq,k no larger only enqueue kernels.  With LEMON_ALGO_AUTO
  * (default) the first LARGE search (ntotal >= 65536, nq*ntotal >= 8e9, d <= 768) after an add()
- * runs a small probe search and synchronises the stream once to choose between the two scans. */
+ * runs a small probe search and synchronises the stream once to choose between the two scans.
+ * q_dev: 16-byte aligned when d % 4 == 0 (see "row alignment" above), else LEMON_E_INVALID. */
 int lemon_index_search(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
                        float *D_dev, int64_t *I_dev, void *stream);
 int lemon_index_set_algo(lemon_index_t *idx, int algo);
@@ -453,6 +459,8 @@ int lemon_debug_scan_plan(int panels, int n_tiles, int *grid, int *splits, int *
  * such limit, but the loop's per-sample record is built from ONE scan pass here; the reference's own grids stop at
  * k = 50 (+1) (experiments.py:86), and deeper lists are available from lemon_index_search (k <= 2048).  Larger k is
  * refused with LEMON_E_INVALID, never truncated.  De-duplication of identical query rows is applied to idx_txt only.
+ * q_img_dev, q_txt_dev: 16-byte aligned when d % 4 == 0 (see "row alignment" above), else LEMON_E_INVALID and no output
+ * is written.
  */
 int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, const float *dists_tr_dev,
                     const float *q_img_dev, const float *q_txt_dev, int64_t nq, int k,
@@ -467,7 +475,8 @@ int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, const float 
  * second-order neighbours (through the DB's own text kNN cache of k+1, self removed by index, :165-169)
  * of its k (+1 on train, not dropped) text neighbours; method 1 = div_x / div_y: sum of pairwise cosine
  * distances inside the neighbour set divided by k^2.  E_tr_dev [ntotal,d] are the DB embeddings of the
- * scored modality (x: image, y: text); neighbours always come from idx_txt (:209).  out_dev [nq]. */
+ * scored modality (x: image, y: text); neighbours always come from idx_txt (:209).  out_dev [nq].
+ * E_tr_dev, qv_dev, q_txt_dev: 16-byte aligned when d % 4 == 0 (see "row alignment" above), else LEMON_E_INVALID. */
 int lemon_discrepancy(int method, lemon_index_t *idx_txt, const float *E_tr_dev, const float *qv_dev,
                       const float *q_txt_dev, int64_t nq, int k, int is_train, float *out_dev, void *stream);
 

@@ -27,6 +27,11 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
 
 static inline int64_t round_up64(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
+// Caller-owned embedding / query rows: with d % 4 == 0 some kernels behind the search read them 16 bytes at a time on the
+// strength of d alone (exact_score and the staged k_bf16_final in knn_bf16.hip), so such rows must start on a 16-byte
+// boundary.  With d % 4 != 0 every kernel walks rows one float at a time and any float pointer will do.
+static inline bool rows_vector_safe(const float *p, int d) { return (d & 3) != 0 || (((uintptr_t)p) & 15) == 0; }
+
 // ---- index lifetime ---------------------------------------------------------------------
 extern "C" int lemon_index_create(int metric, int d, lemon_index_t **out) {
     LEMON_REQUIRE(out != nullptr, "out pointer");
@@ -243,6 +248,7 @@ int lemon_search_internal(lemon_index_t *idx, const float *q_dev, int64_t nq, in
     LEMON_REQUIRE(k >= 1 && k <= LEMON_MAX_K_DEEP, "1 <= k <= LEMON_MAX_K_DEEP");
     if (nq == 0) return LEMON_OK;
     LEMON_REQUIRE(q_dev && D_dev && I_dev, "null pointer");
+    LEMON_REQUIRE(rows_vector_safe(q_dev, idx->d), "q_dev must be 16-byte aligned when d % 4 == 0");
     // identical query rows (class prompts: 50 000 text queries, 100 distinct rows on CIFAR-100) are searched once
     if (idx->qdedup && nq >= LEMON_DEDUP_MIN_NQ && nq < ((int64_t)1 << 31) && idx->n > 0) {
         int64_t U = 0;
@@ -471,6 +477,8 @@ extern "C" int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, c
     LEMON_REQUIRE(dists_tr_dev && q_img_dev && q_txt_dev && d1_dev && D_n_dev && dists_n_dev &&
                       dists_tr_n_dev && D_m_dev && dists_m_dev && dists_tr_m_dev, "null pointer");
     LEMON_REQUIRE(!discrete || (tr_label_id_dev && q_label_id_dev), "label ids required when discrete");
+    LEMON_REQUIRE(rows_vector_safe(q_img_dev, idx_img->d) && rows_vector_safe(q_txt_dev, idx_img->d),
+                  "q_img_dev and q_txt_dev must be 16-byte aligned when d % 4 == 0");
     // raw search outputs live in the image index's neighbour workspace: [2][nq, ks]
     const int64_t need = 2 * nq * ks;
     if (need > idx_img->ws_nb) {
@@ -587,6 +595,9 @@ extern "C" int lemon_discrepancy(int method, lemon_index_t *idx_txt, const float
     LEMON_REQUIRE(nq >= 0 && k >= 1 && k + 1 <= LEMON_MAX_K, "nq >= 0, 1 <= k < LEMON_MAX_K");
     if (nq == 0) return LEMON_OK;
     LEMON_REQUIRE(E_tr_dev && q_txt_dev && out_dev && (method == 1 || qv_dev), "null pointer");
+    LEMON_REQUIRE(rows_vector_safe(E_tr_dev, idx_txt->d) && rows_vector_safe(qv_dev, idx_txt->d) &&
+                      rows_vector_safe(q_txt_dev, idx_txt->d),
+                  "E_tr_dev, qv_dev and q_txt_dev must be 16-byte aligned when d % 4 == 0");
     const int kc = k + 1, kq = k + (is_train ? 1 : 0);
     const int64_t n = idx_txt->n;
     // scratch: cache [n, kc] (dis only) + Im [nq, kq] (+ the D arrays the searches return)

@@ -31,13 +31,16 @@ def stream_ptr(device=None):
 
 
 def dev_f32(t, name="tensor"):
-    """Contiguous float32 CUDA tensor (converted if needed); refuses CPU tensors."""
+    """Contiguous float32 CUDA tensor on a 16-byte boundary (converted or copied if needed); refuses CPU tensors.  The
+    search entry points refuse rows that are not 16-byte aligned when d % 4 == 0 (include/lemon_hip.h, "row alignment"): a
+    view that starts in the middle of a buffer is copied here so that they never see one."""
     if not torch.is_tensor(t):
         raise TypeError(f"{name}: expected a torch CUDA tensor, got {type(t).__name__}")
     if not t.is_cuda:
         raise _lib.LemonHipError(f"{name} lives on {t.device}: the LEMoN hot path only runs on the GPU "
                                  "(no CPU fallback). Move it with .cuda().")
-    return t.detach().to(torch.float32).contiguous()
+    t = t.detach().to(torch.float32).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
 
 
 def ptr(t):
