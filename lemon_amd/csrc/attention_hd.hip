@@ -19,10 +19,9 @@
 
 #include "common.hpp"
 #include "split3.hpp"
+#include "attention_hd64.hpp"   // f32x16, store_row8
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int X_WMAX = 4, X_TB = 2, X_KB = 32 * X_TB;      // waves per workgroup, key tiles and keys per block
 static_assert(2 * X_TB >= X_WMAX, "the output image (32 rows per wave) must fit the K and V regions");
@@ -186,16 +185,7 @@ __global__ __launch_bounds__(64 * X_WMAX, HDP == 96 ? 3 : 2) void k_attention_hd
         if (rl < 32 * ntiles && r < L) {
             const float4 v0 = *reinterpret_cast<const float4 *>(&sK[rl * PITCH + 8 * c8]);
             const float4 v1 = *reinterpret_cast<const float4 *>(&sK[rl * PITCH + 8 * c8 + 4]);
-            if (SPLIT == 3)
-                lemon_split::store_tiled8<lemon_split::TILE_A_ROWS, false>(reinterpret_cast<unsigned short *>(out), b * L + r, H * hd, head * nc8 + c8, v0, v1);
-            else if (SPLIT)
-                lemon_split::store_split8<(SPLIT == 1 || SPLIT == 2) ? SPLIT : 1, false>(reinterpret_cast<unsigned short *>(out) + (b * L + r) * lemon_split::split_segments(SPLIT == 3 ? 2 : SPLIT) * (int64_t)(H * hd), H * hd,
-                                                 head * nc8 + c8, v0, v1);
-            else {
-                float *dst = out + ((b * L + r) * H + head) * hd + 8 * c8;
-                *reinterpret_cast<float4 *>(dst) = v0;
-                *reinterpret_cast<float4 *>(dst + 4) = v1;
-            }
+            store_row8<SPLIT>(out, b * L + r, H, hd, nc8, head, c8, v0, v1);
         }
     }
 }

@@ -318,3 +318,18 @@ def test_no_kernel_uses_a_packed_fp32_op_with_op_sel():
         for name, lines in _kernel_bodies(_kernel_asm(src)).items():
             bad = [ln.strip() for ln in lines if re.search(r"\bv_pk_\w+_f32\b", ln) and re.search(r"op_sel:\[[01,]*1", ln)]
             assert not bad, (src, name, bad[:3])
+
+
+# ---- every local header a unit includes is a dependency of the build: an edit to one that build.py does not list would leave stale
+# objects behind (no compiler needed) ----
+def test_every_included_header_is_a_build_dependency():
+    from lemon_amd import build
+    listed = {os.path.basename(h) for h in build.HEADERS + build.JPEG_HOST_HEADERS}
+    seen = 0
+    for fn in sorted(os.listdir(CSRC)):
+        if not fn.endswith((".hip", ".hpp")):
+            continue
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+\.hpp)"', open(os.path.join(CSRC, fn)).read(), re.M):
+            seen += 1
+            assert os.path.basename(inc) in listed and os.path.exists(os.path.join(CSRC, inc)), (fn, inc)
+    assert seen, "the scan must see the units' includes"

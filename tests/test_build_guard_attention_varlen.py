@@ -1,5 +1,6 @@
-"""CPU (hipcc cross-compiles gfx950 here): the per-sequence-length attention kernels (csrc/attention_varlen.hip) restate three
-kernels of csrc/attention.hip in a translation unit of their own.  Checked on the generated code object:
+"""CPU (hipcc cross-compiles gfx950 here): the per-sequence-length attention kernels (csrc/attention_varlen.hip) are the VL = true
+instantiations of the three bodies in csrc/attention_hd64.hpp, whose VL = false instantiations are kernels of csrc/attention.hip,
+in a translation unit of their own.  Checked on the generated code object:
   * the new unit holds its 24 instantiations (short form: TJ 1, 2 x four output forms x both arithmetics; the fp32 general and
     the staged split-fp16 form x four output forms), under names the guards of the existing units do not count;
   * attention.hip and attention_hd.hip hold what they held;
