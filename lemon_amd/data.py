@@ -111,19 +111,16 @@ def resize_geometry(h, w, size):
     return nh, nw, int(round((nh - size) / 2.0)), int(round((nw - size) / 2.0))
 
 
-@functools.lru_cache(maxsize=16)
-def _gpu_transform_plan(h, w, size, device_index):
-    """Resize geometry of generic_transform for an h x w image + the cropped tap tables on the device."""
-    if (w <= h and w != size) or (h <= w and h != size):
-        nw, nh = (size, int(size * h / w)) if w <= h else (int(size * w / h), size)
-    else:
-        nw, nh = w, h
+def transform_geometry(h, w, size):
+    """Resize geometry of generic_transform for an h x w image on the host (numpy only): the cropped tap tables and the block
+    geometry of lemon_preprocess_u8 -- rows_per_block output rows per workgroup, max_rows the input rows the widest block's
+    vertical windows span.  The kernel takes a block's first input row from its first output row and the last from its last
+    (windows are monotone in y) and sizes its LDS tile by max_rows."""
+    nh, nw, top, left = resize_geometry(h, w, size)
     if nw < size or nh < size:
         raise ValueError(f"image {h}x{w} resizes to {nh}x{nw}, smaller than the {size}x{size} crop")
-    left, top = int(round((nw - size) / 2.0)), int(round((nh - size) / 2.0))
-    kk_h, b_h = pil_bicubic_tables(w, nw)
-    kk_v, b_v = pil_bicubic_tables(h, nh)
-    kk_h, b_h, kk_v, b_v = kk_h[left:left + size], b_h[left:left + size], kk_v[top:top + size], b_v[top:top + size]
+    kk_h, b_h = pil_bicubic_rows(w, nw, left, left + size)
+    kk_v, b_v = pil_bicubic_rows(h, nh, top, top + size)
     rows_per_block = 16
     while True:     # input rows one block's vertical windows span; shrink the block until the tile fits LDS
         spans = [int(b_v[min(y0 + rows_per_block, size) - 1].sum() - b_v[y0, 0]) for y0 in range(0, size, rows_per_block)]
@@ -134,10 +131,18 @@ def _gpu_transform_plan(h, w, size, device_index):
         rows_per_block //= 2
     if not fits:
         raise ValueError(f"image {h}x{w}: vertical window of {max(spans)} rows / {kk_v.shape[1]} taps does not fit the LDS tile")
-    dev = torch.device("cuda", device_index)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    return dict(kk_h=t(kk_h), b_h=t(b_h), kk_v=t(kk_v), b_v=t(b_v), ks_h=kk_h.shape[1], ks_v=kk_v.shape[1],
+    return dict(kk_h=kk_h, b_h=b_h, kk_v=kk_v, b_v=b_v, ks_h=kk_h.shape[1], ks_v=kk_v.shape[1],
                 max_rows=max(spans), rows_per_block=rows_per_block)
+
+
+@functools.lru_cache(maxsize=16)
+def _gpu_transform_plan(h, w, size, device_index):
+    """transform_geometry(h, w, size) with the tap tables on the device."""
+    plan = transform_geometry(h, w, size)
+    dev = torch.device("cuda", device_index)
+    for key in ("kk_h", "b_h", "kk_v", "b_v"):
+        plan[key] = torch.from_numpy(np.ascontiguousarray(plan[key])).to(dev)
+    return plan
 
 
 class PatchOperand:
