@@ -661,6 +661,55 @@ int64_t lemon_jpeg_prog_entropy_workspace_bytes(int64_t batch, int64_t total_ite
 int lemon_jpeg_prog_entropy_par_host(const uint8_t *packet, int64_t packet_bytes, uint8_t *record, int64_t record_cap,
                                      int32_t *status);
 
+/* ---- caption tokenizers on the device, opt-in (LEMON_TOKENIZE=device): the captions cross PCIe as raw bytes and the id matrix is
+ * written where the text tower reads it.  Two vocabularies: the CLIP byte-pair encoding and BERT WordPiece.  The device serves
+ * the rows inside an envelope -- every byte one of {9, 10, 13, 32 .. 126}, no '&', no "<|", for WordPiece no whitespace-delimited
+ * word equal to [PAD] [UNK] [CLS] [SEP] [MASK] -- on which text cleaning reduces to whitespace collapse and ASCII lower-casing
+ * (csrc/tokenize_core.hpp).  Every other row gets one of the status codes below, is written as all pad_id with length 0, and is
+ * the caller's to tokenise (lemon_amd/tokenizer.py: device_form); nothing here falls back and nothing is truncated silently. */
+#define LEMON_TOK_NON_ASCII 1 /* a byte outside {9, 10, 13, 32 .. 126}                                                    */
+#define LEMON_TOK_AMPERSAND 2 /* an '&': html.unescape may rewrite the text                                               */
+#define LEMON_TOK_SPECIAL 3   /* "<|" (CLIP's special tokens), or a reserved [XXX] word of WordPiece                      */
+#define LEMON_TOK_TOO_LONG 4  /* more than LEMON_TOKENIZE_MAX_BYTES bytes                                                 */
+#define LEMON_TOK_WORD 5      /* a word, among those that can reach the row, of more than LEMON_TOKENIZE_MAX_WORD symbols
+                                 (CLIP: bytes of the token; WordPiece: pieces of the word)                                */
+#define LEMON_TOK_BUFFER 6    /* the row's offsets are not ordered or leave text_bytes: the row was not read             */
+/* a row with several reasons reports LEMON_TOK_BUFFER, else LEMON_TOK_TOO_LONG, else the lowest of codes 1 .. 3 */
+#define LEMON_TOKENIZE_MAX_BYTES 4096
+#define LEMON_TOKENIZE_MAX_WORD 64
+#define LEMON_TOKENIZE_MAX_CTX 1024
+typedef struct lemon_tokenizer lemon_tokenizer_t;
+/* The merges table of lib/models/simple_tokenizer.py:86-104 (SimpleTokenizer.__init__) by id: merge m joins the symbols with ids
+ * left[m] and right[m] at rank[m] (lower = earlier) into the symbol with id merged[m]; the caller leaves out merges whose parts
+ * or result have no id.  All ids < 65535.  The pairs go into a hash table keyed by (left, right), compared exactly, of load
+ * factor <= 0.5 and probe sequences <= 64.  LEMON_E_INVALID: an id out of range, one pair given two meanings, no such table.
+ * Host only, no GPU: the table is uploaded by the first lemon_tokenize, to the device current then. */
+int lemon_tokenizer_create_bpe(const int32_t *left, const int32_t *right, const int32_t *rank, const int32_t *merged, int64_t n_merges,
+                               int32_t sot_id, int32_t eot_id, lemon_tokenizer_t **out);
+/* The vocabulary of lib/models/utils.py:72-78's tokenizer (open_clip's HFTokenizer around BERT WordPiece): token v is the bytes
+ * blob[offsets[v], offsets[v + 1]) with id ids[v] < 65535.  A lookup hashes the piece and then compares it with the stored bytes,
+ * so a collision cannot change an id.  lower_case and max_chars as BertTokenizer's do_lower_case and max_input_chars_per_word.
+ * home_buckets: 0; a power of two restricts the home slots to that many (test hook: 2 forces collisions).  Host only, no GPU. */
+int lemon_tokenizer_create_wordpiece(const uint8_t *blob, const int64_t *offsets, const int32_t *ids, int64_t n_tokens, int32_t cls_id,
+                                     int32_t sep_id, int32_t unk_id, int lower_case, int max_chars, int home_buckets,
+                                     lemon_tokenizer_t **out);
+int lemon_tokenizer_free(lemon_tokenizer_t *tok);
+/* slots and entries of the hash table and its longest probe sequence */
+int lemon_tokenizer_table_info(const lemon_tokenizer_t *tok, int64_t *slots, int64_t *entries, int *max_probe);
+/* The tokenizer calls of the hot path for a batch -- lib/models/chexzero_clip.py:481-493 (tokenize: pad_id 0), run_lemon.py:140-154
+ * (the HF call with padding="max_length", truncation=True: pad_id = the end-of-text id) and lib/models/utils.py:72-78 (pad_id =
+ * [PAD]).  Row r is text_dev[offsets_dev[r], offsets_dev[r + 1]) (offsets_dev: n + 1 entries).  ids_dev [n, ctx] int64: first
+ * token, word ids, last token, pad_id; a row with more than ctx - 2 word ids keeps the first ctx - 2 and ends in the last token.
+ * length_dev [n]: tokens before the padding.  status_dev [n]: 0 or a LEMON_TOK_* code.  2 <= ctx <= LEMON_TOKENIZE_MAX_CTX.  One
+ * launch on `stream`, no synchronisation (the first call of a tokenizer uploads its table, synchronously); a wave per row, every
+ * loop bounded: merge rounds by the symbols of a word, probes by the table's longest sequence. */
+int lemon_tokenize(lemon_tokenizer_t *tok, const uint8_t *text_dev, int64_t text_bytes, const int64_t *offsets_dev, int64_t n, int ctx,
+                   int32_t pad_id, int64_t *ids_dev, int32_t *length_dev, uint8_t *status_dev, void *stream);
+/* lemon_tokenize's algorithm with the lanes looped on the host, on host pointers: the same functions, chunks and word groups, so
+ * the same ids, lengths and statuses.  Test support for the same call sites where there is no GPU; no product path calls it. */
+int lemon_tokenize_host(const lemon_tokenizer_t *tok, const uint8_t *text, int64_t text_bytes, const int64_t *offsets, int64_t n, int ctx,
+                        int32_t pad_id, int64_t *ids, int32_t *length, uint8_t *status);
+
 #ifdef __cplusplus
 }
 #endif

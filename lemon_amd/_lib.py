@@ -28,6 +28,8 @@ EXPORTS = [
     "lemon_jpeg_pack", "lemon_jpeg_entropy_device", "lemon_jpeg_entropy_workspace_bytes", "lemon_jpeg_entropy_par_host",
     "lemon_jpeg_prog_info", "lemon_jpeg_prog_entropy", "lemon_jpeg_prog_pack", "lemon_jpeg_prog_entropy_device",
     "lemon_jpeg_prog_entropy_workspace_bytes", "lemon_jpeg_prog_entropy_par_host",
+    "lemon_tokenizer_create_bpe", "lemon_tokenizer_create_wordpiece", "lemon_tokenizer_free", "lemon_tokenizer_table_info",
+    "lemon_tokenize", "lemon_tokenize_host",
 ]
 
 
@@ -151,6 +153,13 @@ def load():
     lib.lemon_jpeg_prog_entropy_workspace_bytes.argtypes = [c_i64, c_i64, ctypes.c_int32]
     lib.lemon_jpeg_prog_entropy_workspace_bytes.restype = c_i64
     lib.lemon_jpeg_prog_entropy_par_host.argtypes = [vp, c_i64, vp, c_i64, ctypes.POINTER(ctypes.c_int32)]
+    i32 = ctypes.c_int32
+    lib.lemon_tokenizer_create_bpe.argtypes = [vp, vp, vp, vp, c_i64, i32, i32, ctypes.POINTER(vp)]
+    lib.lemon_tokenizer_create_wordpiece.argtypes = [vp, vp, vp, c_i64, i32, i32, i32, c_int, c_int, c_int, ctypes.POINTER(vp)]
+    lib.lemon_tokenizer_free.argtypes = [vp]
+    lib.lemon_tokenizer_table_info.argtypes = [vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)]
+    lib.lemon_tokenize.argtypes = [vp, vp, c_i64, vp, c_i64, c_int, i32, vp, vp, vp, vp]
+    lib.lemon_tokenize_host.argtypes = [vp, vp, c_i64, vp, c_i64, c_int, i32, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -140,7 +140,16 @@ def prepare(args):
             return noisy_txt, clean_txt, [prompt_fn(t) for t in noisy_txt]
         return list(noisy), list(clean), list(noisy)
 
+    # LEMON_TOKENIZE=device: the captions are tokenised on the GPU (tokenizer.device_form: the same ids, in HBM) where the
+    # tokenizer has a device form; the AutoTokenizer and synthetic tokenizers stay on the host
+    from .tokenizer import device_form, tokenize_mode
+    device_tokenize = device_form(tokenizer, device) if tokenize_mode() == "device" else None
+    if tokenize_mode() == "device" and device_tokenize is None and rank == 0:
+        print("note: LEMON_TOKENIZE=device, but this tokenizer has no device form (or ftfy is installed): tokenising on the host")
+
     def tokenize(prompts):
+        if device_tokenize is not None:
+            return device_tokenize(prompts)
         if not hf_style:
             return tokenizer(prompts)
         enc = tokenizer(prompts, padding="max_length", truncation=True)

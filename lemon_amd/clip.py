@@ -722,8 +722,8 @@ def algorithm_class_from_scratch(name, text_base_name="openai/clip-vit-base-patc
             return model
         bpe = _bpe_tokenizer(bpe_path) if model.cfg.vocab_size == 49408 else None
         if bpe is not None:
-            from .tokenizer import tokenize
-            tok = lambda texts: tokenize(texts, model, bpe)
+            from .tokenizer import ClipTokenize
+            tok = ClipTokenize(bpe, model.context_length)
         elif rand:
             syn = SyntheticTokenizer(model.cfg.vocab_size, model.cfg.context_length, model.cfg.eos_token_id)
             tok = lambda texts: torch.tensor(syn(texts)["input_ids"], dtype=torch.long)

@@ -183,10 +183,16 @@ def embed_caption_text(embedder, tokenize, text_list, batch_size=4096):
     return normalize_vectors(torch.cat(out)) if out else torch.empty((0, d), device=embedder.device)
 
 
-def make_tokenize(tokenizer):
+def make_tokenize(tokenizer, device=None):
     """The two tokenizer conventions of lib/models/utils.py:64-105 as one list-of-strings -> LongTensor [n, context]
     function: the HF tokenizer is called with padding="max_length", truncation=True and returns a dict of lists
-    (clustering.py:58-60), the in-tree ones return the id tensor themselves (:54)."""
+    (clustering.py:58-60), the in-tree ones return the id tensor themselves (:54).  With `device` and LEMON_TOKENIZE=device
+    the tokenizer's device form is returned where it has one (tokenizer.device_form: the same ids, on the GPU)."""
+    from .tokenizer import device_form, tokenize_mode
+    on_device = device_form(tokenizer, device) if device is not None and tokenize_mode() == "device" else None
+    if on_device is not None:
+        return on_device
+
     def tokenize(prompts):
         try:
             enc = tokenizer(prompts, padding="max_length", truncation=True)
@@ -199,7 +205,7 @@ def make_tokenize(tokenizer):
 def cluster_caption_text(embedder, tokenizer, text_list, n_clusters=100, random_state=42, **kmeans_kwargs):
     """clustering.py:69-75: embed the captions, normalise, fit, predict -> (km, labels int64 [n] on the host).
     `tokenizer`: the tokenizer algorithm_class_from_scratch returns, or any list-of-strings -> LongTensor callable."""
-    tokenizer = make_tokenize(tokenizer)
+    tokenizer = make_tokenize(tokenizer, embedder.device)
     emb = embed_caption_text(embedder, tokenizer, text_list)
     km = KMeans(n_clusters=n_clusters, seed=random_state, device=emb.device,
                 embed_func=lambda texts: embed_caption_text(embedder, tokenizer, texts), **kmeans_kwargs)

@@ -19,6 +19,7 @@ downloaded and no vocabulary ships with this package.  Text cleaning: `ftfy.fix_
 import gzip
 import html
 import os
+import sys
 from functools import lru_cache
 
 import regex as re
@@ -305,3 +306,177 @@ def find_vocab_file(hint=None):
         if d and os.path.isfile(os.path.join(d, "vocab.txt")):
             return os.path.join(d, "vocab.txt")
     return None
+
+
+# ---- the same tokenizers on the device (include/lemon_hip.h: lemon_tokenize), opt-in with LEMON_TOKENIZE=device -----------------
+# The captions cross PCIe as raw bytes and the id matrix is written in HBM, where Embedder.embed_texts reads it.  The device serves
+# the rows on which text cleaning is the identity up to whitespace and ASCII case (printable ASCII without '&' and "<|"); every
+# other row comes back with a status and is tokenised here, by the host tokenizer itself, and scattered into the matrix.
+class ClipTokenize:
+    """`tokenizer(texts)` of the in-tree CLIP branches: tokenize(texts, context_length, bpe) -> LongTensor [n, context_length]."""
+
+    def __init__(self, bpe, context_length):
+        self.bpe, self.context_length = bpe, context_length
+
+    def __call__(self, texts):
+        return tokenize(texts, self.context_length, self.bpe)
+
+
+def tokenize_mode():
+    """$LEMON_TOKENIZE: 'host' (default) or 'device'."""
+    mode = os.environ.get("LEMON_TOKENIZE", "host")
+    if mode not in ("host", "device"):
+        raise ValueError(f"LEMON_TOKENIZE={mode!r}: host or device")
+    return mode
+
+
+def _ftfy_present():
+    import importlib.util
+    try:
+        return importlib.util.find_spec("ftfy") is not None
+    except (ImportError, ValueError):
+        return True
+
+
+def bpe_id_table(bpe):
+    """(left, right, rank, merged) int32 arrays of the merges that can fire -- both parts and the result have an id in
+    `bpe.encoder` --, or None when the ids do not fit the device table (16 bits) or two symbols share an id."""
+    import numpy as np
+    enc = bpe.encoder
+    if max(enc.values()) >= 65535 or len(set(enc.values())) != len(enc):
+        return None
+    rows = [(enc[a], enc[b], r, enc[a + b]) for (a, b), r in bpe.ranks.items() if a in enc and b in enc and 0 <= r < 2 ** 31]
+    arr = np.array(rows, dtype=np.int32).reshape(-1, 4)
+    return tuple(np.ascontiguousarray(arr[:, c]) for c in range(4))
+
+
+class DeviceTokenizer:
+    """texts -> LongTensor [n, context_length] on `device`, equal to the host tokenizer's matrix.  After a call: `lengths`
+    (int32 [n], tokens before the padding) and `declined` (rows the device handed back, tokenised on the host)."""
+
+    def __init__(self, host, device, home_buckets=0):
+        import ctypes
+        import numpy as np
+        import torch
+        from . import _lib
+        self.host, self.device, self.lib = host, torch.device(device), _lib.load()
+        self.handle, self.lengths, self.declined = ctypes.c_void_p(), None, 0
+        if isinstance(host, BertWordPiece):
+            self.ctx, self.pad = host.context_length, host.pad
+            toks = [t.encode("utf-8", "surrogatepass") for t in host.vocab]
+            offsets = np.zeros(len(toks) + 1, dtype=np.int64)
+            np.cumsum([len(t) for t in toks], out=offsets[1:])
+            blob = np.frombuffer(b"".join(toks) or b"\0", dtype=np.uint8)
+            ids = np.fromiter(host.vocab.values(), dtype=np.int64, count=len(toks))
+            if ids.min(initial=0) < 0 or ids.max(initial=0) >= 65535:
+                raise ValueError("vocabulary ids do not fit the device table")
+            ids = ids.astype(np.int32)
+            rc = self.lib.lemon_tokenizer_create_wordpiece(blob.ctypes.data, offsets.ctypes.data, ids.ctypes.data, len(toks), host.cls, host.sep,
+                                                           host.unk, int(bool(host.lower_case)), min(int(host.max_chars), 2 ** 30), home_buckets,
+                                                           ctypes.byref(self.handle))
+        else:
+            self.ctx = host.model_max_length if isinstance(host, HFStyleClipTokenizer) else host.context_length
+            self.pad = host.bpe.eot_id if isinstance(host, HFStyleClipTokenizer) else 0
+            table = bpe_id_table(host.bpe)
+            if table is None:
+                raise ValueError("vocabulary ids do not fit the device table")
+            left, right, rank, merged = table
+            rc = self.lib.lemon_tokenizer_create_bpe(left.ctypes.data, right.ctypes.data, rank.ctypes.data, merged.ctypes.data, len(left),
+                                                     host.bpe.sot_id, host.bpe.eot_id, ctypes.byref(self.handle))
+        _lib.check(rc, "lemon_tokenizer_create")
+
+    def __del__(self):
+        if getattr(self, "handle", None) and not sys.is_finalizing():      # at interpreter exit the runtime frees the table
+            self.lib.lemon_tokenizer_free(self.handle)
+            self.handle = None
+
+    def table_info(self):
+        """(slots, entries, longest probe sequence) of the hash table"""
+        import ctypes
+        from . import _lib
+        slots, entries, probe = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+        _lib.check(self.lib.lemon_tokenizer_table_info(self.handle, ctypes.byref(slots), ctypes.byref(entries), ctypes.byref(probe)), "lemon_tokenizer_table_info")
+        return slots.value, entries.value, probe.value
+
+    @staticmethod
+    def pack(texts):
+        """(offsets int64 [n + 1], bytes): the rows' UTF-8 bytes back to back"""
+        import numpy as np
+        texts = [t if isinstance(t, str) else str(t) for t in texts]
+        blob = "".join(texts).encode("utf-8", "surrogatepass")
+        offsets = np.zeros(len(texts) + 1, dtype=np.int64)
+        if len(blob) == sum(map(len, texts)):                        # ASCII only: a character is a byte
+            np.cumsum(np.fromiter(map(len, texts), dtype=np.int64, count=len(texts)), out=offsets[1:])
+        else:
+            np.cumsum([len(t.encode("utf-8", "surrogatepass")) for t in texts], out=offsets[1:])
+        return offsets, blob
+
+    def host_rows(self, texts):
+        """(ids LongTensor [m, ctx], lengths int32 [m]) from the host tokenizer"""
+        import torch
+        if isinstance(self.host, HFStyleClipTokenizer):
+            enc = self.host(texts, padding="max_length", truncation=True)
+            return torch.tensor(enc["input_ids"], dtype=torch.long), torch.tensor(enc["attention_mask"]).sum(-1).to(torch.int32)
+        ids = self.host(texts)
+        last = ids.shape[1] - 1 - (ids.flip(1) != self.pad).to(torch.int32).argmax(1)       # the last token is never the padding id
+        return ids, (last + 1).to(torch.int32)
+
+    def tokenize_host_loop(self, texts, ctx=None, pad=None):
+        """lemon_tokenize_host on the same packed input: (ids int64 [n, ctx], length int32 [n], status uint8 [n]) as numpy arrays.
+        Test support where there is no GPU."""
+        import numpy as np
+        from . import _lib
+        ctx, pad = ctx or self.ctx, self.pad if pad is None else pad
+        offsets, blob = self.pack(texts)
+        n = len(offsets) - 1
+        text = np.frombuffer(blob or b"\0", dtype=np.uint8)
+        ids, length, status = np.full((n, ctx), -7, np.int64), np.full(n, -7, np.int32), np.full(n, 255, np.uint8)
+        _lib.check(self.lib.lemon_tokenize_host(self.handle, text.ctypes.data, len(blob), offsets.ctypes.data, n, ctx, pad, ids.ctypes.data,
+                                                length.ctypes.data, status.ctypes.data), "lemon_tokenize_host")
+        return ids, length, status
+
+    def __call__(self, texts, **_):
+        import numpy as np
+        import torch
+        from . import _lib
+        from .ops import ptr, stream_ptr
+        if isinstance(texts, str):
+            texts = [texts]
+        n, ctx, dev = len(texts), self.ctx, self.device
+        ids = torch.empty((n, ctx), dtype=torch.long, device=dev)
+        self.lengths, self.declined = torch.zeros(n, dtype=torch.int32), 0
+        if n == 0:
+            return ids
+        offsets, blob = self.pack(texts)
+        head = offsets.nbytes                                             # one upload: the offsets, then the text
+        staged = torch.from_numpy(np.concatenate([offsets.view(np.uint8), np.frombuffer(blob, dtype=np.uint8)])).to(dev)
+        back = torch.empty(5 * n, dtype=torch.uint8, device=dev)          # one read-back: int32 lengths, then uint8 statuses
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.lemon_tokenize(self.handle, staged.data_ptr() + head, len(blob), ptr(staged), n, ctx, self.pad, ptr(ids), ptr(back),
+                                               back.data_ptr() + 4 * n, stream_ptr(dev)), "lemon_tokenize")
+        back = back.cpu()
+        lengths, status = back[:4 * n].view(torch.int32).clone(), back[4 * n:]
+        rows = torch.nonzero(status).squeeze(1)
+        if len(rows):
+            host_ids, host_len = self.host_rows([texts[i] for i in rows.tolist()])
+            ids[rows.to(dev)] = host_ids.to(dev)
+            lengths[rows] = host_len
+        self.lengths, self.declined = lengths, len(rows)
+        return ids
+
+
+def device_form(host_tokenizer, device):
+    """The device form of a host tokenizer -- ClipTokenize, HFStyleClipTokenizer or BertWordPiece --: a callable texts ->
+    LongTensor [n, context] on `device` with the host's ids.  None when there is none: another tokenizer class, `ftfy`
+    importable (the host tokenizers then rewrite text in ways the device does not), a context length or a vocabulary that
+    does not fit the device tables."""
+    if not isinstance(host_tokenizer, (ClipTokenize, HFStyleClipTokenizer, BertWordPiece)) or _ftfy_present():
+        return None
+    ctx = host_tokenizer.model_max_length if isinstance(host_tokenizer, HFStyleClipTokenizer) else host_tokenizer.context_length
+    if not 2 <= ctx <= 1024:                      # LEMON_TOKENIZE_MAX_CTX
+        return None
+    from ._lib import LemonHipError
+    try:
+        return DeviceTokenizer(host_tokenizer, device)
+    except (ValueError, LemonHipError):
+        return None
