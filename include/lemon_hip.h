@@ -393,12 +393,25 @@ const float *lemon_index_data(const lemon_index_t *idx);
  * fp32 scan (each pass admits only rows ranked behind the previous pass's last result: same order, same tie rule).
  * Grows an internal workspace on first use of a larger (nq,k): that first call is not
  * graph-capturable; later calls with nq,k no larger only enqueue kernels.  With LEMON_ALGO_AUTO
- * (default) the first LARGE search (ntotal >= 65536, nq*ntotal >= 8e9, d <= 768) after an add()
+ * (default) the first LARGE search (ntotal >= 65536, nq*ntotal >= 8e9, d <= 768 -- d <= 1280 once
+ * lemon_index_set_wide_filter(idx, 1) has switched the wide filter kernel on) after an add()
  * runs a small probe search and synchronises the stream once to choose between the two scans.
  * q_dev: 16-byte aligned when d % 4 == 0 (see "row alignment" above), else LEMON_E_INVALID. */
 int lemon_index_search(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
                        float *D_dev, int64_t *I_dev, void *stream);
 int lemon_index_set_algo(lemon_index_t *idx, int algo);
+/* index.search(x, k) on embeddings wider than 768 (run_lemon.py:235-236 with a ViT-H/14, g/14 or bigG/14 tower: d = 1024 /
+ * 1280): enabled != 0 lets LEMON_ALGO_BF16_FILTER serve 768 < d <= 1280 with a register-resident fp16 filter kernel (16-bit
+ * copies at column pitch 1024 / 1280) and raises LEMON_ALGO_AUTO's width limit from 768 to 1280; results stay bit-identical to
+ * LEMON_ALGO_F32_MFMA.  Off by default (LEMON_WIDE_FILTER=1 turns it on process-wide): with it off every call takes the path
+ * it took before.  Toggling it on an index whose 16-bit copy exists at the other pitch rebuilds that copy at the next filter
+ * search (one stream synchronisation). */
+int lemon_index_set_wide_filter(lemon_index_t *idx, int enabled);
+/* Which scan kernel served the last index.search (run_lemon.py:235-236) -- the family name of its dominant kernel, a static
+ * string: "scan_f32" (LEMON_ALGO_F32_MFMA), or for LEMON_ALGO_BF16_FILTER "scan_bf16" (streaming), "qs", "qs2", "qs4"
+ * (Q-stationary, d <= 768) or "qsw" (Q-stationary, 768 < d <= 1280 with the wide filter on); "" before any search.
+ * lemon_search_info_t cannot tell "qsw" from "scan_bf16": both run 128-query panels. */
+const char *lemon_index_last_scan_kernel(const lemon_index_t *idx);
 /* Query de-duplication (on by default; LEMON_QUERY_DEDUP=0 disables it process-wide): from 1024 queries on, the rows of
  * q are grouped by content (64-bit hash + stable sort + full bitwise comparison) and, when at most half of them are
  * distinct, the search runs once per distinct row and its (D, I) lists are copied to every member -- exact, because a

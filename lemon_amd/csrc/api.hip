@@ -2,6 +2,7 @@
 #include "common.hpp"
 #include <stdlib.h>
 #include <math.h>
+#include "knn_wide.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -47,6 +48,10 @@ extern "C" int lemon_index_create(int metric, int d, lemon_index_t **out) {
         const char *e = getenv("LEMON_QUERY_DEDUP");
         idx->qdedup = (e && e[0] == '0') ? 0 : 1;
     }
+    {   // wide fp16 filter scan (769 <= d <= 1280): off by default, LEMON_WIDE_FILTER=1 turns it on process-wide
+        const char *e = getenv("LEMON_WIDE_FILTER");
+        idx->wide_filter = (e && e[0] == '1') ? 1 : 0;
+    }
     idx->prof_events = new std::vector<std::pair<hipEvent_t, hipEvent_t>>();
     if (hipGetDevice(&idx->device) != hipSuccess) {
         delete idx->prof_events;
@@ -80,6 +85,18 @@ extern "C" int lemon_index_set_query_dedup(lemon_index_t *idx, int enabled) {
     LEMON_REQUIRE(idx != nullptr, "index handle");
     idx->qdedup = enabled ? 1 : 0;
     return LEMON_OK;
+}
+
+extern "C" int lemon_index_set_wide_filter(lemon_index_t *idx, int enabled) {
+    LEMON_REQUIRE(idx != nullptr, "index handle");
+    const int on = enabled ? 1 : 0;
+    if (on != idx->wide_filter) idx->auto_algo = 0;      // AUTO's width limit follows the switch: probe again
+    idx->wide_filter = on;      // (a 16-bit copy at the other pitch is dropped and rebuilt by the next filter search)
+    return LEMON_OK;
+}
+
+extern "C" const char *lemon_index_last_scan_kernel(const lemon_index_t *idx) {
+    return (idx && idx->last_kernel) ? idx->last_kernel : "";
 }
 
 extern "C" int lemon_index_set_algo(lemon_index_t *idx, int algo) {
@@ -177,7 +194,8 @@ extern "C" int lemon_index_add(lemon_index_t *idx, const float *x_dev, int64_t n
 }
 
 // ---- LEMON_ALGO_AUTO ----------------------------------------------------------------------
-// The 16-bit filter scan (knn_bf16.hip; fp16 operands) is ~5x faster than the fp32 scan on large, "spread out" data, but its work
+// The 16-bit filter scan (knn_bf16.hip; fp16 operands) is ~5x faster than the fp32 scan on large, "spread out" data (d <= 768; the
+// wide kernel's figures at 1024 / 1280: DESIGN.md section 5), but its work
 // grows with the number of database rows whose score lies within the rounding band of a query's
 // k-th best: exact duplicates (class prompts: SURVEY 0.9) or tightly concentrated embeddings put
 // hundreds of rows there and every one of them must be re-scored exactly.  AUTO therefore probes:
@@ -189,7 +207,9 @@ static int lemon_auto_choose(lemon_index_t *idx, const float *q_dev, int64_t nq,
     (void)k;
     const int S = 2048, P = 64, KP = 16;
     const int d = idx->d;
-    if (d > 768 || idx->n < 65536 || (double)nq * (double)idx->n < 8.0e9) return LEMON_ALGO_F32_MFMA;
+    // width limit: the register-resident filter kernels -- 768, or 1280 with the wide filter switched on
+    const int dmax = idx->wide_filter ? LEMON_QSW_MAX_D : 768;
+    if (d > dmax || idx->n < 65536 || (double)nq * (double)idx->n < 8.0e9) return LEMON_ALGO_F32_MFMA;
     if (idx->auto_n == idx->n && idx->auto_algo) return idx->auto_algo;
     int choice = LEMON_ALGO_F32_MFMA;
     float *xs = nullptr, *qs = nullptr, *Dp = nullptr, *qn = nullptr;

@@ -77,6 +77,8 @@ struct lemon_index {
     float *ws_D;          // [ws_nb]
     int64_t *ws_I;        // [ws_nb]
     lemon_search_info_t last;
+    const char *last_kernel;  // family name of the last search's dominant scan kernel (static string; null before any search)
+    int wide_filter;      // 1: widths 769..1280 take the register-resident pitches 1024 / 1280 (k_scan_f16_qsw, knn_bf16.hip)
     // LEMON_ALGO_AUTO decision cache (valid while auto_n == n)
     int auto_algo;
     int64_t auto_n;

@@ -19,6 +19,7 @@
 // re-scored exactly on the spot and cut to k.  The band is a proof, so there is no fallback path and the
 // output is bit-identical to LEMON_ALGO_F32_MFMA and the CPU oracle.
 #include "knn_common.hpp"
+#include "knn_wide.hpp"
 #include <stdlib.h>
 
 using namespace lemon_knn;
@@ -1765,6 +1766,303 @@ __global__ __launch_bounds__(NT, 1) void k_scan_f16_qs4(ScanParamsH p) {
 }
 
 // ======================================================================================
+// QSW: the Q-stationary scan for embeddings wider than 768 (pitches 1024 and 1280: ViT-H/14, g/14, bigG/14), opt-in
+// (lemon_index_set_wide_filter / LEMON_WIDE_FILTER=1).  Inner product AND squared L2 at both pitches.
+//
+// QS4 holds 4 query groups x NS k32 steps of fragments per wave: 128 fragments = 512 registers at pitch 1024, the whole file.
+// Here a wave owns TWO query groups (32 queries, 128 per workgroup) against the same 64-row database tiles and the same
+// 4 x 16 KB LDS-DMA ring: the wave's 64 x 32 tile is 4 x 2 accumulator tiles of 16 x 16 (32 registers), per k32 step 4
+// database fragments x 2 query fragments = 8 MFMAs of 16 cycles.
+// Fragment homes (knn_wide.hpp): (group b, step s) -> f = b NS + s; f < 64 in AccVGPRs, the rest in VGPRs -- 64 fragments =
+// all 256 AccVGPRs at pitch 1024, 64 + 16 at pitch 1280.  Nothing is parked in LDS.
+// Issue slots of a step (behind MFMA i = 4 b + a): the four fragment reads of the NEXT step behind MFMAs 0..3 (group 0's), the
+// two DMA pieces of a step (steps 2 and 3 of a stage, stage t + 3) behind MFMAs 5 and 7 (inside group 1's), so no gap carries
+// two memory instructions.  Four waves read 4 x 1 KB of LDS per 128 cycles each = 128 B/clk/CU of the 256 the array gives.
+// The ring's protocol is QS4's: the barrier sits behind step 1 of a stage, stage t + 1 has landed for everybody by then and
+// the slot of stage t - 1 is free for the pieces of stage t + 3.
+// The filter is NOT interleaved: a tile is 32 / 40 steps = 4 096 / 5 120 MFMA cycles here (QS4: 24 steps of 256), so the
+// tile's filter runs behind its last step -- the next tile's first fragments, read during that step, have landed by then --
+// at ~2 x (8 v_max3 + compare + ballot) exposed per tile.  Candidate bookkeeping is QS4's: a query on four lanes, four
+// lane-private quarter lists, append_slot4's clamp, light compaction with round-robin deal, exact compaction on band overflow,
+// the -inf MFMA for the padding rows of the database's last tile, state in p.state between chunk launches.
+// Tiles, splits and chunks are counted in 64-ROW units, as in QS2 / QS4.
+// ======================================================================================
+constexpr int BQW = 128;       // queries per workgroup (32 per wave)
+static_assert(BQW == BQ, "the host side sizes the wide kernel's panels like the streaming kernel's");
+
+template <int KT, bool l2>
+__global__ __launch_bounds__(NT, 1) void k_scan_f16_qsw(ScanParamsH p) {
+    constexpr int NS = 2 * KT;                 // k32 steps per tile
+    constexpr int KT2 = KT / 2;                // stages per tile: 2 x 64-wide k-slices = 4 k32 steps each
+    constexpr int NFR = 2 * NS;                // query fragments, all in registers: index f = b NS + s
+    constexpr int NB = 4;                      // LDS stage ring
+    constexpr int STG = 2 * RT2 * BK;          // floats per stage (16 KB)
+    static_assert(NT == 2 * BQW && (KT2 == 8 || KT2 == 10) && NFR >= LEMON_QSW_ACC_FRAGS && NFR == 2 * (64 * KT / 32), "fragment homes");
+    __shared__ __attribute__((aligned(16))) float smem[NB * STG + 2 * BQW + (NT / 64) * (512 + 128)];
+    float *s_x = smem;                                   // [NB][2][64 * 32]
+    float *s_qn = smem + NB * STG;                       // [128]
+    float *s_eps = s_qn + BQW;                           // [128]
+    u64 *s_keys = reinterpret_cast<u64 *>(s_eps + BQW);  // [4][256] rank-select scratch
+    u64 *s_best = s_keys + (NT / 64) * 256;              // [4][64]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, g4 = lane >> 4;
+
+    const int panel = blockIdx.x / p.b.splits;
+    const int64_t q0 = (int64_t)panel * BQW;
+    int t_begin = (blockIdx.x % p.b.splits) * p.b.tiles_per_split;
+    int t_end = t_begin + p.b.tiles_per_split;
+    if (t_end > p.b.n_tiles) t_end = p.b.n_tiles;
+    if (p.b.splits == 1) { t_begin = p.chunk_t0; t_end = p.chunk_t1; }
+    const int ntile = t_end > t_begin ? t_end - t_begin : 0;
+    const bool final_pass = (p.b.splits > 1) || p.last_chunk;
+    const int dpad = p.dpad_h / 2;             // row pitch in 4-byte words
+
+    if (tid < BQW) {
+        const float qn = p.b.qnorm[q0 + tid];
+        s_eps[tid] = band_eps(p, qn, p.qres2[q0 + tid], l2);
+        s_qn[tid] = qn;
+    }
+
+    // ---- lane-private candidate state per query group b: query = 32 wave + 16 b + (lane & 15), quarter g4 = lane >> 4 ----
+    const int qrow0 = 32 * wave + l15;                   // group 1: + 16
+    u64 *cand_panel = p.b.cand + (int64_t)blockIdx.x * BQW * CAPH;
+    char *panel_bytes = reinterpret_cast<char *>(cand_panel);
+    const unsigned my_off0 = (unsigned)(qrow0 * CAPH + g4 * QCAP4) * 8u;      // group 1: + 16 * CAPH * 8
+    int ccnt0 = 0, ccnt1 = 0, clast0 = 0, clast1 = 0;
+    float thk0, thk1, qn0 = 0.f, qn1 = 0.f;
+    thk0 = (q0 + qrow0 < p.b.nq) ? -INFINITY : INFINITY;
+    thk1 = (q0 + qrow0 + 16 < p.b.nq) ? -INFINITY : INFINITY;
+    if (l2) { qn0 = p.b.qnorm[q0 + qrow0]; qn1 = p.b.qnorm[q0 + qrow0 + 16]; }
+    if (p.b.splits == 1 && !p.first_chunk) {   // resume from the previous database chunk
+        const float *st = p.state + 8 * ((int64_t)blockIdx.x * NT + tid);
+        ccnt0 = __float_as_int(st[0]); clast0 = __float_as_int(st[1]); thk0 = st[2];
+        ccnt1 = __float_as_int(st[4]); clast1 = __float_as_int(st[5]); thk1 = st[6];
+    }
+    auto th_of = [&](float tk, float qn) -> float {      // what the filter compares against (L2: proxy carries +|q|^2)
+        if (!l2 || tk == -INFINITY || tk == INFINITY) return tk;
+        return (tk + qn) - (fabsf(tk) + qn) * 2.4e-7f - 1e-37f;
+    };
+    float th0 = th_of(thk0, qn0), th1 = th_of(thk1, qn1);
+
+    // ---- stationary operands: fragment (b, s) = the lane's query of group b, k = 32 s + 8 g4 .. + 7 ----
+    bf16x8 qf[NFR];
+    {
+        const lp16 *src = p.qh + (q0 + qrow0) * (int64_t)p.dpad_h + 8 * g4;
+        // (loads in groups of eight with a scheduling fence in between: see k_scan_bf16_qs2)
+#pragma unroll
+        for (int f = 0; f < NFR; ++f) {
+            const int b = f / NS, s2 = f % NS;
+            qf[f] = *reinterpret_cast<const bf16x8 *>(src + (int64_t)(16 * b) * p.dpad_h + 32 * s2);
+            if ((f & 7) == 7) {
+#pragma unroll
+                for (int f2 = f & ~7; f2 <= f; ++f2) { if (f2 < LEMON_QSW_ACC_FRAGS) asm volatile("" : "+a"(qf[f2])); else asm volatile("" : "+v"(qf[f2])); }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+
+    f32x4 acc[4][2];                            // acc[a][b]: rows 16 a .. + 15 of the tile x query group b
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // lane (l15, g4) reads row 16 a + l15, 16-byte chunk 4 (s & 1) + g4 of slice (s >> 1) & 1 (see k_scan_f16_qs4)
+    unsigned fa0 = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) float *)(s_x + swz(l15, g4));
+    unsigned fa1 = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) float *)(s_x + swz(l15, 4 + g4));
+
+    const float *xbase = reinterpret_cast<const float *>(p.xh + (int64_t)t_begin * RT2 * p.dpad_h);
+    const int total = ntile * KT2;
+    const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) float *)s_x + (unsigned)wave * 2048u;
+    const unsigned voff0 = (unsigned)(((16 * wave + (lane >> 3)) * dpad + 4 * ((lane & 7) ^ ((lane >> 4) & 7))) * 4);
+    const unsigned voff1 = (unsigned)(((16 * wave + 8 + (lane >> 3)) * dpad + 4 * ((lane & 7) ^ ((4 + (lane >> 4)) & 7))) * 4);
+    // piece pc (0..3) of the stage kt2_ of the tile at tile_base into ring slot slot_: slice pc >> 1, row half pc & 1
+#define QW_PIECE(tile_base, kt2_, slot_, pc)                                                                               \
+    qs4_dma_piece((tile_base) + (2 * (kt2_) + ((pc) >> 1)) * BK, lds0 + (unsigned)(((slot_) * STG + ((pc) >> 1) * RT2 * BK) * 4) + 1024u * ((pc) & 1), \
+                  ((pc) & 1) ? voff1 : voff0)
+#pragma unroll
+    for (int s0 = 0; s0 < NB - 1; ++s0)
+        if (s0 < total) {
+#pragma unroll
+            for (int pc = 0; pc < 4; ++pc) QW_PIECE(xbase + (int64_t)(s0 / KT2) * RT2 * dpad, s0 % KT2, s0, pc);
+        }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (prologue only)
+    __syncthreads();
+
+    bf16x8 fA[2][4];                            // two fragment sets: database fragments a = 0..3
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) fA[u][a] = bf16x8{};
+    unsigned va0 = fa0, va1 = fa1;              // fragment addresses inside the ring slot being read (slot 0 first)
+    const bool filter_on = !(p.ablate & 1);
+    if (p.ablate & 4) th0 = th1 = INFINITY;     // (diagnostic, results invalid: nothing passes the filter, so nothing re-arms it)
+    const int lim4 = (p.b.stale + 3) >> 2;      // a lane's share of `stale` new candidates per query
+
+#define QW_LOADA(U, S, a_)                                                                                                 \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(fA[U][a_]) : "v"(((S) & 1) ? va1 : va0), "n"((((S) >> 1) & 1) * RT2 * 128 + 2048 * (a_)) : "memory")
+#define QW_WAIT(U) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fA[U][0]), "+v"(fA[U][1]), "+v"(fA[U][2]), "+v"(fA[U][3]))
+    // MFMA i of step S: query group b = i >> 2 against database fragment a = i & 3
+#define QW_MF(U, S, i_)                                                                                                    \
+    do {                                                                                                                   \
+        constexpr int b_ = (i_) >> 2, a_ = (i_) & 3, f_ = b_ * NS + (S);                                                   \
+        if (f_ < LEMON_QSW_ACC_FRAGS) mfma16<true, (S) == 0>(acc[a_][b_], fA[U][a_], qf[f_]);                              \
+        else                          mfma16<false, (S) == 0>(acc[a_][b_], fA[U][a_], qf[f_]);                             \
+    } while (0)
+
+    // ---- maintenance: light compaction of the queries whose lists need it (both groups; b, c wave-uniform): see k_scan_f16_qs4 ----
+    auto maintain = [&](u64 todo) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this tile's appends are visible
+        do {
+            const int r = __ffsll((long long)todo) - 1;     // = 16 b + c: the query's row inside the wave's 32
+            todo &= todo - 1;
+            const int b = r >> 4, c = r & 15;
+            const int row = 32 * wave + r;
+            u64 *list = cand_panel + (int64_t)row * CAPH;
+            const int cc = b == 0 ? ccnt0 : ccnt1;
+            const int n0 = __builtin_amdgcn_readlane(cc, c), n1 = __builtin_amdgcn_readlane(cc, c + 16);
+            const int n2 = __builtin_amdgcn_readlane(cc, c + 32), n3 = __builtin_amdgcn_readlane(cc, c + 48);
+            if (n0 + n1 + n2 + n3 < p.b.kk) continue;   // (a lane trigger before the query holds kk keys: nothing to select yet)
+            float lo;
+            int kept = qs4_compact_light(list, n0, n1, n2, n3, p.b.kk, s_eps[row], lane, &lo);
+            if (kept > CAPH - 64) {            // the band itself leaves no room for a tile's appends: settle it exactly
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                u64 kth;
+                kept = qs4_compact_exact(p, list, kept, q0 + row, s_qn[row], lane, s_keys + wave * 256, s_best + wave * 64, &kth);
+                if (kept == p.b.kk) lo = bound_from_tau(lemon_key_score(kth), s_eps[row]);
+            }
+            const int mine = (kept + 3 - g4) >> 2;        // round-robin deal: quarter g holds entries g, g + 4, ...
+            const bool me = l15 == c;
+            if (me && b == 0) { ccnt0 = mine; clast0 = mine; thk0 = lo; th0 = th_of(lo, qn0); }
+            if (me && b == 1) { ccnt1 = mine; clast1 = mine; thk1 = lo; th1 = th_of(lo, qn1); }
+        } while (todo);
+    };
+#define QW_ACC(b_) acc[0][b_], acc[1][b_], acc[2][b_], acc[3][b_]
+#define QW_TH(b_) ((b_) == 0 ? th0 : th1)
+#define QW_GMAX(b_, jt_) (__ballot(qs4_group_max<l2>(QW_ACC(b_), (jt_) + 4u * (unsigned)g4, p.b.xnorm) > QW_TH(b_)))
+    // (a lane whose query does not exist -- the panel's padding -- carries the bound +inf: it never appends, its counts stay 0)
+#define QW_NEED(cc_, cl_, tk_) ((cc_) - (cl_) >= lim4 || (cc_) > QCAP4 - 16 || ((tk_) == -INFINITY && (cc_) >= 16))
+#define QW_SLOW(b_, jt_)                                                                                                   \
+    do {                                                                                                                   \
+        unsigned jb_ = (jt_) + 4u * (unsigned)g4;                                                                          \
+        u64 nd_ = 0;                                                                                                       \
+        if ((b_) == 0) { qs4_filter_slow<l2>(QW_ACC(0), QW_TH(0), jb_, qn0, ccnt0, panel_bytes, my_off0); nd_ = __ballot(QW_NEED(ccnt0, clast0, thk0)); } \
+        if ((b_) == 1) { qs4_filter_slow<l2>(QW_ACC(1), QW_TH(1), jb_, qn1, ccnt1, panel_bytes, my_off0 + 16u * CAPH * 8u); nd_ = __ballot(QW_NEED(ccnt1, clast1, thk1)); } \
+        todo |= ((nd_ | (nd_ >> 16) | (nd_ >> 32) | (nd_ >> 48)) & 0xffffull) << (16 * (b_));                              \
+    } while (0)
+
+    // k32 step S (compile-time) of the tile on fragment set S & 1; the gaps behind its MFMAs carry the reads of step S + 1 (the
+    // next stage's slot once S + 1 opens a stage) and, in steps 2 and 3 of a stage, the DMA pieces of stage t + 3
+#define QW_SLOT(S, i_)                                                                                                     \
+    do {                                                                                                                   \
+        QW_MF((S) & 1, S, i_);                                                                                             \
+        if ((i_) < 4) QW_LOADA(((S) & 1) ^ 1, ((S) + 1) % NS, i_);                                                         \
+        if (((S) & 3) >= 2 && ((i_) == 5 || (i_) == 7)) {                                                                  \
+            constexpr int pc_ = 2 * (((S) & 3) - 2) + ((i_) == 7);                                                         \
+            qs4_dma_piece_off<(pc_ >> 1) * BK * 4>(ssrc_, pc_ == 0 ? sl0_ : pc_ == 1 ? sl1_ : pc_ == 2 ? sl2_ : sl3_, (pc_ & 1) ? voff1 : voff0); \
+        }                                                                                                                  \
+    } while (0)
+#define QW_STEP(S)                                                                                                         \
+    do {                                                                                                                   \
+        QW_WAIT((S) & 1);                                                                                                  \
+        if (((S) & 3) == 3) {   /* the next step opens a stage: its slot */                                                \
+            const unsigned sbn_ = (unsigned)(((t + 1) & (NB - 1)) * STG * 4);                                              \
+            va0 = fa0 + sbn_; va1 = fa1 + sbn_;                                                                            \
+        }                                                                                                                  \
+        QW_SLOT(S, 0); QW_SLOT(S, 1); QW_SLOT(S, 2); QW_SLOT(S, 3); QW_SLOT(S, 4); QW_SLOT(S, 5); QW_SLOT(S, 6); QW_SLOT(S, 7);    \
+        if (((S) & 3) == 1) {                                                                                              \
+            /* stage t + 1 has landed (this wave's pieces: at most the four of stage t + 2 may still be in flight; younger */ \
+            /* appends only make the wait longer), then the rendezvous: everybody's pieces, and everybody is done with stage t - 1 */ \
+            if (t + 2 < total) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                            \
+            else               asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                            \
+            __builtin_amdgcn_s_barrier();                                                                                  \
+        }                                                                                                                  \
+    } while (0)
+    // (stage t + 3's pieces are ALWAYS issued -- behind the end of the launch they re-fetch the launch's first stage into a ring
+    // slot nobody reads any more -- so that no branch stands between the MFMAs; pieces 2, 3 carry the k-slice's 128 source bytes
+    // in the instruction's offset field, which LDS-DMA adds to the LDS address as well: their M0 is 128 short)
+#define QW_STAGE(K)                                                                                                        \
+    do {                                                                                                                   \
+        const int t = jl * KT2 + (K);                                                                                      \
+        const float *ssrc_ = (t + 3 < total) ? xt + (int64_t)(((K) + 3) / KT2) * RT2 * dpad + 2 * (((K) + 3) % KT2) * BK : xbase; \
+        unsigned sl0_ = lds0 + (unsigned)(((t + 3) & (NB - 1)) * STG * 4);                                                 \
+        asm volatile("" : "+s"(ssrc_), "+s"(sl0_));                                                                        \
+        const unsigned sl1_ = sl0_ + 1024u, sl2_ = sl0_ + (unsigned)(RT2 * BK * 4 - BK * 4), sl3_ = sl0_ + (unsigned)(RT2 * BK * 4 - BK * 4) + 1024u; \
+        QW_STEP(4 * (K) + 0);                                                                                              \
+        QW_STEP(4 * (K) + 1);                                                                                              \
+        QW_STEP(4 * (K) + 2);                                                                                              \
+        QW_STEP(4 * (K) + 3);                                                                                              \
+    } while (0)
+
+    // the first step's fragments (slot 0)
+    if (ntile > 0) {
+        QW_LOADA(0, 0, 0); QW_LOADA(0, 0, 1); QW_LOADA(0, 0, 2); QW_LOADA(0, 0, 3);
+    }
+    for (int jl = 0; jl < ntile; ++jl) {
+        const float *xt = xbase + (int64_t)jl * RT2 * dpad;
+        QW_STAGE(0); QW_STAGE(1); QW_STAGE(2); QW_STAGE(3); QW_STAGE(4); QW_STAGE(5); QW_STAGE(6); QW_STAGE(7);
+        if constexpr (KT2 > 8) { QW_STAGE(8); QW_STAGE(9); }
+        // ---- the tile's filter, behind its last step.  The reads that step issued (the next tile's first fragments; behind the
+        // launch's last tile: a slot nobody needs) are retired first, so no asm load is in flight across the compiler's code ----
+        QW_WAIT(0);
+        if (filter_on) {
+            const unsigned jt = (unsigned)(t_begin + jl) * RT2;
+            if (jt + (unsigned)RT2 > (unsigned)p.b.n) {
+                // last tile of the database (uniform): its padding rows must never pass.  One more MFMA per accumulator tile: A' =
+                // -inf in k-slot 0 of the padding rows (0 elsewhere), B' = 1 in k-slot 0 -> padding rows' scores become -inf, valid rows' + 0
+                typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+                u16x8 ones = {}, mk0 = {}, mk1 = {}, mk2 = {}, mk3 = {};
+                ones[0] = g4 == 0 ? (unsigned short)0x3c00u : (unsigned short)0;
+                mk0[0] = (g4 == 0 && jt + (unsigned)l15 >= (unsigned)p.b.n) ? (unsigned short)0xfc00u : (unsigned short)0;
+                mk1[0] = (g4 == 0 && jt + 16u + (unsigned)l15 >= (unsigned)p.b.n) ? (unsigned short)0xfc00u : (unsigned short)0;
+                mk2[0] = (g4 == 0 && jt + 32u + (unsigned)l15 >= (unsigned)p.b.n) ? (unsigned short)0xfc00u : (unsigned short)0;
+                mk3[0] = (g4 == 0 && jt + 48u + (unsigned)l15 >= (unsigned)p.b.n) ? (unsigned short)0xfc00u : (unsigned short)0;
+                bf16x8 b1 = __builtin_bit_cast(bf16x8, ones), a0 = __builtin_bit_cast(bf16x8, mk0), a1 = __builtin_bit_cast(bf16x8, mk1);
+                bf16x8 a2 = __builtin_bit_cast(bf16x8, mk2), a3 = __builtin_bit_cast(bf16x8, mk3);
+                // (VALU -> asm MFMA: hipcc pads nothing in front of an asm statement; three instructions, six wait states)
+                asm volatile("s_nop 1\n\ts_nop 1\n\ts_nop 1" : "+v"(b1), "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    mfma16<false, false>(acc[0][b], a0, b1); mfma16<false, false>(acc[1][b], a1, b1);
+                    mfma16<false, false>(acc[2][b], a2, b1); mfma16<false, false>(acc[3][b], a3, b1);
+                }
+            }
+            // MFMA results are read by VALU next: wait out the matrix pipe (hipcc pads nothing around asm)
+            asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc[0][0]), "+v"(acc[1][0]), "+v"(acc[2][0]), "+v"(acc[3][0]));
+            asm volatile("" : "+v"(acc[0][1]), "+v"(acc[1][1]), "+v"(acc[2][1]), "+v"(acc[3][1]));
+            u64 todo = 0;
+            if (QW_GMAX(0, jt)) QW_SLOW(0, jt);
+            if (QW_GMAX(1, jt)) QW_SLOW(1, jt);
+            if (todo) maintain(todo);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the pieces issued behind the end of the launch, and the appends)
+#undef QW_STAGE
+#undef QW_STEP
+#undef QW_SLOT
+#undef QW_SLOW
+#undef QW_NEED
+#undef QW_GMAX
+#undef QW_TH
+#undef QW_ACC
+#undef QW_MF
+#undef QW_WAIT
+#undef QW_LOADA
+#undef QW_PIECE
+    if (!final_pass) {      // park the lane-private state for the next database chunk
+        float *st = p.state + 8 * ((int64_t)blockIdx.x * NT + tid);
+        st[0] = __int_as_float(ccnt0); st[1] = __int_as_float(clast0); st[2] = thk0;
+        st[4] = __int_as_float(ccnt1); st[5] = __int_as_float(clast1); st[6] = thk1;
+        return;
+    }
+    // ---- end of the scan: counts for k_bf16_final (exact re-scoring + exact top-k, one wave per query) ----
+    int *cn = p.cnt + 4 * ((int64_t)blockIdx.x * BQW + qrow0) + g4;
+    cn[0] = ccnt0; cn[4 * 16] = ccnt1;
+}
+
+// ======================================================================================
 // Final pass of the Q-stationary scans: exact fp32-chain re-scoring of every surviving candidate + exact top-k.
 //
 // Inside the scan kernel this ran with ONE wave per SIMD, one lane per candidate row, every lane walking its own 3 KB row
@@ -1974,14 +2272,11 @@ __global__ __launch_bounds__(256) void k_bf16_final(FinalParams p) {
 
 }  // namespace
 
-// column pitch of the bf16 copies: the Q-stationary kernel is instantiated for 256/512/768
-// (at 1024 the stationary operand alone would need all 256 accumulator registers next to the tile)
-static int bf16_pitch(int d) {
-    if (d <= 256) return 256;
-    if (d <= 512) return 512;
-    if (d <= 768) return 768;
-    return (int)round_up(d, BKH);
-}
+// column pitch of the 16-bit copies (knn_wide.hpp): the Q-stationary kernels are instantiated for 256 / 512 / 768 and, with the
+// index's wide filter switched on, for 1024 / 1280 (k_scan_f16_qsw: two query groups per wave, so that the stationary operand
+// fits the register file next to the tile); any other width is streamed at the next multiple of 64
+static int bf16_pitch(const lemon_index_t *idx) { return lemon_bf16_pitch(idx->d, idx->wide_filter != 0); }
+static_assert(BKH == 64, "lemon_bf16_pitch rounds to the streaming kernel's k-slice");
 
 static int convert_rows(const float *src, int64_t n, int d, lp16 *dst, int dpad_h, float *res2, float *hn2,
                         hipStream_t stream) {
@@ -1993,7 +2288,13 @@ static int convert_rows(const float *src, int64_t n, int d, lp16 *dst, int dpad_
 }
 
 static int ensure_bf16_copy(lemon_index_t *idx, hipStream_t stream) {
-    const int dpad_h = bf16_pitch(idx->d);
+    const int dpad_h = bf16_pitch(idx);
+    if (idx->xh && idx->dpad_h != dpad_h) {      // the wide-filter switch was toggled: the copy exists at the other pitch
+        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
+        (void)hipFree(idx->xh); idx->xh = nullptr;
+        if (idx->xh_stats) { (void)hipFree(idx->xh_stats); idx->xh_stats = nullptr; }
+        idx->xh_rows = 0;
+    }
     idx->dpad_h = dpad_h;
     if (!idx->xh) {
         LEMON_HIP_CHECK(hipStreamSynchronize(stream));
@@ -2063,6 +2364,13 @@ static void launch_qs4(int kt, unsigned grid, hipStream_t stream, const ScanPara
     else if (!l2) hipLaunchKernelGGL((k_scan_f16_qs4<12, 16, false>), dim3(grid), dim3(NT), 0, stream, p);
 }
 
+// QSW: pitches 1024 (kt = 16) and 1280 (kt = 20), both metrics
+template <bool l2>
+static void launch_qsw(int kt, unsigned grid, hipStream_t stream, const ScanParamsH &p) {
+    if (kt == 16) hipLaunchKernelGGL((k_scan_f16_qsw<16, l2>), dim3(grid), dim3(NT), 0, stream, p);
+    else          hipLaunchKernelGGL((k_scan_f16_qsw<20, l2>), dim3(grid), dim3(NT), 0, stream, p);
+}
+
 int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, float *D_dev,
                       int64_t *I_dev, hipStream_t stream) {
     const int d = idx->d;
@@ -2071,6 +2379,9 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
     if (rc) return rc;
     const int dpad_h = idx->dpad_h;
     const bool qs = dpad_h <= 768;
+    // pitches 1024 / 1280 exist only with the wide filter on (bf16_pitch): k_scan_f16_qsw from the panel threshold on
+    const bool wide = idx->wide_filter && idx->d > 768 && (dpad_h == 1024 || dpad_h == 1280);
+    const char *kernel_name = "scan_bf16";
     // QS2 halves the panel count.  When 256-query panels alone do not fill the chip the database would be split between more
     // workgroups, and every split pays its own cold start (k ln(n/k) appends per query): measured 13.0 -> 20.1 ms at
     // 50 000 x 40 000 x 512 and 17.3 -> 21.8 ms at 131 072^2 x 256 (k = 11), against 1 648 -> 1 501 ms at 1 M x 768,
@@ -2085,7 +2396,7 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
     }();
     const int n_tiles128 = (int)((idx->n + BX - 1) / BX);
     static const bool rest_qs4 = [] { const char *e = getenv("LEMON_QS4_REST"); return !(e && e[0] == '0'); }();   // (A/B aid)
-    bool prev_qs4 = false;
+    bool prev_qs4 = false, prev_qsw = false;
     int64_t cn = 0;
     for (int64_t c0 = 0; c0 < nq; c0 += cn) {
         cn = (nq - c0) < QCHUNK_H ? (nq - c0) : QCHUNK_H;
@@ -2104,6 +2415,22 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
             if (rest_splits) qs2 = qs4 = true;
         }
         prev_qs4 = qs4;
+        // the wide kernel: the same threshold in panels of its own 128 queries, the same whole-round cut and split rest
+        bool qsw = wide && cn >= (int64_t)qs2_min * BQW;
+        if (wide && !qsw && prev_qsw && c0 > 0 && rest_qs4) {
+            const int panels_r = (int)((cn + BQW - 1) / BQW);
+            for (int sp = 1; sp <= 16 && !rest_splits; ++sp) {
+                const int64_t wgs = (int64_t)panels_r * sp, rounds = (wgs + cus - 1) / cus;
+                if (wgs * 4 >= rounds * cus * 3 && n_tiles128 / sp >= 64) rest_splits = sp;
+            }
+            if (rest_splits) qsw = true;
+        }
+        prev_qsw = qsw;
+        if (qsw && cn < QCHUNK_H) {
+            const int64_t panels_c = (cn + BQW - 1) / BQW, full = panels_c / cus * cus;
+            if (full > 0 && panels_c != full && (panels_c - full) * 5 < (int64_t)cus * 4) cn = full * BQW;
+        }
+        const bool qsx = qs || qsw;                        // a Q-stationary kernel: lane lists, chunked launches, k_bf16_final
         if (qs2 && cn < QCHUNK_H) {
             // Whole rounds first.  The chunked scan runs ONE workgroup per CU, all of equal length: 1 859 workgroups take
             // eight rounds of 256 like 2 048 do (1 M queries = 2 048 + 1 859 panels: 4.6 % of the scan spent in a quarter-full
@@ -2114,7 +2441,7 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
             if (full > 0 && panels_c != full && (panels_c - full) * 5 < (int64_t)cus * 4) cn = full * BQ2;
         }
         const int bqw = qs2 ? BQ2 : BQ;                     // queries per workgroup
-        const int rt = qs2 ? RT2 : BX;                      // database rows per tile
+        const int rt = (qs2 || qsw) ? RT2 : BX;             // database rows per tile
         const int n_tiles = (int)((idx->n + rt - 1) / rt);
         const int64_t nq_pad = round_up(cn, bqw);
         const int panels = (int)(nq_pad / bqw);
@@ -2124,7 +2451,7 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
             tiles_per_split = (n_tiles128 + rest_splits - 1) / rest_splits;
             splits = (n_tiles128 + tiles_per_split - 1) / tiles_per_split;
         }
-        if (qs2) tiles_per_split *= BX / RT2;            // (the plan counts 128-row tiles)
+        if (qs2 || qsw) tiles_per_split *= BX / RT2;     // (the plan counts 128-row tiles)
         rc = lemon_ensure_search_ws(idx, nq_pad, splits, (int64_t)panels * splits * (bqw / BQ), dpad_h * 2, CAPH, stream);
         if (rc) return rc;
         // bf16 query panel (pad rows zero), chain norms, measured rounding residuals
@@ -2153,7 +2480,7 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
         const unsigned grid = (unsigned)(panels * splits);
         // database chunks sized for the Infinity Cache (the chunk is re-read by every query panel)
         int chunk_tiles = n_tiles;
-        if (qs && splits == 1) {
+        if (qsx && splits == 1) {
             const char *env = getenv("LEMON_CHUNK_MB");
             const double mb = env ? atof(env) : 64.0;
             if (mb > 0) {
@@ -2163,8 +2490,8 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
             if (chunk_tiles > n_tiles) chunk_tiles = n_tiles;
         }
         // per-lane state carried between chunk launches (splits == 1) + the half-list counts handed to k_bf16_final
-        const int64_t state_elems = (qs && splits == 1) ? (int64_t)grid * NT * (qs4 ? 16 : qs2 ? 8 : 4) : 0;
-        const int64_t cnt_elems = qs ? (int64_t)grid * bqw * (qs4 ? 4 : 2) : 0;
+        const int64_t state_elems = (qsx && splits == 1) ? (int64_t)grid * NT * (qs4 ? 16 : (qs2 || qsw) ? 8 : 4) : 0;
+        const int64_t cnt_elems = qsx ? (int64_t)grid * bqw * ((qs4 || qsw) ? 4 : 2) : 0;
         if (state_elems + cnt_elems > idx->ws_state_elems) {
             LEMON_HIP_CHECK(hipStreamSynchronize(stream));
             if (idx->ws_state) (void)hipFree(idx->ws_state);
@@ -2179,7 +2506,7 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
         p.cnt = reinterpret_cast<int *>(idx->ws_state + state_elems);
         const bool l2m_ = idx->metric == LEMON_METRIC_L2;
         FinalParams fp;
-        fp.b = p.b; fp.q = p.q; fp.x = p.x; fp.cnt = p.cnt; fp.d = d; fp.rows_per_wg = bqw; fp.segs = qs4 ? 4 : 2; fp.n_lists = (int64_t)grid * bqw;
+        fp.b = p.b; fp.q = p.q; fp.x = p.x; fp.cnt = p.cnt; fp.d = d; fp.rows_per_wg = bqw; fp.segs = (qs4 || qsw) ? 4 : 2; fp.n_lists = (int64_t)grid * bqw;
         fp.qres2 = qres2; fp.xstat = idx->xn2max_dev;
         static const int prefilter = [] { const char *e = getenv("LEMON_FINAL_PREFILTER"); return !(e && e[0] == '0'); }();   // (A/B aid)
         fp.prefilter = prefilter;
@@ -2200,6 +2527,12 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
             const double flops = 2.0 * (double)cn * rows * (double)d;
             const double bytes = 2.0 * d * ((double)nq_pad / BQ * rows) + (p.last_chunk ? 2.0 * d * cn + 12.0 * k * (double)cn : 0.0);
             LemonProfScope prof(idx, stream, flops, bytes);
+            if (qsw) {
+                if (l2m) launch_qsw<true>(dpad_h / BKH, grid, stream, p);
+                else     launch_qsw<false>(dpad_h / BKH, grid, stream, p);
+                if (p.last_chunk) launch_final();
+                continue;
+            }
             if (qs4) {
 #ifdef LEMON_QS4_PHASES
                 static unsigned long long *dbg4 = nullptr;
@@ -2266,10 +2599,12 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
         }
         idx->last.algo = LEMON_ALGO_BF16_FILTER;
         if (c0 == 0) {                                  // (the first chunk is the largest: its geometry is what gets reported)
+            kernel_name = qsw ? "qsw" : qs4 ? "qs4" : qs2 ? "qs2" : qs ? "qs" : "scan_bf16";
             idx->last.grid = (int)grid; idx->last.block = NT;
             idx->last.query_panel = bqw; idx->last.db_splits = splits;
         }
     }
     idx->last.nq = nq; idx->last.n = idx->n; idx->last.d = d; idx->last.k = k;
+    idx->last_kernel = kernel_name;
     return LEMON_OK;
 }

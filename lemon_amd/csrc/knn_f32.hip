@@ -844,6 +844,7 @@ static int lemon_search_f32_pass(lemon_index_t *idx, const float *q_dev, int64_t
             if (rc) return rc;
         }
         idx->last.algo = LEMON_ALGO_F32_MFMA;
+        idx->last_kernel = "scan_f32";
         idx->last.grid = (int)grid; idx->last.block = NT;
         idx->last.query_panel = BQ; idx->last.db_splits = splits;
     }

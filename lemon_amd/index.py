@@ -53,6 +53,14 @@ class _IndexFlat:
         """Fold identical query rows into one search each (exact; on by default -- see include/lemon_hip.h)."""
         _lib.check(self._lib.lemon_index_set_query_dedup(self._h, int(bool(enabled))), "lemon_index_set_query_dedup")
 
+    def set_wide_filter(self, enabled=True):
+        """Serve 768 < d <= 1280 with the register-resident fp16 filter kernel (off by default -- see include/lemon_hip.h)."""
+        _lib.check(self._lib.lemon_index_set_wide_filter(self._h, int(bool(enabled))), "lemon_index_set_wide_filter")
+
+    def last_scan_kernel(self):
+        """Family name of the scan kernel that served the last search ("scan_f32", "scan_bf16", "qs", "qs2", "qs4", "qsw"; "" before any)."""
+        return self._lib.lemon_index_last_scan_kernel(self._h).decode("ascii")
+
     def last_search_info(self):
         info = _lib.SearchInfo()
         _lib.check(self._lib.lemon_index_last_search_info(self._h, ctypes.byref(info)), "last_search_info")
