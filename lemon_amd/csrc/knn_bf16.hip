@@ -20,9 +20,12 @@
 // output is bit-identical to LEMON_ALGO_F32_MFMA and the CPU oracle.
 #include "knn_common.hpp"
 #include "knn_wide.hpp"
+#include "knn_bf16_plan.hpp"
 #include <stdlib.h>
 
 using namespace lemon_knn;
+namespace plan = lemon_bf16_plan;
+static_assert(plan::BQ == BQ && plan::BX == BX && plan::NT == NT, "knn_bf16_plan.hpp mirrors the scan geometry of knn_common.hpp");
 
 // The 16-bit filter format is IEEE fp16 (11 significant bits; the first two rounds used bf16, whose 8 bits made the band 5x
 // wider -- the names of the algorithm and of the kernels still say bf16).  Unit-norm embeddings sit far inside its range; the
@@ -33,7 +36,7 @@ typedef lp16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-constexpr int BKH = 64;   // bf16 k-slice per LDS stage (128 B rows, like fp32 BK=32)
+using plan::BKH;          // bf16 k-slice per LDS stage (128 B rows, like fp32 BK=32)
 constexpr int CAPH = 512; // candidate slots per query (approximate keys): 8 per lane in a light compaction
 static_assert(CAPH == PAIR_CAP, "append_slot() clamps to the pair-list half capacity");
 constexpr int REFRESH = 96; // light-compact a list after this many new candidates: the admission bound then
@@ -98,13 +101,10 @@ struct ScanParamsH {
     int *cnt;                  // [grid * queries per workgroup][2]: half-list counts at the end of the scan, for k_bf16_final
     float *state;              // [grid*256 lanes][4]: {half-list count, last compacted length, thr_key, -}
     int ablate;                // diagnostics only (LEMON_ABLATE): 1 = skip the filter epilogue AND maintenance (nothing is
-                               // appended), 4 = nothing passes the filter, 8 (phase-stamped build) = the tile-end wait for
-                               // the DMA is booked under "maintain", so that "sync" is the barrier alone (measured: 2.6 %
-                               // and 8.7 % of wave 0's cycles).  There is deliberately NO "appends without maintenance"
+                               // appended), 4 = nothing passes the filter.  There is deliberately NO "appends without maintenance"
                                // mode: maintenance is what keeps the 256-entry half-lists in bounds (a working-tree
                                // diagnostic of round 2 had one as value 2 and faulted the GPU; lemon_parse_ablate now
                                // refuses unknown bits and append_slot() clamps the store)
-    unsigned long long *phase_dbg;   // diagnostic builds only: [grid][4] cycle sums (loop, epilogue, sync, maintain)
 };
 
 // proven bound on |s~ - s| for one query (see file header); for L2 the bound on the key -D
@@ -612,10 +612,8 @@ __device__ __forceinline__ void mfma_qs(f32x16 &acc, bf16x8 a, const bf16x8 &bq)
 
 // (the metric is a template parameter: the L2 epilogue issues ordinary global loads (|x|^2), and hipcc
 // drains the whole LDS-DMA queue before any use of an ordinary load while DMAs are in flight)
-template <int KT, bool l2, bool PROF>
+template <int KT, bool l2>
 __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs(ScanParamsH p) {
-    unsigned long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0, ts = 0;
-#define PH_STAMP(acc) do { if (PROF) { unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - ts; ts = now_; } } while (0)
     constexpr int KS = 4 * KT;                 // 16-wide k steps
     constexpr int SUB = 2;                     // 64-wide k-slices per stage: 32 MFMAs per wave between barriers
     constexpr int KT2 = KT / SUB;              // stages per database tile
@@ -702,7 +700,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs(ScanParamsH p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (prologue only)
     __syncthreads();
 
-    if (PROF) ts = __builtin_amdgcn_s_memtime();
     for (int jl = 0; jl < ntile; ++jl) {
         const float *xt = xbase + (int64_t)jl * BX * dpad;
 #pragma clang loop unroll(full)
@@ -757,7 +754,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs(ScanParamsH p) {
 #undef QS_LOAD
             }
             if (kt == KT2 - 1 && !(p.ablate & 1)) {
-                PH_STAMP(ph0);
                 // MFMA results are read by VALU next: hipcc pads nothing around asm, so wait out the
                 // 16-pass MFMA latency here (once per tile)
                 asm volatile("s_nop 15\n\ts_nop 15" : "+a"(acc0), "+a"(acc1), "+a"(acc2), "+a"(acc3));
@@ -781,7 +777,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs(ScanParamsH p) {
                 qs_filter_tile<l2>(acc1, th_f, jb + 32, my_qn, p.b.xnorm, (unsigned)p.b.n, ccnt, panel_bytes, my_off);
                 qs_filter_tile<l2>(acc2, th_f, jb + 64, my_qn, p.b.xnorm, (unsigned)p.b.n, ccnt, panel_bytes, my_off);
                 qs_filter_tile<l2>(acc3, th_f, jb + 96, my_qn, p.b.xnorm, (unsigned)p.b.n, ccnt, panel_bytes, my_off);
-                PH_STAMP(ph1);
 
                 // ---- maintenance: which queries need a (light) compaction? ----
                 const int pair = ccnt + __shfl_xor(ccnt, 32);
@@ -815,7 +810,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs(ScanParamsH p) {
                             th = th_of(lo);
                         }
                     } while (todo);
-                    PH_STAMP(ph3);
                 }
             }
             // stage t+1 must have landed (all waves' parts) before anyone reads it: at most the LA-1
@@ -823,17 +817,10 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs(ScanParamsH p) {
             if (more) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // (LA-1) stages x 2 slices x 4 DMAs
             else      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): this wave's LDS reads retired
-            if (PROF && (p.ablate & 8) && kt == KT2 - 1) PH_STAMP(ph3);   // diagnostic: the wait for the DMA counts as "maintain"
             __builtin_amdgcn_s_barrier();
-            if (kt == KT2 - 1) PH_STAMP(ph2);
         }
     }
 
-    if (PROF && tid == 0) {
-        atomicAdd(&p.phase_dbg[0], ph0); atomicAdd(&p.phase_dbg[1], ph1);
-        atomicAdd(&p.phase_dbg[2], ph2); atomicAdd(&p.phase_dbg[3], ph3);
-    }
-#undef PH_STAMP
 #undef QS_ISSUE_STAGE
     if (!final_pass) {      // park the lane-private state for the next database chunk
         float *st = p.state + 4 * ((int64_t)blockIdx.x * NT + tid);
@@ -861,25 +848,21 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs(ScanParamsH p) {
 // Candidate bookkeeping is the QS kernel's, per block: thresholds / counts in VGPRs, lane-private half-lists.
 // Tiles, splits and chunks are counted in 64-ROW units here (p.b.n_tiles, tiles_per_split, chunk_t0/t1).
 // ======================================================================================
-constexpr int RT2 = 64;        // database rows per tile
-constexpr int BQ2 = 256;       // queries per workgroup (64 per wave)
+using plan::RT2;               // database rows per tile (64)
+using plan::BQ2;               // queries per workgroup (256: 64 per wave)
 
-// one MFMA with the accumulator tile in the AccVGPR (CV = false) or the architectural (CV = true) half of the register file
-// and the stationary B operand in AccVGPRs (BA) or VGPRs; INIT: C = 0
-template <bool CV, bool BA, bool INIT>
+// one MFMA with the accumulator tile in the architectural half of the register file and the stationary B operand in
+// AccVGPRs (BA) or VGPRs; INIT: C = 0
+template <bool BA, bool INIT>
 __device__ __forceinline__ void mfma_x(f32x16 &acc, bf16x8 a, const bf16x8 &bq) {
     if (INIT) {
         // (early-clobber: a multi-pass MFMA may write its destination before it has read all of A / B, so the fresh tile
         // must not share registers with the fragments -- hipcc would otherwise reuse a dying fragment's VGPRs for it)
-        if (CV) { if (BA) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(bq));
-                  else    asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(bq)); }
-        else    { if (BA) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&a"(acc) : "v"(a), "a"(bq));
-                  else    asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&a"(acc) : "v"(a), "v"(bq)); }
+        if (BA) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(bq));
+        else    asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(bq));
     } else {
-        if (CV) { if (BA) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(bq));
-                  else    asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(bq)); }
-        else    { if (BA) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "a"(bq));
-                  else    asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(bq)); }
+        if (BA) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(bq));
+        else    asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(bq));
     }
 }
 
@@ -892,15 +875,13 @@ __device__ __forceinline__ void qs2_dma_slice(const float *__restrict__ src, uns
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff1), "s"(src), "s"(lds_bytes + 1024u) : "memory");
 }
 
-// ACCV: the four accumulator tiles live in ARCHITECTURAL VGPRs (the epilogue then reads them with VALU instructions directly:
+// The four accumulator tiles live in ARCHITECTURAL VGPRs (the epilogue then reads them with VALU instructions directly:
 // no 64 v_accvgpr_read per tile) and the first NA k-steps of query block 1 take the 64 AccVGPRs they leave free
-template <int KT, int PARK, bool l2, bool PROF, bool ACCV>
+template <int KT, int PARK, bool l2>
 __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs2(ScanParamsH p) {
-    unsigned long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0, ts = 0;
-#define PH_STAMP(acc) do { if (PROF) { unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - ts; ts = now_; } } while (0)
     constexpr int KS = 4 * KT;                 // 16-wide k steps
     constexpr int NR = KS - PARK;              // block-1 fragments kept in registers
-    constexpr int NA = ACCV ? (NR < 16 ? NR : 16) : 0;   // ... of which in AccVGPRs
+    constexpr int NA = NR < 16 ? NR : 16;      // ... of which in AccVGPRs
     constexpr int SUB = 2, KT2 = KT / SUB, NB = 4, LA = NB - 1;
     constexpr int STG = SUB * RT2 * BK;        // floats per stage (16 KB)
     constexpr int PK = PARK ? PARK : 1;
@@ -1002,7 +983,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs2(ScanParamsH p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (prologue only)
     __syncthreads();
 
-    if (PROF) ts = __builtin_amdgcn_s_memtime();
     for (int jl = 0; jl < ntile; ++jl) {
         const float *xt = xbase + (int64_t)jl * RT2 * dpad;
 #pragma clang loop unroll(full)
@@ -1039,13 +1019,13 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs2(ScanParamsH p) {
                 do {                                                                                                     \
                     const int ks_ = ks0 + (KSV);                     /* compile-time after unrolling */                  \
                     if (ks_ == 0) {                                                                                      \
-                        mfma_x<ACCV, true, true>(acc00, f##S##0, qa[0]); mfma_x<ACCV, true, true>(acc01, f##S##1, qa[0]); \
-                        mfma_x<ACCV, (NA > 0), true>(acc10, f##S##0, qb[0]); mfma_x<ACCV, (NA > 0), true>(acc11, f##S##1, qb[0]); \
+                        mfma_x<true, true>(acc00, f##S##0, qa[0]); mfma_x<true, true>(acc01, f##S##1, qa[0]); \
+                        mfma_x<true, true>(acc10, f##S##0, qb[0]); mfma_x<true, true>(acc11, f##S##1, qb[0]); \
                     } else {                                                                                             \
-                        mfma_x<ACCV, true, false>(acc00, f##S##0, qa[ks_]); mfma_x<ACCV, true, false>(acc01, f##S##1, qa[ks_]); \
-                        if (ks_ < NA)      { mfma_x<ACCV, true, false>(acc10, f##S##0, qb[ks_ < NR ? ks_ : 0]); mfma_x<ACCV, true, false>(acc11, f##S##1, qb[ks_ < NR ? ks_ : 0]); } \
-                        else if (ks_ < NR) { mfma_x<ACCV, false, false>(acc10, f##S##0, qb[ks_ < NR ? ks_ : 0]); mfma_x<ACCV, false, false>(acc11, f##S##1, qb[ks_ < NR ? ks_ : 0]); } \
-                        else               { mfma_x<ACCV, false, false>(acc10, f##S##0, p##S); mfma_x<ACCV, false, false>(acc11, f##S##1, p##S); } \
+                        mfma_x<true, false>(acc00, f##S##0, qa[ks_]); mfma_x<true, false>(acc01, f##S##1, qa[ks_]); \
+                        if (ks_ < NA)      { mfma_x<true, false>(acc10, f##S##0, qb[ks_ < NR ? ks_ : 0]); mfma_x<true, false>(acc11, f##S##1, qb[ks_ < NR ? ks_ : 0]); } \
+                        else if (ks_ < NR) { mfma_x<false, false>(acc10, f##S##0, qb[ks_ < NR ? ks_ : 0]); mfma_x<false, false>(acc11, f##S##1, qb[ks_ < NR ? ks_ : 0]); } \
+                        else               { mfma_x<false, false>(acc10, f##S##0, p##S); mfma_x<false, false>(acc11, f##S##1, p##S); } \
                     }                                                                                                    \
                 } while (0)
                 // (fragment reads TWO k-steps ahead over three sets were measured too: 1 404.5 vs 1 400.6 ms at 1 M x 768 -- nothing)
@@ -1065,7 +1045,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs2(ScanParamsH p) {
 #undef Q2_LOADS
             }
             if (kt == KT2 - 1 && !(p.ablate & 1)) {
-                PH_STAMP(ph0);
                 if ((unsigned)(t_begin + jl + 1) * RT2 > (unsigned)p.b.n) {
                     // last tile of the database (uniform): its padding rows must never pass.  One more MFMA per accumulator
                     // tile does it: A' = -inf in k-slot 0 of the padding rows (0 elsewhere), B' = 1 in k-slot 0 (0
@@ -1079,11 +1058,10 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs2(ScanParamsH p) {
                     m1[0] = (h == 0 && row + 32 >= (unsigned)p.b.n) ? ninf : (unsigned short)0;
                     ones[0] = h == 0 ? one : (unsigned short)0;
                     const bf16x8 a0 = __builtin_bit_cast(bf16x8, m0), a1 = __builtin_bit_cast(bf16x8, m1), b1 = __builtin_bit_cast(bf16x8, ones);
-                    mfma_x<ACCV, false, false>(acc00, a0, b1); mfma_x<ACCV, false, false>(acc01, a1, b1);
-                    mfma_x<ACCV, false, false>(acc10, a0, b1); mfma_x<ACCV, false, false>(acc11, a1, b1);
+                    mfma_x<false, false>(acc00, a0, b1); mfma_x<false, false>(acc01, a1, b1);
+                    mfma_x<false, false>(acc10, a0, b1); mfma_x<false, false>(acc11, a1, b1);
                 }
-                if (ACCV) asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc00), "+v"(acc01), "+v"(acc10), "+v"(acc11));
-                else      asm volatile("s_nop 15\n\ts_nop 15" : "+a"(acc00), "+a"(acc01), "+a"(acc10), "+a"(acc11));
+                asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc00), "+v"(acc01), "+v"(acc10), "+v"(acc11));
                 // ---- epilogue: acc<b><i>[e] = s~(db row 32 i + (e&3) + 8(e>>2) + 4h of the tile, query block b's lane&31) ----
                 const unsigned jb = (unsigned)(t_begin + jl) * RT2 + 4 * h;
                 const float tf0 = (p.ablate & 4) ? INFINITY : th0, tf1 = (p.ablate & 4) ? INFINITY : th1;
@@ -1095,7 +1073,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs2(ScanParamsH p) {
                 qs_filter_tile<l2>(acc10, tf1, jb, my_qn1, p.b.xnorm, (unsigned)p.b.n, ccnt1, panel_bytes, my_off1);
                 if (l2) __builtin_amdgcn_sched_barrier(0);
                 qs_filter_tile<l2>(acc11, tf1, jb + 32, my_qn1, p.b.xnorm, (unsigned)p.b.n, ccnt1, panel_bytes, my_off1);
-                PH_STAMP(ph1);
 
                 // ---- maintenance, per query block: which queries need a (light) compaction? ----
                 bool waited = false;
@@ -1137,24 +1114,16 @@ __global__ __launch_bounds__(NT, 1) void k_scan_bf16_qs2(ScanParamsH p) {
                         }
                     } while (todo);
                 }
-                if (waited) PH_STAMP(ph3);
             }
             // stage t+1 must have landed (all waves' parts) before anyone reads it: at most the LA-1 youngest stages
             // (4 DMA instructions each; younger appends only make the wait longer, never shorter) may still be in flight
             if (more) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): this wave's LDS reads retired
-            if (PROF && (p.ablate & 8) && kt == KT2 - 1) PH_STAMP(ph3);
             __builtin_amdgcn_s_barrier();
-            if (kt == KT2 - 1) PH_STAMP(ph2);
         }
     }
 
-    if (PROF && tid == 0) {
-        atomicAdd(&p.phase_dbg[0], ph0); atomicAdd(&p.phase_dbg[1], ph1);
-        atomicAdd(&p.phase_dbg[2], ph2); atomicAdd(&p.phase_dbg[3], ph3);
-    }
-#undef PH_STAMP
 #undef Q2_ISSUE_STAGE
     if (!final_pass) {      // park the lane-private state for the next database chunk
         float *st = p.state + 8 * ((int64_t)blockIdx.x * NT + tid);
@@ -1364,11 +1333,7 @@ template <int KT, int PARK, bool l2>
 __global__ __launch_bounds__(NT, 1) void k_scan_f16_qs4(ScanParamsH p) {
     // issue slots (MFMA index of a step behind which something else is issued): the five fragment reads of the next step behind
     // MFMAs RD0, RD0 + RDS, ...; the two DMA pieces of a step behind MFMAs DM0 and DM1
-#ifndef LEMON_QS4_SLOTS
     constexpr int RD0 = 0, RDS = 1, DM0 = 8, DM1 = 12;
-#else
-    constexpr int RD0 = (LEMON_QS4_SLOTS) / 1000 % 10, RDS = (LEMON_QS4_SLOTS) / 100 % 10, DM0 = (LEMON_QS4_SLOTS) / 10 % 10 + 6, DM1 = (LEMON_QS4_SLOTS) % 10 + 6;
-#endif
     constexpr int NS = 2 * KT;                 // k32 steps per tile
     constexpr int KT2 = KT / 2;                // stages per tile: 2 x 64-wide k-slices = 4 k32 steps each
     constexpr int NFR = 4 * NS - PARK;         // query fragments in registers: index f = b NS + s
@@ -1633,11 +1598,9 @@ __global__ __launch_bounds__(NT, 1) void k_scan_f16_qs4(ScanParamsH p) {
         if (((S) & 3) == 1) {                                                                                              \
             /* stage t + 1 has landed (this wave's pieces: at most the four of stage t + 2 may still be in flight; younger */ \
             /* appends only make the wait longer), then the rendezvous: everybody's pieces, and everybody is done with stage t - 1 */ \
-            Q4_PH_BEGIN();                                                                                                 \
             if (t + 2 < total) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                            \
             else               asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                            \
             __builtin_amdgcn_s_barrier();                                                                                  \
-            Q4_PH_END(3);                                                                                                  \
         }                                                                                                                  \
     } while (0)
 
@@ -1646,17 +1609,6 @@ __global__ __launch_bounds__(NT, 1) void k_scan_f16_qs4(ScanParamsH p) {
         Q4_LOADA(0, 0, 0); Q4_LOADA(0, 0, 1); Q4_LOADA(0, 0, 2); Q4_LOADA(0, 0, 3);
     }
     // (stages written out with literal indices: fragment homes and offsets are template / immediate operands)
-#ifdef LEMON_QS4_PHASES
-    // diagnostic build (tools/r5_build_phases.sh; results unchanged, timing +~10 %): shader-cycle sums per wave 0 of every workgroup --
-    // [0] whole loop, [1] step 0 of every tile (the 16 init MFMAs + the previous tile's filter), [2] maintain(), [3] the wait +
-    // barrier of every stage, [4] tiles, [5] tiles whose filter took a slow path, [6] tiles with a compaction
-    unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt_ = 0, pl_ = __builtin_amdgcn_s_memtime();
-#define Q4_PH_BEGIN() do { pt_ = __builtin_amdgcn_s_memtime(); } while (0)
-#define Q4_PH_END(i_) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); ph_[i_] += n_ - pt_; pt_ = n_; } while (0)
-#else
-#define Q4_PH_BEGIN() do { } while (0)
-#define Q4_PH_END(i_) do { } while (0)
-#endif
 #define Q4_STAGE(K)                                                                                                        \
     do {                                                                                                                   \
         const int t = jl * KT2 + (K);                                                                                      \
@@ -1669,10 +1621,8 @@ __global__ __launch_bounds__(NT, 1) void k_scan_f16_qs4(ScanParamsH p) {
         /* (pieces 2, 3 carry the k-slice's 128 source bytes in the instruction's offset field, and LDS-DMA adds that field to   \
            the LDS address as well: their M0 is 128 short) */                                                                  \
         const unsigned sl1_ = sl0_ + 1024u, sl2_ = sl0_ + (unsigned)(RT2 * BK * 4 - BK * 4), sl3_ = sl0_ + (unsigned)(RT2 * BK * 4 - BK * 4) + 1024u; \
-        if ((K) == 0) Q4_PH_BEGIN();                                                                                       \
         Q4_STEP(4 * (K) + 0);                                                                                              \
-        if ((K) == 0) Q4_PH_END(1);                                                                                        \
-        if ((K) == 0 && todo) { maintain(todo); Q4_PH_END(2); }                                                            \
+        if ((K) == 0 && todo) maintain(todo);                                                                              \
         Q4_STEP(4 * (K) + 1);                                                                                              \
         Q4_STEP(4 * (K) + 2);                                                                                              \
         Q4_STEP(4 * (K) + 3);                                                                                              \
@@ -1686,20 +1636,11 @@ __global__ __launch_bounds__(NT, 1) void k_scan_f16_qs4(ScanParamsH p) {
         u64 todo = 0;
         Q4_STAGE(0); Q4_STAGE(1); Q4_STAGE(2); Q4_STAGE(3);
         if constexpr (KT2 > 4) { Q4_STAGE(4); Q4_STAGE(5); }
-#ifdef LEMON_QS4_PHASES
-        ph_[4] += 1; ph_[5] += (pm0 | pm1 | pm2 | pm3) != 0; ph_[6] += todo != 0;
-#endif
         static_assert(KT2 == 4 || KT2 == 6, "stages per tile written out for d = 512 and d = 768");
     }
 #undef Q4_STAGE
-#undef Q4_PH_BEGIN
-#undef Q4_PH_END
     Q4_WAIT(0);                                 // (the reads the last step issued for a tile that does not exist: retired, unused)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (and the pieces issued behind the end of the launch)
-#ifdef LEMON_QS4_PHASES
-    ph_[0] = __builtin_amdgcn_s_memtime() - pl_;
-    if (p.phase_dbg && tid == 0) { for (int i_ = 0; i_ < 7; ++i_) atomicAdd(&p.phase_dbg[i_], ph_[i_]); }
-#endif
 #undef Q4_STEP
 #undef Q4_SLOT
 #undef Q4_TREES
@@ -1787,8 +1728,7 @@ __global__ __launch_bounds__(NT, 1) void k_scan_f16_qs4(ScanParamsH p) {
 // the -inf MFMA for the padding rows of the database's last tile, state in p.state between chunk launches.
 // Tiles, splits and chunks are counted in 64-ROW units, as in QS2 / QS4.
 // ======================================================================================
-constexpr int BQW = 128;       // queries per workgroup (32 per wave)
-static_assert(BQW == BQ, "the host side sizes the wide kernel's panels like the streaming kernel's");
+using plan::BQW;               // queries per workgroup (128: 32 per wave)
 
 template <int KT, bool l2>
 __global__ __launch_bounds__(NT, 1) void k_scan_f16_qsw(ScanParamsH p) {
@@ -2324,51 +2264,96 @@ static int ensure_bf16_copy(lemon_index_t *idx, hipStream_t stream) {
     return LEMON_OK;
 }
 
-static const int64_t QCHUNK_H = 1 << 19;
-
-// QS2 (two query blocks per wave, 256 queries per workgroup, 64-row tiles) serves the register-resident pitches;
-// LEMON_QS2=0 selects the one-block kernel (A/B aid)
-static bool use_qs2() {
-    const char *e = getenv("LEMON_QS2");
-    return !(e && e[0] == '0');
+// the plan's runtime knobs, read once per call (the tests set LEMON_QS2_MIN_PANELS and LEMON_CHUNK_MB with monkeypatch)
+static bool env_not_off(const char *name) { const char *e = getenv(name); return !(e && e[0] == '0'); }
+static plan::Knobs read_knobs() {
+    plan::Knobs kn;
+    kn.qs2 = env_not_off("LEMON_QS2");
+    kn.qs4 = env_not_off("LEMON_QS4");
+    kn.rest_split = env_not_off("LEMON_QS4_REST");
+    if (const char *e = getenv("LEMON_QS2_MIN_PANELS")) kn.qs2_min_panels = atoi(e);
+    if (const char *e = getenv("LEMON_CHUNK_MB")) kn.chunk_mb = atof(e);
+    if (const char *e = getenv("LEMON_SPLITS")) kn.forced_splits = atoi(e);
+    return kn;
 }
 
-template <bool l2, bool PROF>
-static void launch_qs2(int kt, unsigned grid, hipStream_t stream, const ScanParamsH &p) {
-    static const bool accv = [] { const char *e = getenv("LEMON_QS2_ACCV"); return !(e && e[0] == '0'); }();   // A/B aid
-    switch (kt) {
-        case 8:
-            if (accv) hipLaunchKernelGGL((k_scan_bf16_qs2<8, 0, l2, PROF, true>), dim3(grid), dim3(NT), 0, stream, p);
-            else      hipLaunchKernelGGL((k_scan_bf16_qs2<8, 0, l2, PROF, false>), dim3(grid), dim3(NT), 0, stream, p);
+// tuning knobs outside the plan, read once per process: new candidates per query that trigger a light compaction, and
+// the prefilter of k_bf16_final (A/B aid)
+static int scan_refresh() {
+    static const int refresh = [] { const char *e = getenv("LEMON_REFRESH"); return e && atoi(e) > 0 ? atoi(e) : REFRESH; }();
+    return refresh;
+}
+static int final_prefilter_on() {
+    static const int on = env_not_off("LEMON_FINAL_PREFILTER");
+    return on;
+}
+
+static int device_cus() {
+    static const int cus = [] {
+        int dev = 0, c = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+        return c > 0 ? c : 256;
+    }();
+    return cus;
+}
+
+// the instantiation that serves (kernel, kt = pitch / 64, metric), nullptr where there is none
+typedef void (*scan_kernel_t)(ScanParamsH);
+static scan_kernel_t scan_kernel(plan::Kernel kernel, int kt, bool l2) {
+    switch (kernel) {
+        case plan::SCAN_BF16: return k_scan_bf16;
+        case plan::QS:
+            if (kt == 4) return l2 ? k_scan_bf16_qs<4, true> : k_scan_bf16_qs<4, false>;
+            if (kt == 8) return l2 ? k_scan_bf16_qs<8, true> : k_scan_bf16_qs<8, false>;
+            if (kt == 12) return l2 ? k_scan_bf16_qs<12, true> : k_scan_bf16_qs<12, false>;
             break;
-        default:    // (the L2 epilogue's |x|^2 loads need a few more registers: four more parked k-steps)
-            if (accv) hipLaunchKernelGGL((k_scan_bf16_qs2<12, l2 ? 20 : 16, l2, PROF, true>), dim3(grid), dim3(NT), 0, stream, p);
-            else      hipLaunchKernelGGL((k_scan_bf16_qs2<12, l2 ? 20 : 16, l2, PROF, false>), dim3(grid), dim3(NT), 0, stream, p);
+        case plan::QS2:     // (the L2 epilogue's |x|^2 loads need a few more registers: four more parked k-steps)
+            if (kt == 8) return l2 ? k_scan_bf16_qs2<8, 0, true> : k_scan_bf16_qs2<8, 0, false>;
+            if (kt == 12) return l2 ? k_scan_bf16_qs2<12, 20, true> : k_scan_bf16_qs2<12, 16, false>;
             break;
+        case plan::QS4:
+            if (kt == 8) return l2 ? k_scan_f16_qs4<8, 0, true> : k_scan_f16_qs4<8, 0, false>;
+            if (kt == 12 && !l2) return k_scan_f16_qs4<12, 16, false>;
+            break;
+        case plan::QSW:
+            if (kt == 16) return l2 ? k_scan_f16_qsw<16, true> : k_scan_f16_qsw<16, false>;
+            if (kt == 20) return l2 ? k_scan_f16_qsw<20, true> : k_scan_f16_qsw<20, false>;
+            break;
+        default: break;
     }
+    return nullptr;
 }
 
-// QS4 = the QS2 work decomposition on v_mfma_f32_16x16x32_f16 (round 5); LEMON_QS4=0 selects QS2 (A/B aid)
-static bool use_qs4() {
-    const char *e = getenv("LEMON_QS4");
-    return !(e && e[0] == '0');
+static int launch_scan(plan::Kernel kernel, int kt, bool l2, unsigned grid, hipStream_t stream, const ScanParamsH &p) {
+    const scan_kernel_t fn = scan_kernel(kernel, kt, l2);
+    if (!fn) {      // (a plan that asks for a form that was never built is a bug, not a reason for another kernel)
+        lemon_set_error("bf16 scan: no %s kernel at pitch %d", plan::FACTS[kernel].name, kt * BKH);
+        return LEMON_E_INVALID;
+    }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), 0, stream, p);
+    return LEMON_OK;
 }
 
-// (the L2 epilogue's |x|^2 loads and |q|^2 registers do not fit next to d = 768's fragments -- 14 spilled registers with 20 parked
-// steps, and 21 is what the LDS holds --, so squared-L2 at pitch 768 stays on QS2)
-static bool qs4_serves(int kt, bool l2) { return kt == 8 || !l2; }
-
-template <bool l2>
-static void launch_qs4(int kt, unsigned grid, hipStream_t stream, const ScanParamsH &p) {
-    if (kt == 8) hipLaunchKernelGGL((k_scan_f16_qs4<8, 0, l2>), dim3(grid), dim3(NT), 0, stream, p);
-    else if (!l2) hipLaunchKernelGGL((k_scan_f16_qs4<12, 16, false>), dim3(grid), dim3(NT), 0, stream, p);
+// exact re-scoring + exact top-k of every (query, split) list, one wave each
+static void launch_final(const FinalParams &fp, bool l2, hipStream_t stream) {
+    const bool staged = (fp.d % 4) == 0 && fp.d <= 1024;
+    void (*const fn)(FinalParams) = l2 ? (staged ? k_bf16_final<true, true> : k_bf16_final<true, false>)
+                                       : (staged ? k_bf16_final<false, true> : k_bf16_final<false, false>);
+    hipLaunchKernelGGL(fn, dim3((unsigned)((fp.n_lists + 3) / 4)), dim3(256), 0, stream, fp);
 }
 
-// QSW: pitches 1024 (kt = 16) and 1280 (kt = 20), both metrics
-template <bool l2>
-static void launch_qsw(int kt, unsigned grid, hipStream_t stream, const ScanParamsH &p) {
-    if (kt == 16) hipLaunchKernelGGL((k_scan_f16_qsw<16, l2>), dim3(grid), dim3(NT), 0, stream, p);
-    else          hipLaunchKernelGGL((k_scan_f16_qsw<20, l2>), dim3(grid), dim3(NT), 0, stream, p);
+// per-lane state carried between chunk launches + the list counts handed to k_bf16_final
+static int ensure_scan_state(lemon_index_t *idx, int64_t elems, hipStream_t stream) {
+    if (elems <= idx->ws_state_elems) return LEMON_OK;
+    LEMON_HIP_CHECK(hipStreamSynchronize(stream));
+    if (idx->ws_state) (void)hipFree(idx->ws_state);
+    idx->ws_state = nullptr; idx->ws_state_elems = 0;
+    if (hipMalloc(&idx->ws_state, (size_t)elems * sizeof(float)) != hipSuccess) {
+        lemon_set_error("scan state allocation failed");
+        return LEMON_E_NOMEM;
+    }
+    idx->ws_state_elems = elems;
+    return LEMON_OK;
 }
 
 int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, float *D_dev,
@@ -2378,81 +2363,19 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
     int rc = ensure_bf16_copy(idx, stream);
     if (rc) return rc;
     const int dpad_h = idx->dpad_h;
-    const bool qs = dpad_h <= 768;
-    // pitches 1024 / 1280 exist only with the wide filter on (bf16_pitch): k_scan_f16_qsw from the panel threshold on
-    const bool wide = idx->wide_filter && idx->d > 768 && (dpad_h == 1024 || dpad_h == 1280);
-    const char *kernel_name = "scan_bf16";
-    // QS2 halves the panel count.  When 256-query panels alone do not fill the chip the database would be split between more
-    // workgroups, and every split pays its own cold start (k ln(n/k) appends per query): measured 13.0 -> 20.1 ms at
-    // 50 000 x 40 000 x 512 and 17.3 -> 21.8 ms at 131 072^2 x 256 (k = 11), against 1 648 -> 1 501 ms at 1 M x 768,
-    // 142.1 -> 129.9 ms at 262 144^2 x 768 and 103.9 -> 97.8 ms at 262 144^2 x 512.  So: from 768 panels of 256 queries on
-    // (the splits == 1 regime of lemon_plan_splits), pitches 512 and 768.
-    const char *qs2_env = getenv("LEMON_QS2_MIN_PANELS");      // (read per call: the tests force QS2 onto small shapes with 0)
-    const int qs2_min = qs2_env ? atoi(qs2_env) : 768;
-    static const int cus = [] {
-        int dev = 0, c = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-        return c > 0 ? c : 256;
-    }();
-    const int n_tiles128 = (int)((idx->n + BX - 1) / BX);
-    static const bool rest_qs4 = [] { const char *e = getenv("LEMON_QS4_REST"); return !(e && e[0] == '0'); }();   // (A/B aid)
-    bool prev_qs4 = false, prev_qsw = false;
-    int64_t cn = 0;
-    for (int64_t c0 = 0; c0 < nq; c0 += cn) {
-        cn = (nq - c0) < QCHUNK_H ? (nq - c0) : QCHUNK_H;
-        bool qs2 = qs && use_qs2() && dpad_h >= 512 && cn >= (int64_t)qs2_min * BQ2;
-        bool qs4 = qs2 && use_qs4() && qs4_serves(dpad_h / BKH, idx->metric == LEMON_METRIC_L2);
-        // The ragged rest behind whole-round QS4 chunks (1 M queries: 16 960 = 67 panels of 256): the same kernel with the database
-        // split between a few workgroups per panel -- the smallest split count that fills at least three quarters of the rounds it
-        // takes (67 panels x 3 = 201 of 256 slots) -- instead of 133 one-block panels x 6 splits (39 ms per modality at 1 M x 768).
-        int rest_splits = 0;
-        if (!qs2 && prev_qs4 && c0 > 0 && rest_qs4) {
-            const int panels_r = (int)((cn + BQ2 - 1) / BQ2);
-            for (int sp = 1; sp <= 16 && !rest_splits; ++sp) {
-                const int64_t wgs = (int64_t)panels_r * sp, rounds = (wgs + cus - 1) / cus;
-                if (wgs * 4 >= rounds * cus * 3 && n_tiles128 / sp >= 64) rest_splits = sp;
-            }
-            if (rest_splits) qs2 = qs4 = true;
-        }
-        prev_qs4 = qs4;
-        // the wide kernel: the same threshold in panels of its own 128 queries, the same whole-round cut and split rest
-        bool qsw = wide && cn >= (int64_t)qs2_min * BQW;
-        if (wide && !qsw && prev_qsw && c0 > 0 && rest_qs4) {
-            const int panels_r = (int)((cn + BQW - 1) / BQW);
-            for (int sp = 1; sp <= 16 && !rest_splits; ++sp) {
-                const int64_t wgs = (int64_t)panels_r * sp, rounds = (wgs + cus - 1) / cus;
-                if (wgs * 4 >= rounds * cus * 3 && n_tiles128 / sp >= 64) rest_splits = sp;
-            }
-            if (rest_splits) qsw = true;
-        }
-        prev_qsw = qsw;
-        if (qsw && cn < QCHUNK_H) {
-            const int64_t panels_c = (cn + BQW - 1) / BQW, full = panels_c / cus * cus;
-            if (full > 0 && panels_c != full && (panels_c - full) * 5 < (int64_t)cus * 4) cn = full * BQW;
-        }
-        const bool qsx = qs || qsw;                        // a Q-stationary kernel: lane lists, chunked launches, k_bf16_final
-        if (qs2 && cn < QCHUNK_H) {
-            // Whole rounds first.  The chunked scan runs ONE workgroup per CU, all of equal length: 1 859 workgroups take
-            // eight rounds of 256 like 2 048 do (1 M queries = 2 048 + 1 859 panels: 4.6 % of the scan spent in a quarter-full
-            // last round).  So a final stretch that does not fill its last round to 80 % is cut at the last whole round; the
-            // ragged rest (< 205 panels) comes back through this loop, is too small for QS2 and goes through the one-block
-            // kernel with the database split between workgroups -- a few rounds of 1/splits of the scan each.
-            const int64_t panels_c = (cn + BQ2 - 1) / BQ2, full = panels_c / cus * cus;
-            if (full > 0 && panels_c != full && (panels_c - full) * 5 < (int64_t)cus * 4) cn = full * BQ2;
-        }
-        const int bqw = qs2 ? BQ2 : BQ;                     // queries per workgroup
-        const int rt = (qs2 || qsw) ? RT2 : BX;             // database rows per tile
-        const int n_tiles = (int)((idx->n + rt - 1) / rt);
-        const int64_t nq_pad = round_up(cn, bqw);
-        const int panels = (int)(nq_pad / bqw);
-        int splits, tiles_per_split;
-        lemon_plan_splits(panels, n_tiles128, &splits, &tiles_per_split);
-        if (rest_splits) {
-            tiles_per_split = (n_tiles128 + rest_splits - 1) / rest_splits;
-            splits = (n_tiles128 + tiles_per_split - 1) / tiles_per_split;
-        }
-        if (qs2 || qsw) tiles_per_split *= BX / RT2;     // (the plan counts 128-row tiles)
-        rc = lemon_ensure_search_ws(idx, nq_pad, splits, (int64_t)panels * splits * (bqw / BQ), dpad_h * 2, CAPH, stream);
+    const bool l2 = idx->metric == LEMON_METRIC_L2;
+    const plan::Knobs knobs = read_knobs();
+    const char *kernel_name = plan::FACTS[plan::SCAN_BF16].name;
+    plan::Plan pl;
+    pl.kernel = plan::SCAN_BF16; pl.cn = 0;
+    for (int64_t c0 = 0; c0 < nq; c0 += pl.cn) {
+        pl = plan::plan_chunk(nq - c0, c0 == 0, pl.kernel, idx->n, d, dpad_h, l2, idx->wide_filter != 0, device_cus(), knobs);
+        const int64_t cn = pl.cn, nq_pad = (int64_t)pl.panels * pl.panel;
+        const unsigned grid = (unsigned)(pl.panels * pl.splits);
+        const bool stationary = pl.kernel != plan::SCAN_BF16;   // lane lists, chunked launches, k_bf16_final
+        rc = lemon_ensure_search_ws(idx, nq_pad, pl.splits, (int64_t)grid * (pl.panel / BQ), dpad_h * 2, CAPH, stream);
+        if (rc) return rc;
+        rc = ensure_scan_state(idx, pl.state_elems + pl.cnt_elems, stream);
         if (rc) return rc;
         // bf16 query panel (pad rows zero), chain norms, measured rounding residuals
         lp16 *qh = reinterpret_cast<lp16 *>(idx->ws_qp);
@@ -2469,139 +2392,40 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
         p.b.cand = idx->ws_cand; p.b.part = idx->ws_part;
         p.b.D = D_dev + c0 * k; p.b.I = I_dev + c0 * k;
         p.b.nq = cn; p.b.n = idx->n; p.b.dpad = dpad_h; p.b.kk = k; p.b.metric = idx->metric;
-        p.b.n_tiles = n_tiles; p.b.tiles_per_split = tiles_per_split; p.b.splits = splits; p.b.nq_pad = nq_pad;
+        p.b.n_tiles = pl.n_tiles; p.b.tiles_per_split = pl.tiles_per_split; p.b.splits = pl.splits; p.b.nq_pad = nq_pad;
         p.qh = qh; p.xh = reinterpret_cast<const lp16 *>(idx->xh);
         p.q = q_dev + c0 * d; p.x = idx->x; p.qres2 = qres2; p.qhn2 = qhn2; p.xstat = idx->xn2max_dev;
-        p.d = d; p.dpad_h = dpad_h; p.phase_dbg = nullptr;
-        rc = lemon_parse_ablate("k_scan_bf16_qs", 1 | 4 | 8, &p.ablate);   // bit 1 (value 2) does not exist: see ScanParamsH
+        p.d = d; p.dpad_h = dpad_h;
+        rc = lemon_parse_ablate("k_scan_bf16_qs", 1 | 4, &p.ablate);   // bit 1 (value 2) does not exist: see ScanParamsH
         if (rc) return rc;
-        static const int refresh = [] { const char *e = getenv("LEMON_REFRESH"); return e && atoi(e) > 0 ? atoi(e) : REFRESH; }();
-        p.b.stale = refresh;                  // new candidates per query that trigger a light compaction (tuning knob)
-        const unsigned grid = (unsigned)(panels * splits);
-        // database chunks sized for the Infinity Cache (the chunk is re-read by every query panel)
-        int chunk_tiles = n_tiles;
-        if (qsx && splits == 1) {
-            const char *env = getenv("LEMON_CHUNK_MB");
-            const double mb = env ? atof(env) : 64.0;
-            if (mb > 0) {
-                chunk_tiles = (int)(mb * 1048576.0 / ((double)rt * dpad_h * 2));
-                if (chunk_tiles < 8) chunk_tiles = 8;
-            }
-            if (chunk_tiles > n_tiles) chunk_tiles = n_tiles;
-        }
-        // per-lane state carried between chunk launches (splits == 1) + the half-list counts handed to k_bf16_final
-        const int64_t state_elems = (qsx && splits == 1) ? (int64_t)grid * NT * (qs4 ? 16 : (qs2 || qsw) ? 8 : 4) : 0;
-        const int64_t cnt_elems = qsx ? (int64_t)grid * bqw * ((qs4 || qsw) ? 4 : 2) : 0;
-        if (state_elems + cnt_elems > idx->ws_state_elems) {
-            LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-            if (idx->ws_state) (void)hipFree(idx->ws_state);
-            idx->ws_state = nullptr; idx->ws_state_elems = 0;
-            if (hipMalloc(&idx->ws_state, (size_t)(state_elems + cnt_elems) * sizeof(float)) != hipSuccess) {
-                lemon_set_error("scan state allocation failed");
-                return LEMON_E_NOMEM;
-            }
-            idx->ws_state_elems = state_elems + cnt_elems;
-        }
+        p.b.stale = scan_refresh();
         p.state = idx->ws_state;
-        p.cnt = reinterpret_cast<int *>(idx->ws_state + state_elems);
-        const bool l2m_ = idx->metric == LEMON_METRIC_L2;
+        p.cnt = reinterpret_cast<int *>(idx->ws_state + pl.state_elems);
         FinalParams fp;
-        fp.b = p.b; fp.q = p.q; fp.x = p.x; fp.cnt = p.cnt; fp.d = d; fp.rows_per_wg = bqw; fp.segs = (qs4 || qsw) ? 4 : 2; fp.n_lists = (int64_t)grid * bqw;
-        fp.qres2 = qres2; fp.xstat = idx->xn2max_dev;
-        static const int prefilter = [] { const char *e = getenv("LEMON_FINAL_PREFILTER"); return !(e && e[0] == '0'); }();   // (A/B aid)
-        fp.prefilter = prefilter;
-        auto launch_final = [&]() {     // exact re-scoring + exact top-k of every (query, split) list, one wave each
-            const unsigned fg = (unsigned)((fp.n_lists + 3) / 4);
-            const bool staged = (d % 4) == 0 && d <= 1024;
-            if (l2m_) { if (staged) hipLaunchKernelGGL((k_bf16_final<true, true>), dim3(fg), dim3(256), 0, stream, fp);
-                        else        hipLaunchKernelGGL((k_bf16_final<true, false>), dim3(fg), dim3(256), 0, stream, fp); }
-            else      { if (staged) hipLaunchKernelGGL((k_bf16_final<false, true>), dim3(fg), dim3(256), 0, stream, fp);
-                        else        hipLaunchKernelGGL((k_bf16_final<false, false>), dim3(fg), dim3(256), 0, stream, fp); }
-        };
-        const bool l2m = idx->metric == LEMON_METRIC_L2;
-        for (int t0 = 0; t0 < n_tiles; t0 += chunk_tiles) {
-            const int t1 = (t0 + chunk_tiles < n_tiles) ? t0 + chunk_tiles : n_tiles;
-            p.chunk_t0 = t0; p.chunk_t1 = t1; p.first_chunk = (t0 == 0); p.last_chunk = (t1 == n_tiles);
-            const double rows = (double)(t1 - t0) * rt < (double)idx->n - (double)t0 * rt ? (double)(t1 - t0) * rt
-                                                                                            : (double)idx->n - (double)t0 * rt;
+        fp.b = p.b; fp.q = p.q; fp.x = p.x; fp.cnt = p.cnt; fp.d = d; fp.rows_per_wg = pl.panel; fp.segs = pl.segs;
+        fp.n_lists = (int64_t)grid * pl.panel; fp.qres2 = qres2; fp.xstat = idx->xn2max_dev; fp.prefilter = final_prefilter_on();
+        for (int t0 = 0; t0 < pl.n_tiles; t0 += pl.chunk_tiles) {
+            const int t1 = (t0 + pl.chunk_tiles < pl.n_tiles) ? t0 + pl.chunk_tiles : pl.n_tiles;
+            p.chunk_t0 = t0; p.chunk_t1 = t1; p.first_chunk = (t0 == 0); p.last_chunk = (t1 == pl.n_tiles);
+            const double rows = (double)(t1 - t0) * pl.tile < (double)idx->n - (double)t0 * pl.tile ? (double)(t1 - t0) * pl.tile
+                                                                                                    : (double)idx->n - (double)t0 * pl.tile;
             const double flops = 2.0 * (double)cn * rows * (double)d;
             const double bytes = 2.0 * d * ((double)nq_pad / BQ * rows) + (p.last_chunk ? 2.0 * d * cn + 12.0 * k * (double)cn : 0.0);
             LemonProfScope prof(idx, stream, flops, bytes);
-            if (qsw) {
-                if (l2m) launch_qsw<true>(dpad_h / BKH, grid, stream, p);
-                else     launch_qsw<false>(dpad_h / BKH, grid, stream, p);
-                if (p.last_chunk) launch_final();
-                continue;
-            }
-            if (qs4) {
-#ifdef LEMON_QS4_PHASES
-                static unsigned long long *dbg4 = nullptr;
-                if (!dbg4) { (void)hipMalloc(&dbg4, 64); }
-                (void)hipMemsetAsync(dbg4, 0, 64, stream);
-                p.phase_dbg = dbg4;
-#endif
-                if (l2m) launch_qs4<true>(dpad_h / BKH, grid, stream, p);
-                else     launch_qs4<false>(dpad_h / BKH, grid, stream, p);
-#ifdef LEMON_QS4_PHASES
-                (void)hipStreamSynchronize(stream);
-                unsigned long long h4[8];
-                (void)hipMemcpy(h4, dbg4, 64, hipMemcpyDeviceToHost);
-                fprintf(stderr, "[qs4 phases] grid=%u tiles/wg=%.0f loop=%.4g cyc/wg  step0=%.1f%% (%.0f cyc/tile) maintain=%.1f%% sync=%.1f%% (%.0f cyc/tile)  tiles with slow path %.1f%%, with compaction %.2f%%\n",
-                        grid, (double)h4[4] / grid, (double)h4[0] / grid, 100.0 * h4[1] / h4[0], (double)h4[1] / (double)h4[4], 100.0 * h4[2] / h4[0],
-                        100.0 * h4[3] / h4[0], (double)h4[3] / (double)h4[4], 100.0 * h4[5] / (double)h4[4], 100.0 * h4[6] / (double)h4[4]);
-#endif
-                if (p.last_chunk) launch_final();
-                continue;
-            }
-            if (qs && dpad_h / BKH == 12 && !l2m && getenv("LEMON_PHASE_PROF")) {   // diagnostic build: phase cycle sums
-                static unsigned long long *dbg = nullptr;
-                if (!dbg) { (void)hipMalloc(&dbg, 64); (void)hipMemset(dbg, 0, 64); }
-                p.phase_dbg = dbg;
-                if (qs2) launch_qs2<false, true>(12, grid, stream, p);
-                else hipLaunchKernelGGL((k_scan_bf16_qs<12, false, true>), dim3(grid), dim3(NT), 0, stream, p);
-                (void)hipStreamSynchronize(stream);
-                unsigned long long h[8]; (void)hipMemcpy(h, dbg, 64, hipMemcpyDeviceToHost);
-
-                const double tot = (double)(h[0] + h[1] + h[2] + h[3]);
-                fprintf(stderr, "[phase] grid=%u loop=%.1f%% epilogue=%.1f%% sync=%.1f%% maintain=%.1f%% total=%.3g cyc/WG=%.3g\n",
-                        grid, 100.0 * h[0] / tot, 100.0 * h[1] / tot, 100.0 * h[2] / tot, 100.0 * h[3] / tot, tot, tot / grid);
-                (void)hipMemset(dbg, 0, 64);
-                if (p.last_chunk) launch_final();
-                continue;
-            }
-            if (qs2) {
-                if (l2m) launch_qs2<true, false>(dpad_h / BKH, grid, stream, p);
-                else     launch_qs2<false, false>(dpad_h / BKH, grid, stream, p);
-                if (p.last_chunk) launch_final();
-                continue;
-            }
-            switch (qs ? dpad_h / BKH : 0) {
-                case 4:
-                    if (l2m) hipLaunchKernelGGL((k_scan_bf16_qs<4, true, false>), dim3(grid), dim3(NT), 0, stream, p);
-                    else     hipLaunchKernelGGL((k_scan_bf16_qs<4, false, false>), dim3(grid), dim3(NT), 0, stream, p);
-                    break;
-                case 8:
-                    if (l2m) hipLaunchKernelGGL((k_scan_bf16_qs<8, true, false>), dim3(grid), dim3(NT), 0, stream, p);
-                    else     hipLaunchKernelGGL((k_scan_bf16_qs<8, false, false>), dim3(grid), dim3(NT), 0, stream, p);
-                    break;
-                case 12:
-                    if (l2m) hipLaunchKernelGGL((k_scan_bf16_qs<12, true, false>), dim3(grid), dim3(NT), 0, stream, p);
-                    else     hipLaunchKernelGGL((k_scan_bf16_qs<12, false, false>), dim3(grid), dim3(NT), 0, stream, p);
-                    break;
-                default: hipLaunchKernelGGL(k_scan_bf16, dim3(grid), dim3(NT), 0, stream, p); break;
-            }
-            if (qs && p.last_chunk) launch_final();
+            rc = launch_scan(pl.kernel, dpad_h / BKH, l2, grid, stream, p);
+            if (rc) return rc;
+            if (stationary && p.last_chunk) launch_final(fp, l2, stream);
         }
         LEMON_HIP_CHECK(hipGetLastError());
-        if (splits > 1) {
-            rc = lemon_launch_merge(idx->ws_part, splits, nullptr, nq_pad, cn, k, idx->metric, p.b.D, p.b.I, stream);
+        if (pl.splits > 1) {
+            rc = lemon_launch_merge(idx->ws_part, pl.splits, nullptr, nq_pad, cn, k, idx->metric, p.b.D, p.b.I, stream);
             if (rc) return rc;
         }
         idx->last.algo = LEMON_ALGO_BF16_FILTER;
         if (c0 == 0) {                                  // (the first chunk is the largest: its geometry is what gets reported)
-            kernel_name = qsw ? "qsw" : qs4 ? "qs4" : qs2 ? "qs2" : qs ? "qs" : "scan_bf16";
+            kernel_name = pl.name;
             idx->last.grid = (int)grid; idx->last.block = NT;
-            idx->last.query_panel = bqw; idx->last.db_splits = splits;
+            idx->last.query_panel = pl.panel; idx->last.db_splits = pl.splits;
         }
     }
     idx->last.nq = nq; idx->last.n = idx->n; idx->last.d = d; idx->last.k = k;

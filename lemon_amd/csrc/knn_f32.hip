@@ -17,6 +17,7 @@
 // workgroups that walk the same tiles in step.
 #include "knn_common.hpp"
 #include "scan_plan.hpp"
+#include "knn_bf16_plan.hpp"
 #include <algorithm>
 #include <vector>
 
@@ -536,23 +537,10 @@ int lemon_fill_empty(float *D, int64_t *I, int64_t total, int metric, hipStream_
     return LEMON_OK;
 }
 
-// enough workgroups to fill 256 CUs x 2 resident 1.5 times; every split keeps >= 8 tiles so the
-// per-split warm-up (first-tile selection, final sort, merge) amortises
+// (the rule itself is plain C++ in knn_bf16_plan.hpp, where the 16-bit scan's plan uses it too)
 void lemon_plan_splits(int panels, int n_tiles, int *splits_out, int *tiles_per_split_out) {
-    int splits = 1;
     static const int forced = [] { const char *e = getenv("LEMON_SPLITS"); return e ? atoi(e) : 0; }();   // tuning knob
-    if (forced > 0) {
-        splits = forced;
-        if (splits > n_tiles) splits = n_tiles;
-    } else if (panels < 768) {
-        splits = (768 + panels - 1) / panels;
-        int max_splits = n_tiles / 8;
-        if (max_splits < 1) max_splits = 1;
-        if (splits > max_splits) splits = max_splits;
-    }
-    const int tiles_per_split = (n_tiles + splits - 1) / splits;
-    *splits_out = (n_tiles + tiles_per_split - 1) / tiles_per_split;
-    *tiles_per_split_out = tiles_per_split;
+    lemon_bf16_plan::plan_splits(panels, n_tiles, forced, splits_out, tiles_per_split_out);
 }
 
 // Planned ("stream-K", XCD-aware) decomposition of the fp32 scan.

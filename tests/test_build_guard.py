@@ -60,13 +60,15 @@ _GEMM_ASM = ["k_gemm_f16x3tILi0E", "k_gemm_f16x3tILi1E", "k_gemm_f16x3tILi2E",
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src,must_be_clean", [
-    # (mangled-name fragments of the PRODUCTION instantiations: PROF = false)
+    # (mangled-name fragments of the PRODUCTION instantiations; k_scan_f32: PROF = false, the 16-bit scans have no other form)
     ("knn_f32.hip", ["k_scan_f32ILb0ELb0ELb0E", "k_scan_f32ILb1ELb0ELb0E"]),
-    ("knn_bf16.hip", ["k_scan_bf16_qsILi12ELb0ELb0E", "k_scan_bf16_qsILi8ELb0ELb0E", "k_scan_bf16_qsILi4ELb0ELb0E",
-                      "k_scan_bf16_qs2ILi12ELi16ELb0ELb0ELb1E", "k_scan_bf16_qs2ILi12ELi20ELb1ELb0ELb1E",
-                      "k_scan_bf16_qs2ILi8ELi0ELb0ELb0ELb1E", "k_bf16_finalILb0ELb1E", "k_bf16_finalILb1ELb1E",
+    ("knn_bf16.hip", ["k_scan_bf16_qsILi12ELb0E", "k_scan_bf16_qsILi8ELb0E", "k_scan_bf16_qsILi4ELb0E",
+                      "k_scan_bf16_qs2ILi12ELi16ELb0E", "k_scan_bf16_qs2ILi12ELi20ELb1E",
+                      "k_scan_bf16_qs2ILi8ELi0ELb0E", "k_bf16_finalILb0ELb1E", "k_bf16_finalILb1ELb1E",
                       # round 5: the same scan on v_mfma_f32_16x16x32_f16 (IP at pitches 768 / 512, squared L2 at pitch 512)
-                      "k_scan_f16_qs4ILi12ELi16ELb0E", "k_scan_f16_qs4ILi8ELi0ELb0E", "k_scan_f16_qs4ILi8ELi0ELb1E"]),
+                      "k_scan_f16_qs4ILi12ELi16ELb0E", "k_scan_f16_qs4ILi8ELi0ELb0E", "k_scan_f16_qs4ILi8ELi0ELb1E",
+                      # the wide kernel, pitches 1024 / 1280, both metrics each
+                      "k_scan_f16_qswILi16E", "k_scan_f16_qswILi20E"]),
     # the hand-written GEMM (asm LDS-DMA / ds_read / MFMA with pinned accumulators: two workgroups per CU need <= 256 registers)
     # and the attention kernels (three waves per SIMD)
     ("gemm_f16x3.hip", _GEMM_CLEAN),
@@ -196,8 +198,9 @@ def _check_asm_discipline(name, lines):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src,kernels", [
     ("gemm_f16x3.hip", _GEMM_ASM),
-    ("knn_bf16.hip", ["k_scan_bf16_qs2ILi12ELi16ELb0ELb0ELb1E", "k_scan_bf16_qs2ILi12ELi20ELb1ELb0ELb1E", "k_scan_bf16_qs2ILi8ELi0ELb0ELb0ELb1E",
-                      "k_scan_f16_qs4ILi12ELi16ELb0E", "k_scan_f16_qs4ILi8ELi0ELb0E", "k_scan_f16_qs4ILi8ELi0ELb1E"]),
+    ("knn_bf16.hip", ["k_scan_bf16_qs2ILi12ELi16ELb0E", "k_scan_bf16_qs2ILi12ELi20ELb1E", "k_scan_bf16_qs2ILi8ELi0ELb0E",
+                      "k_scan_f16_qs4ILi12ELi16ELb0E", "k_scan_f16_qs4ILi8ELi0ELb0E", "k_scan_f16_qs4ILi8ELi0ELb1E",
+                      "k_scan_f16_qswILi16E", "k_scan_f16_qswILi20E"]),
     ("knn_f32.hip", ["k_scan_f32ILb0ELb0ELb0E", "k_scan_f32ILb1ELb0ELb0E"]),
 ])
 def test_hand_issued_asm_is_left_alone_by_the_compiler(src, kernels):

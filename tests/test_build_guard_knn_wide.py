@@ -15,9 +15,10 @@ import test_build_guard as g   # noqa: E402
 WIDE = ["k_scan_f16_qswILi16ELb0E", "k_scan_f16_qswILi16ELb1E", "k_scan_f16_qswILi20ELb0E", "k_scan_f16_qswILi20ELb1E"]
 
 # what tests/test_build_guard.py lists for knn_bf16.hip, with the number of kernels each fragment matched before k_scan_f16_qsw
-EXISTING = {"k_scan_bf16_qsILi12ELb0ELb0E": 1, "k_scan_bf16_qsILi8ELb0ELb0E": 1, "k_scan_bf16_qsILi4ELb0ELb0E": 1,
-            "k_scan_bf16_qs2ILi12ELi16ELb0ELb0ELb1E": 1, "k_scan_bf16_qs2ILi12ELi20ELb1ELb0ELb1E": 1,
-            "k_scan_bf16_qs2ILi8ELi0ELb0ELb0ELb1E": 1, "k_bf16_finalILb0ELb1E": 1, "k_bf16_finalILb1ELb1E": 1,
+# (the QS / QS2 fragments as they read since the PROF and ACCV template parameters were retired)
+EXISTING = {"k_scan_bf16_qsILi12ELb0E": 1, "k_scan_bf16_qsILi8ELb0E": 1, "k_scan_bf16_qsILi4ELb0E": 1,
+            "k_scan_bf16_qs2ILi12ELi16ELb0E": 1, "k_scan_bf16_qs2ILi12ELi20ELb1E": 1,
+            "k_scan_bf16_qs2ILi8ELi0ELb0E": 1, "k_bf16_finalILb0ELb1E": 1, "k_bf16_finalILb1ELb1E": 1,
             "k_scan_f16_qs4ILi12ELi16ELb0E": 1, "k_scan_f16_qs4ILi8ELi0ELb0E": 1, "k_scan_f16_qs4ILi8ELi0ELb1E": 1}
 
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # k_scan_bf16_qs A/B aid (GPU box): the in-tree library, then the variant libraries named in $VARIANTS
-# (.variants/liblemon_<X>.so, tools/build_variant.sh): 262 144^2 x 768 whole and filter-ablated, phase stamps, 1M x 768
+# (.variants/liblemon_<X>.so, tools/build_variant.sh): 262 144^2 x 768 whole and filter-ablated, 1M x 768
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 export PYTHONPATH=$R
@@ -9,7 +9,6 @@ one() {
   LABEL=$1
   run A=0
   run LEMON_ABLATE=1
-  TAILN=2 run LEMON_PHASE_PROF=1
   SHAPE="1000000 1000000 768 51" run A=0
 }
 one in-tree
