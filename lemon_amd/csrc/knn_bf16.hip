@@ -114,7 +114,9 @@ __device__ __forceinline__ float band_eps_raw(const unsigned *__restrict__ xstat
     float eps = (nq * sqrtf(xr2) + sqrtf(qres2) * sqrtf(xh2)) * 1.002f
               + 3.0f * (float)d * 5.9604645e-8f * nq * sqrtf(xn2) * 1.002f + 1e-30f;
     if (l2) eps = 2.0f * eps + 4.8e-7f * (qn + xn2);
-    return eps;
+    // a database maximum that overflowed to +inf (k_max_nonneg) times a zero query norm is NaN, and a NaN bound drops every row
+    // (`score > lo` is false): like +inf it has to admit everything -- bound_from_tau then gives -inf, every list is settled exactly
+    return eps == eps ? eps : INFINITY;
 }
 __device__ __forceinline__ float band_eps(const ScanParamsH &p, float qn, float qres2, bool l2) {
     return band_eps_raw(p.xstat, p.d, qn, qres2, l2);
