@@ -513,6 +513,24 @@ int lemon_grid_f1(const float *d1_dev, const float *D_n_dev, const float *dists_
                   const uint8_t *y_dev, int64_t n, int k, const double *hp_dev, int G, double xtol, int maxfun,
                   double *scores_ws_dev, double *f1_dev, double *thres_dev, void *stream);
 
+/* lemon_grid_f1 for several knn_k from ONE record: the six neighbour arrays are [n, kmax] (row pitch kmax) and for every
+ * k in ks[K] (host ints, strictly ascending, 1 <= ks[0], ks[K-1] <= kmax <= LEMON_MAX_K, 1 <= K <= LEMON_KSWEEP_MAX_KS) the
+ * outputs are what lemon_grid_f1 returns on the contiguous [n, k] prefix of the record, bit for bit: f1_dev, thres_dev [K, G]
+ * float64 and, when scores_dev is not NULL, the scores [K, G, n] float64.  hp [G, 6] is a HOST pointer (as in lemon_score);
+ * rows are arbitrary -- the neighbour terms are computed once per distinct (tau_1, tau_2) bit pattern of a side and once per
+ * sample for all ks (an exact top-k list is a prefix of every deeper one and the score sum runs in column order).
+ * ws_dev: caller-provided device workspace of at least lemon_grid_f1_ks_workspace_bytes(n, K, G, hp) bytes (ws_bytes says how
+ * many there are), 8-byte aligned; nothing is allocated on the device.  The call waits for the stream once, when the row
+ * tables have been handed to it.  G <= 65535.  Anything out of contract is refused with LEMON_E_INVALID and nothing is
+ * written.  lemon_grid_f1_ks_workspace_bytes returns -1 for arguments out of contract. */
+#define LEMON_KSWEEP_MAX_KS 16
+int64_t lemon_grid_f1_ks_workspace_bytes(int64_t n, int K, int G, const double *hp);
+int lemon_grid_f1_ks(const float *d1_dev, const float *D_n_dev, const float *dists_tr_n_dev, const float *dists_n_dev,
+                     const float *D_m_dev, const float *dists_tr_m_dev, const float *dists_m_dev,
+                     const uint8_t *y_dev, int64_t n, int kmax, const int *ks, int K, const double *hp, int G,
+                     double xtol, int maxfun, void *ws_dev, int64_t ws_bytes, double *scores_dev, double *f1_dev,
+                     double *thres_dev, void *stream);
+
 /* ---- k-means on caption embeddings + the deep-kNN label score ------------------------ */
 
 /* FaissKMeans.predict = index.search(x, 1) (lib/datasets/clustering.py:38-41) and the assignment step of faiss.Kmeans.train

@@ -11,6 +11,7 @@ SO_PATH = os.path.join(_HERE, "liblemon_hip.so")
 METRIC_IP = 0
 METRIC_L2 = 1
 MAX_K = 64            # per scan pass and in lemon_neighbors
+KSWEEP_MAX_KS = 16   # LEMON_KSWEEP_MAX_KS: values of k per lemon_grid_f1_ks call
 MAX_K_DEEP = 2048     # lemon_index_search (passes of MAX_K, include/lemon_hip.h)
 ATTENTION_MAX_SEQ = 4096   # LEMON_ATTENTION_MAX_SEQ (include/lemon_hip.h)
 ALGO_AUTO, ALGO_F32_MFMA, ALGO_BF16_FILTER = 0, 1, 2
@@ -23,6 +24,7 @@ EXPORTS = [
     "lemon_index_ntotal", "lemon_index_dim", "lemon_index_data", "lemon_index_search",
     "lemon_index_set_algo", "lemon_index_set_wide_filter", "lemon_index_last_scan_kernel", "lemon_index_set_query_dedup", "lemon_index_last_search_info", "lemon_index_set_profiling",
     "lemon_index_profile_read", "lemon_debug_scan_plan", "lemon_neighbors", "lemon_discrepancy", "lemon_score", "lemon_grid_f1",
+    "lemon_grid_f1_ks", "lemon_grid_f1_ks_workspace_bytes",
     "lemon_kmeans_assign", "lemon_kmeans_update", "lemon_kmeans_split", "lemon_kmeans_train", "lemon_kmeans_workspace_bytes",
     "lemon_knn_label_disagreement", "lemon_jpeg_info", "lemon_jpeg_entropy", "lemon_jpeg_reconstruct_host", "lemon_jpeg_decode",
     "lemon_jpeg_pack", "lemon_jpeg_entropy_device", "lemon_jpeg_entropy_workspace_bytes", "lemon_jpeg_entropy_par_host",
@@ -76,6 +78,10 @@ def load():
     lib.lemon_preprocess_ragged.argtypes = [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, vp, vp, c_int, ctypes.POINTER(ctypes.c_float),
                                             ctypes.POINTER(ctypes.c_float), c_int, c_int, vp, vp]
     lib.lemon_grid_f1.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_int, vp, c_int, ctypes.c_double, c_int, vp, vp, vp, vp]
+    lib.lemon_grid_f1_ks.argtypes = [vp] * 8 + [c_i64, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(ctypes.c_double), c_int,
+                                     ctypes.c_double, c_int, vp, c_i64, vp, vp, vp, vp]
+    lib.lemon_grid_f1_ks_workspace_bytes.argtypes = [c_i64, c_int, c_int, ctypes.POINTER(ctypes.c_double)]
+    lib.lemon_grid_f1_ks_workspace_bytes.restype = c_i64
     lib.lemon_attention_f32.argtypes = [vp, c_i64, c_int, c_int, c_int, c_int, vp, vp]
     lib.lemon_attention_split3.argtypes = [vp, c_i64, c_int, c_int, c_int, c_int, vp, vp]
     lib.lemon_attention_f16x3.argtypes = [vp, c_i64, c_int, c_int, c_int, c_int, vp, vp]

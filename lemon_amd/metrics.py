@@ -187,6 +187,32 @@ def _torch_lbfgs(rec_t, y, x0, force_zero, force_one, max_iter=20):
     return x.detach().cpu().numpy()
 
 
+def grid_vectors(grid, force_zero=()):
+    """The grid of maximize_metric as hyper-parameter vectors in HP_NAMES order, in the reference's order of combinations:
+    tau_1 / tau_2 are shared between the n and m sides, forced-zero names are 0."""
+    gs = []
+    for c in combinations_base(grid):
+        g = []
+        for name in HP_NAMES:
+            if name in c:
+                g.append(c[name])
+            elif name in ("tau_1_n", "tau_1_m"):
+                g.append(c["tau_1"])
+            elif name in ("tau_2_n", "tau_2_m"):
+                g.append(c["tau_2"])
+            else:
+                raise NotImplementedError(name)
+            if name in force_zero:
+                g[-1] = 0.0
+        gs.append(g)
+    return gs
+
+
+def grid_points(grid, force_zero=(), force_one=()):
+    """The hyper-parameter dicts maximize_metric hands to its `batch_grid` callback, in that order."""
+    return [unpack_vector(g, force_zero, force_one) for g in grid_vectors(grid, force_zero)]
+
+
 def maximize_metric(score_fn, y, grid, x0s, obj_func=optimize_f1_efficient, obj_func_args=None,
                     force_zero=(), force_one=(), scipy_methods=("Powell", "Nelder-Mead"), rec_for_lbfgs=None,
                     batch_grid=None, lbfgs_device="cpu"):
@@ -222,21 +248,7 @@ def maximize_metric(score_fn, y, grid, x0s, obj_func=optimize_f1_efficient, obj_
             val = -objective(cand)
             if val > best_val:
                 best_val, best_x = val, cand
-    gs = []
-    for c in combinations_base(grid):
-        g = []
-        for name in HP_NAMES:
-            if name in c:
-                g.append(c[name])
-            elif name in ("tau_1_n", "tau_1_m"):
-                g.append(c["tau_1"])
-            elif name in ("tau_2_n", "tau_2_m"):
-                g.append(c["tau_2"])
-            else:
-                raise NotImplementedError(name)
-            if name in force_zero:
-                g[-1] = 0.0
-        gs.append(g)
+    gs = grid_vectors(grid, force_zero)
     # batch_grid: all grid points in one device launch (ops.grid_f1: same scores, same bounded-Brent search,
     # bit-identical values); the winner is still picked in grid order with the reference's strict '>'
     vals = batch_grid([unpack_vector(g, force_zero, force_one) for g in gs]) if (batch_grid is not None and gs) else None

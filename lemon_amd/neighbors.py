@@ -10,6 +10,19 @@ from .ops import dev_f32, metric_id, paired_distance, ptr, stream_ptr
 REC_KEYS = ("d_1", "D_n", "dists_n", "dists_tr_n", "D_m", "dists_m", "dists_tr_m", "I_n", "I_m")
 
 
+def prefix_record(rec, k):
+    """The record of a `k` search from the record of a deeper one: an exact best-first list is a prefix of every deeper
+    exact list, and dropping the self match (position 0 where the sample is in the DB, else the last position) leaves ranks
+    1..K or 0..K-1, whose first k columns are what a k search keeps ("k sweep").  d_1 (and anything else
+    that is not a per-neighbour array) passes through as it is; the first k columns of the six neighbour arrays, and of
+    I_n / I_m when present, are made contiguous."""
+    k = int(k)
+    depth = rec["D_n"].shape[1]
+    if not 1 <= k <= depth:
+        raise ValueError(f"prefix_record: k = {k} is outside 1 .. {depth}, the depth of the record")
+    return {key: (v[:, :k].contiguous() if key in REC_KEYS and key != "d_1" else v) for key, v in rec.items()}
+
+
 class LemonDB:
     """DB side of run_lemon.py:163-176: normalised train embeddings, the two flat indices and
     dists_tr.  Everything stays in HBM."""

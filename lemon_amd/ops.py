@@ -104,6 +104,54 @@ def grid_f1(rec, y, hparams, xtol=1e-8, maxfun=500, return_scores=False):
     return f1.cpu().numpy(), th.cpu().numpy()
 
 
+def grid_f1_ks(rec, y, hparams, ks, xtol=1e-8, maxfun=500, return_scores=False):
+    """grid_f1 for every k of `ks` from ONE record of depth kmax >= max(ks) (lemon_grid_f1_ks): the neighbour terms of all ks
+    come from one walk over the record, once per distinct (tau_1, tau_2) pair of a side -> (f1 [K, G], thres [K, G]) numpy
+    float64 (+ scores [K, G, n] with return_scores), row t bit-identical to grid_f1 on the contiguous [n, ks[t]] prefix.
+    `ks` strictly ascending.  Chunked over G so that the workspace of a launch stays within 1 GiB."""
+    dev = rec["D_n"].device
+    f32 = lambda key: dev_f32(rec[key], key)
+    d1, Dn, trn, dn, Dm, trm, dm = (f32(key) for key in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m"))
+    n, kmax = Dn.shape
+    ks = [int(k) for k in ks]
+    K = len(ks)
+    yb = torch.as_tensor(np.asarray(y).astype(bool).astype(np.uint8)).to(dev)
+    hp = np.ascontiguousarray(np.asarray(hparams, dtype=np.float64).reshape(-1, 6))
+    G = hp.shape[0]
+    lib = _lib.load()
+    c_ks = (ctypes.c_int * max(K, 1))(*ks)
+    dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    f1 = np.empty((K, G), dtype=np.float64)
+    th = np.empty((K, G), dtype=np.float64)
+    scores = np.empty((K, G, n), dtype=np.float64) if return_scores else None
+    bound = 1 << 30
+
+    def ws_bytes(g0, g1):
+        b = lib.lemon_grid_f1_ks_workspace_bytes(n, K, g1 - g0, dp(hp[g0:g1]))
+        if b < 0:
+            _lib.check(-1, "lemon_grid_f1_ks_workspace_bytes")
+        return b
+
+    chunk = max(1, min(65535, G, bound // (8 * n * max(K, 1))))
+    while chunk > 1 and any(ws_bytes(g0, min(G, g0 + chunk)) > bound for g0 in range(0, G, chunk)):
+        chunk = (chunk + 1) // 2
+    spans = [(g0, min(G, g0 + chunk)) for g0 in range(0, G, chunk)]
+    need = max([ws_bytes(*sp) for sp in spans] + [8])
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for g0, g1 in spans:
+            f1c = torch.empty((K, g1 - g0), dtype=torch.float64, device=dev)
+            thc = torch.empty((K, g1 - g0), dtype=torch.float64, device=dev)
+            sc = torch.empty((K, g1 - g0, n), dtype=torch.float64, device=dev) if return_scores else None
+            _lib.check(lib.lemon_grid_f1_ks(ptr(d1), ptr(Dn), ptr(trn), ptr(dn), ptr(Dm), ptr(trm), ptr(dm), ptr(yb), n, kmax,
+                                            c_ks, K, dp(hp[g0:g1]), g1 - g0, float(xtol), int(maxfun), ptr(ws), need, ptr(sc),
+                                            ptr(f1c), ptr(thc), stream_ptr(dev)), "lemon_grid_f1_ks")
+            f1[:, g0:g1], th[:, g0:g1] = f1c.cpu().numpy(), thc.cpu().numpy()
+            if return_scores:
+                scores[:, g0:g1] = sc.cpu().numpy()
+    return (f1, th, scores) if return_scores else (f1, th)
+
+
 ATTENTION_MAX_SEQ = _lib.ATTENTION_MAX_SEQ    # the header's LEMON_ATTENTION_MAX_SEQ; beyond 288 tokens the streaming kernels
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 _ACT_CODE = {None: ACT_NONE, "silu": ACT_SILU, "gelu": ACT_GELU}      # 'gelu': the exact (erf) GELU of BiomedCLIP's towers

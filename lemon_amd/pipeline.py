@@ -6,6 +6,7 @@ Python (:238-307).  Here embeddings never leave HBM: encoder output -> K1 normal
 world_size > 1 every rank embeds its shard of each split, the DB shards are all-gathered over RCCL
 (torch.distributed, backend "nccl") and each rank scores its own query shard.
 """
+import numbers
 import os
 import time
 
@@ -337,7 +338,23 @@ def score_splits(db, splits, k, hparams=None, discrete=False):
     All splits go through ONE lemon_neighbors call (one scan launch per modality instead of one per
     split and modality): the train split searches k+1 and drops result[0] where the sample is in the DB
     else result[-1] (run_lemon.py:257-263); val/test search k.  With the per-query `in_db` flag the
-    second case is exactly "keep the first k of k+1", so val/test ride along with in_db = 0."""
+    second case is exactly "keep the first k of k+1", so val/test ride along with in_db = 0.
+
+    k may be a list of ks: the same single call runs at max(ks) and the return value is {k: records}, the records of each k
+    being the prefix of the deep record (neighbors.prefix_record), scored with its own k when hparams is given."""
+    if not isinstance(k, numbers.Integral):
+        from .neighbors import prefix_record
+        ks = sorted({int(v) for v in k})
+        if not ks or ks[0] < 1:
+            raise ValueError(f"score_splits: the list of ks must hold values >= 1, got {list(k)}")
+        deep = score_splits(db, splits, ks[-1], None, discrete)
+        out = {}
+        for kk in ks:
+            out[kk] = {}
+            for name, rec in deep.items():
+                r = rec if kk == ks[-1] else prefix_record(rec, kk)
+                out[kk][name] = dict(r, score=ops.lemon_score(r, hparams)) if hparams is not None else dict(r)
+        return out
     splits = [s for s in splits if s["img"].shape[0] > 0]
     if not splits:
         return {}
@@ -381,7 +398,8 @@ def run_hot_path(embedder, data, k=5, dist_type="cosine", hparams=FIXED_HPARAMS,
     """One pass of the hot path over `data` = {split: {"pixels": float [n,3,S,S] or raw uint8 [n,H,W,3], "ids": [n,L], "label_id": [n]}}
     for split in train/val/test, this rank's shard of each.  DB = all ranks' train shards in global
     order.  The train split is embedded ONCE and reused as DB and as queries (the reference embeds it
-    twice, run_lemon.py:137-161 and :198-233; same model, same inputs => same embeddings)."""
+    twice, run_lemon.py:137-161 and :198-233; same model, same inputs => same embeddings).  k: an int, or a list of ks
+    (score_splits: one neighbour call at max(ks); returns ({k: records}, db))."""
     dev = embedder.device
     t0 = time.perf_counter()
     emb = {}
@@ -416,6 +434,7 @@ def run_hot_path(embedder, data, k=5, dist_type="cosine", hparams=FIXED_HPARAMS,
     if timers is not None:
         torch.cuda.synchronize(dev)
         timers["knn_score_s"] = time.perf_counter() - t0
-    for name in recs:                       # keep the embeddings the scores were computed from
-        recs[name]["emb_img"], recs[name]["emb_txt"] = emb[name]
+    for per_k in ([recs] if isinstance(k, numbers.Integral) else recs.values()):
+        for name in per_k:                  # keep the embeddings the scores were computed from
+            per_k[name]["emb_img"], per_k[name]["emb_txt"] = emb[name]
     return recs, db

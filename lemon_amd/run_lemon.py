@@ -7,7 +7,9 @@ per-sample record schema (:291-307).  Differences, all explicit:
     per-sample Python loop); the train split is embedded once and reused as DB and as queries;
   * weights/data come from LOCAL paths (extension flags --clip_path, --data_root, --arch, --algo,
     --encoder_batch); `--clip_path random[:arch]` / `--data_root synthetic:N` run without any files;
-  * under torchrun (WORLD_SIZE>1) samples are sharded over ranks, DB shards all-gathered over RCCL.
+  * under torchrun (WORLD_SIZE>1) samples are sharded over ranks, DB shards all-gathered over RCCL;
+  * extension flag --knn_k_sweep 1,2,5,...: the validation protocol's choice of knn_k in ONE run -- embed, DB build and search
+    once at the largest k, then the tail of a run per k on the prefix of the record (<output_dir>/knn_k=<k>/, k_selection.json).
 """
 import argparse
 import os
@@ -59,12 +61,56 @@ def build_parser():
                    help="where the SoftMargin/LBFGS polish of the hyper-parameter search runs (lib/metrics/utils.py:121-149)")
     p.add_argument("--hparam_grid", default="full", choices=["full", "small"],
                    help="'small' = 3x3x2x2 grid for smoke runs (reference grid is 21x21x4x4)")
+    p.add_argument("--knn_k_sweep", default=None, type=str,
+                   help="comma-separated knn_k values, e.g. 1,2,5,10,15,20,30,50 (the reference's grid, experiments.py:86): embed, build "
+                        "the DB and search ONCE at the largest, then run the tail of a --knn_k run for every value on the prefix "
+                        "of the record -> <output_dir>/knn_k=<k>/ and <output_dir>/k_selection.json; --knn_k is ignored")
     return p
+
+
+MAX_SWEEP_K = 63       # max + 1 <= LEMON_MAX_K: the train split searches k + 1 (include/lemon_hip.h)
+
+
+def parse_k_sweep(text):
+    """'10,1,5,5' -> [1, 5, 10]: sorted, de-duplicated.  Refused (ValueError): an empty list, anything that is not an integer,
+    a value < 1, a largest value whose train-split search (k + 1) would pass LEMON_MAX_K."""
+    parts = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not parts:
+        raise ValueError("--knn_k_sweep: the list is empty; expected comma-separated values of knn_k such as 1,2,5,10")
+    try:
+        ks = sorted({int(t) for t in parts})
+    except ValueError:
+        raise ValueError(f"--knn_k_sweep: {text!r} is not a comma-separated list of integers") from None
+    if ks[0] < 1:
+        raise ValueError(f"--knn_k_sweep: every knn_k must be >= 1, got {ks[0]}")
+    if ks[-1] > MAX_SWEEP_K:
+        raise ValueError(f"--knn_k_sweep: the largest knn_k is {ks[-1]}, but knn_k + 1 (the train split's search) must not "
+                         f"exceed LEMON_MAX_K = {MAX_SWEEP_K + 1}")
+    return ks
+
+
+def select_best_k(selected_val):
+    """{k: selected_val} -> the k with the highest value, ties to the smaller k; None when there is nothing to select on
+    (no k, or a k without a value)."""
+    if not selected_val or any(v is None for v in selected_val.values()):
+        return None
+    best = None
+    for k in sorted(selected_val):
+        if best is None or selected_val[k] > selected_val[best]:
+            best = k
+    return best
 
 
 def main(argv=None):
     from .cli_common import run_with_tee
-    return run_with_tee(_run, build_parser().parse_args(argv))
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.knn_k_sweep is not None:
+        try:
+            parse_k_sweep(args.knn_k_sweep)
+        except ValueError as e:
+            parser.error(str(e))
+    return run_with_tee(_run, args)
 
 
 def _run(args):
@@ -101,7 +147,8 @@ def _run(args):
     in_db_mask = np.zeros(n_train, dtype=np.uint8)
     in_db_mask[train_indices_in_compr] = 1
     names = ["val", "test"] if (args.debug or args.skip_train) else ["train", "val", "test"]
-    k = args.knn_k
+    sweep = parse_k_sweep(args.knn_k_sweep) if getattr(args, "knn_k_sweep", None) is not None else None
+    k = sweep[-1] if sweep else args.knn_k        # a sweep searches once, at its largest k
     frames = []
     for sname in names:
         if sname not in emb:
@@ -134,14 +181,100 @@ def _run(args):
     df = pd.concat(frames, ignore_index=True)
     n_samples = len(df)
     print(f"Finished {n_samples} samples in {timedelta} seconds; avg of {timedelta / n_samples}s per sample")
+    if sweep:
+        _sweep_tail(args, df, out_dir, device, sweep)
+    else:
+        _tail(args, df, out_dir, device)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+    return 0
 
+
+NEIGHBOR_COLUMNS = ("dists_n", "D_n", "dists_tr_n", "dists_m", "D_m", "dists_tr_m")
+
+
+def _device_rec(frame, device):
+    return {c: torch.from_numpy(np.stack(frame[c].values).astype(np.float32)).to(device)
+            for c in ("D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")} | \
+           {"d_1": torch.from_numpy(frame["d_1"].values.astype(np.float32)).to(device)}
+
+
+def _grid_setup(args):
+    """(grid, force_zero, force_one) of the hyper-parameter search, or None where the run never reaches the grid."""
+    if args.real_dataset or args.skip_hparam_optim or args.ablation in ("only_beta", "only_gamma", "multimodal_baseline"):
+        return None
+    grid = {"beta": np.arange(0, 100.01, 5), "gamma": np.arange(0, 100.01, 5), "tau_1": [0, 1, 5, 10],
+            "tau_2": [0, 1, 5, 10]} if args.hparam_grid == "full" else \
+           {"beta": [0, 5, 10], "gamma": [0, 5, 10], "tau_1": [0, 1], "tau_2": [0, 5]}
+    force_zero = {"none": [], "d1": [], "tau_1": ["tau_1_n", "tau_1_m"], "tau_2": ["tau_2_n", "tau_2_m"],
+                  "tau_1_2": ["tau_1_n", "tau_1_m", "tau_2_n", "tau_2_m"], "beta": ["beta"],
+                  "gamma": ["gamma"]}[args.ablation]
+    force_one = ["beta"] if args.ablation == "d1" else []
+    return grid, force_zero, force_one
+
+
+def _sweep_tail(args, df, out_dir, device, ks):
+    """The tail of a run for every k of the sweep, on the prefix of the record searched at max(ks); the grid of all ks comes
+    from ONE ops.grid_f1_ks call made in front of the loop."""
+    import copy
+    import json
+    from . import metrics as M, ops
+    from .neighbors import prefix_record
     if "d1" in args.ablation:
         df["d_1"] = 0.0
+    deep = {c: torch.from_numpy(np.stack(df[c].values)) for c in NEIGHBOR_COLUMNS}     # the gathered record, [n, max(ks)]
+    setup = _grid_setup(args)
+    grid_f1 = hps = None
+    if setup is not None:
+        df_val = df.query('sset == "val"')
+        hps = M.grid_points(*setup)
+        grid_f1 = ops.grid_f1_ks(_device_rec(df_val, device), df_val["is_mislabel"].values,
+                                 [[hp[n] for n in M.HP_NAMES] for hp in hps], ks)[0]
+    selection = {}
+    for t, k in enumerate(ks):
+        out_k = out_dir / f"knn_k={k}"
+        out_k.mkdir(exist_ok=True, parents=True)
+        args_k = copy.copy(args)
+        args_k.knn_k, args_k.output_dir = k, str(out_k)
+        with open(out_k / "args.json", "w") as f:
+            json.dump(vars(args_k), f, default=str)
+        df_k = df.copy()
+        pre = prefix_record(deep, k)
+        for c in NEIGHBOR_COLUMNS:
+            df_k[c] = list(pre[c].numpy())
 
-    def device_rec(frame):
-        return {c: torch.from_numpy(np.stack(frame[c].values).astype(np.float32)).to(device)
-                for c in ("D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")} | \
-               {"d_1": torch.from_numpy(frame["d_1"].values.astype(np.float32)).to(device)}
+        def served(asked, t=t):
+            assert asked == hps, "the grid of maximize_metric is not the grid lemon_grid_f1_ks was called with"
+            return grid_f1[t]
+
+        print(f"---- knn_k = {k} ----")
+        sel_res = _tail(args_k, df_k, out_k, device, batch_grid=served if grid_f1 is not None else None)
+        entry = None
+        if sel_res is not None:
+            entry = {"selected_val": sel_res.get("selected_val"), **{name: float(sel_res[name]) for name in M.HP_NAMES},
+                     "thres": sel_res.get("thres"),
+                     "splits": {sset: {"AUROC": float(sel_res[sset]["AUROC"]), "F1_optimal": float(sel_res[sset]["F1_optimal"])}
+                                for sset in df_k.sset.unique()}}
+            for key in ("selected_val", "thres"):
+                entry[key] = None if entry[key] is None else float(entry[key])
+        selection[k] = entry
+    best = None if any(e is None for e in selection.values()) else \
+        select_best_k({k: e["selected_val"] for k, e in selection.items()})
+    with open(out_dir / "k_selection.json", "w") as f:
+        json.dump({"ks": list(ks), "best_k": best, "per_k": {str(k): e for k, e in selection.items()}}, f, indent=1)
+    with open(os.path.join(out_dir, "done"), "w") as f:
+        f.write("done")
+
+
+def _tail(args, df, out_dir, device, batch_grid=None):
+    """Everything behind the per-sample record: the d1 ablation, the hyper-parameter search, the final score, the metrics and
+    the files of a run.  Returns agg_results' entry (None with --real_dataset / --skip_hparam_optim).  batch_grid: serves the
+    grid's F1 values in place of the ops.grid_f1 call (the k sweep)."""
+    from . import metrics as M, ops
+    device_rec = lambda frame: _device_rec(frame, device)
+    sel_res = None
+    if "d1" in args.ablation:
+        df["d_1"] = 0.0
 
     if args.real_dataset or args.skip_hparam_optim:
         res = {"df": df}
@@ -150,9 +283,6 @@ def _run(args):
         rec_val = device_rec(df_val)
         y_val = df_val["is_mislabel"].values
         score_fn = lambda hp: ops.lemon_score(rec_val, hp).cpu().numpy()      # K5 on the device-resident val arrays
-        grid = {"beta": np.arange(0, 100.01, 5), "gamma": np.arange(0, 100.01, 5), "tau_1": [0, 1, 5, 10],
-                "tau_2": [0, 1, 5, 10]} if args.hparam_grid == "full" else \
-               {"beta": [0, 5, 10], "gamma": [0, 5, 10], "tau_1": [0, 1], "tau_2": [0, 5]}
         crit = "know_val_labels"
         zero6 = dict(beta=0, gamma=0, tau_1_n=0, tau_2_n=0, tau_1_m=0, tau_2_m=0)
         if args.ablation == "only_beta":
@@ -164,17 +294,15 @@ def _run(args):
                 best = [0] * 6
                 best_f1, best_thres = M.optimize_f1_efficient(y_val, df_val["d_1"].values, return_thres=True)
             else:
-                force_zero = {"none": [], "d1": [], "tau_1": ["tau_1_n", "tau_1_m"], "tau_2": ["tau_2_n", "tau_2_m"],
-                              "tau_1_2": ["tau_1_n", "tau_1_m", "tau_2_n", "tau_2_m"], "beta": ["beta"],
-                              "gamma": ["gamma"]}[args.ablation]
-                force_one = ["beta"] if args.ablation == "d1" else []
+                grid, force_zero, force_one = _grid_setup(args)
                 rec_lbfgs = {c: (df_val[c].values if c == "d_1" else np.stack(df_val[c].values))
                              for c in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")}
                 best, best_f1, best_thres = M.maximize_metric(
                     score_fn, y_val, grid, [[0] * 6, [0.5] * 6, [1] * 6, [10] * 6], M.optimize_f1_efficient, {},
                     force_zero=force_zero, force_one=force_one, rec_for_lbfgs=rec_lbfgs,
                     lbfgs_device=str(device) if args.lbfgs_device == "cuda" else "cpu",
-                    batch_grid=lambda hps: ops.grid_f1(rec_val, y_val, [[hp[n] for n in M.HP_NAMES] for hp in hps])[0])
+                    batch_grid=batch_grid or
+                    (lambda hps: ops.grid_f1(rec_val, y_val, [[hp[n] for n in M.HP_NAMES] for hp in hps])[0]))
             sel_res = dict(zip(M.HP_NAMES, best))
             sel_res.update(thres=best_thres, selected_val=best_f1)
         s, dn, dm = ops.lemon_score(device_rec(df), sel_res, return_dn=True)
@@ -199,9 +327,7 @@ def _run(args):
             f.write("need_hparam_optim")
     with open(os.path.join(out_dir, "done"), "w") as f:
         f.write("done")
-    if world > 1:
-        torch.distributed.destroy_process_group()
-    return 0
+    return sel_res
 
 
 if __name__ == "__main__":
