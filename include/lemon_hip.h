@@ -353,6 +353,9 @@ int lemon_linear_f16x3t_set_profiling(int on);
  * summation order inside a k32 step; process-wide, for A/B runs and tests.  Returns the previous setting (>= 0) or an error. */
 int lemon_linear_f16x3t_set_mfma(int shape);
 int lemon_linear_f16x3t_profile_read(int64_t *launches, double *kernel_ms, double *flops);
+/* The kernel instantiation the calling thread's last lemon_linear_f16x3t / _ln / _chain call launched, as
+ * csrc/gemm_f16x3_plan.hpp names it (e.g. "k_gemm_f16x3t16<0, false, true, 2>"); "" before any launch.  For tests and tools. */
+const char *lemon_linear_f16x3t_last_kernel(void);
 /* lemon_attention_f32 whose result is written as that activation operand (rows = batch*seq_len, k = heads*64): the output
  * projection then runs in the hand-written GEMM too (with QKV: all four GEMMs of a block). */
 int lemon_attention_f16x3t(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,

@@ -104,18 +104,20 @@ class BertLayer(Block):
 
     def forward(self, x, causal=False, rows=None, carry=None, lengths=None):
         B, L, W = x.shape
-        if lengths is not None and not (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
+        # (the library form of a layer takes head dim 64 whatever the head-dim mode says, and has no width cap: only `attn` is read)
+        p = self._plan(x, head_dims=0)
+        if lengths is not None and p.qkv == "torch":
             raise ValueError("BertLayer: per-caption lengths exist on the fused GPU path only")
-        if x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled():
+        if p.qkv != "torch":
             # every GEMM through the library entry points of the current mode (lemon_linear_f32 / _bf16x6 / _f16x3), LayerNorm and
             # attention kernels: the form the fallbacks and the A/B modes run
             from . import ops
-            mode = ops.gemm_mode()
+            mode = p.mode
             ops.select_attention_arithmetic(mode)
             qkv = self._gemm(x, "qkv", ops, mode)
             if lengths is not None:                    # (ops.attention raises where the kernels take no lengths: never unmasked)
                 a = ops.attention(qkv, self.heads, False, lengths=lengths)
-            elif W == 64 * self.heads and L <= ops.ATTENTION_MAX_SEQ:
+            elif p.attn != "sdpa":
                 a = ops.attention(qkv, self.heads, False)
             else:
                 a = self._sdpa(qkv, B, L, W, False)
@@ -130,13 +132,10 @@ class BertLayer(Block):
         x = self.ln1(x + self.out(a))
         return self.ln2(x + self.fc2(F.gelu(self.fc1(x))))
 
+    WIDTH_CAP = 1024      # always: unlike clip.Block's cap (ops.fused_width_max()) it does not rise to 2048 with the head-dim mode
+
     def chain_supported(self, x):
-        from . import ops
-        B, L, W = x.shape
-        mlp = self.fc1.weight.shape[0]
-        return (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and W % 32 == 0 and mlp % 32 == 0 and W <= 1024
-                and ops.gemm_mode() == "f16x3" and ops.mlp_mode() == "block" and ops.ln_fold_enabled()
-                and ops.block_fused_supported(W, mlp, self.heads, L))
+        return self._plan(x).chain
 
     def forward_chain(self, x, carry, last=False, lengths=None):
         """x = LN_prev(y_prev) in fp32; carry = (y_prev as the tile-major operand, its rows' (rstd, -mean rstd), LN_prev): QKV

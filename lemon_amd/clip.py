@@ -122,13 +122,15 @@ class ClipConfig:
 
 
 def split_weight_cached(owner, name, w, ops, mode):
-    """The weight `w` ([n, k] view of a parameter of `owner`) as the split GEMM operand of `mode` ([n, 6k] bf16 / [n, 3k] fp16 of
-    w * wscale) and 1 / wscale, made once per weight version (inference: once) and kept on the module."""
+    """The weight `w` ([n, k] view of a parameter of `owner`) as the GEMM operand of `mode` -- the split rows [n, 6k] bf16 / [n, 3k]
+    fp16, or with 'tiled' the tile-major fp16 operand of lemon_linear_f16x3t, of w * wscale -- and 1 / wscale, made once per weight
+    version (inference: once) and kept on the module."""
     cache = owner.__dict__.setdefault("_split_cache", {})
     hit = cache.get((name, mode))
     if hit is None or hit[0] != (w.data_ptr(), w._version):
-        wscale = ops.weight_scale_f16x3(w) if mode == "f16x3" else 1.0
-        hit = ((w.data_ptr(), w._version), ops.split_operand(w.detach(), mode, weight=True, wscale=wscale), 1.0 / wscale)
+        wscale = 1.0 if mode == "bf16x6" else ops.weight_scale_f16x3(w)
+        packed = ops.pack_weight_t(w.detach(), wscale) if mode == "tiled" else ops.split_operand(w.detach(), mode, weight=True, wscale=wscale)
+        hit = ((w.data_ptr(), w._version), packed, 1.0 / wscale)
         cache[(name, mode)] = hit
     return hit[1], hit[2]
 
@@ -155,21 +157,17 @@ class Block(nn.Module):
         FLOPs, all row-wise -- are then evaluated for the pooled rows only.  Same function of the input.
         carry: what forward_chain of the block in front left behind (x as the hand-written GEMM's operand + row statistics), or None."""
         B, L, W = x.shape
-        fused = x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-        if fused:
+        p = self._plan(x, rows is not None, carry is not None)
+        if p.qkv != "torch":
             # inference on the GPU: every GEMM of the block goes through lemon_linear_f32 (bias, QuickGELU
             # and the residual adds ride in the hipBLASLt epilogue), attention through lemon_attention_f32
             from . import ops
-            mode = ops.gemm_mode()
-            ops.select_attention_arithmetic(mode)
-            if W % 4 == 0 and W <= ops.fused_width_max() and mode != "f32":
-                return self._forward_split(x, causal, rows, ops, mode, carry)
+            ops.select_attention_arithmetic(p.mode)
+            if p.qkv != "f32":
+                return self._forward_split(x, causal, rows, ops, p, carry)
             ln = lambda m, t: ops.layer_norm(t, m.weight, m.bias, m.eps) if t.shape[-1] % 4 == 0 else m(t)
             qkv = ops.linear(ln(self.ln1, x), self.qkv.weight, self.qkv.bias)
-            if ops.attention_supported(W, self.heads, L):
-                a = ops.attention(qkv, self.heads, causal)
-            else:
-                a = self._sdpa(qkv, B, L, W, causal)
+            a = ops.attention(qkv, self.heads, causal) if p.attn == "f32" else self._sdpa(qkv, B, L, W, causal)
             if rows is not None:
                 a, x = a[rows].contiguous(), x[rows].contiguous()
             x = ops.linear(a, self.out.weight, self.out.bias, residual=x)
@@ -184,6 +182,14 @@ class Block(nn.Module):
         h = self.fc1(self.ln2(x))
         h = h * torch.sigmoid(1.702 * h) if self.act == "quick_gelu" else F.gelu(h)
         return x + self.fc2(h)
+
+    WIDTH_CAP = None      # the widest residual stream the split paths take; None: ops.fused_width_max()
+
+    def _plan(self, x, pooled=False, carry=False, **kw):
+        """ops.current_block_plan for the input x [B, L, W]"""
+        from . import ops
+        return ops.current_block_plan(ops.on_fused_path(x), x.shape[2], self.fc1.weight.shape[0], self.heads, x.shape[1], pooled, carry,
+                                      self.WIDTH_CAP, **kw)
 
     def _act_scale(self, ops):
         """(s, epilogue name): fc1 runs as act(s (x W^T + b)) and fc2 with alpha / s -- QuickGELU(z) = silu(1.702 z) / 1.702;
@@ -216,60 +222,44 @@ class Block(nn.Module):
 
     def _w_tiled(self, name, ops):
         """The layer's weight as the tile-major fp16 operand of lemon_linear_f16x3t and 1 / wscale, once per weight version."""
-        w = getattr(self, name).weight
-        cache = self.__dict__.setdefault("_split_cache", {})
-        hit = cache.get((name, "tiled"))
-        if hit is None or hit[0] != (w.data_ptr(), w._version):
-            wscale = ops.weight_scale_f16x3(w)
-            hit = ((w.data_ptr(), w._version), ops.pack_weight_t(w.detach(), wscale), 1.0 / wscale)
-            cache[(name, "tiled")] = hit
-        return hit[1], hit[2]
+        return split_weight_cached(self, name, getattr(self, name).weight, ops, "tiled")
 
-    def _forward_split(self, x, causal, rows, ops, mode, carry=None):
+    def _forward_split(self, x, causal, rows, ops, p, carry=None):
         """The fused inference path with the four GEMMs of the block (QKV, output projection, fc1, fc2) on the 16-bit matrix
         cores at fp32-equivalent accuracy (ops.linear_split: exact splits of both operands -- 3-way bf16, six cross products, or
         2-way fp16, three --, fp32 accumulate); LayerNorm and attention write the split operand directly, the MLP activations
-        get one split pass."""
+        get one split pass.  p: the block's plan (ops.block_plan) -- which of the GEMMs run in the hand-written kernel instead."""
         B, L, W = x.shape
-        mlp = self.fc1.weight.shape[0]
-        hand = mode == "f16x3" and rows is None and ops.mlp_mode()
-        if hand == "block" and ops.block_fused_supported(W, mlp, self.heads, L):
-            # QKV and the output projection in the hand-written GEMM as well (LEMON_MLP=block, the default: see ops.mlp_mode):
-            # LayerNorm and attention write its tile-major operands
-            m = B * L
+        mlp, mode, m = self.fc1.weight.shape[0], p.mode, B * L
+        if p.qkv == "tiled_ln":
+            # (the pooled last block behind a chain: the block in front left its operand and statistics)
+            wq, aq, csq, bq = self._w_tiled_ln("qkv", self.ln1, ops, 1.0)
+            qkv = ops.linear_t_ln(carry[0], wq, m, 3 * W, W, bq, alpha=aq, out_shape=(B, L, 3 * W),
+                                  row_aff=ops.ln_finalize(carry[1], m, W, self.ln1.eps), colsum=csq)
+        elif p.qkv == "tiled":
             wq, aq = self._w_tiled("qkv", ops)
-            wo, ao = self._w_tiled("out", ops)
+            wo, ao = self._w_tiled("out", ops) if p.out == "tiled" else (None, None)     # (packed in front of the first launch)
             qkv = ops.linear_t(ops.layer_norm_t(x, self.ln1.weight, self.ln1.bias, self.ln1.eps), wq, m, 3 * W, W, self.qkv.bias,
                                alpha=aq, out_shape=(B, L, 3 * W))
-            x = ops.linear_t(ops.attention_t(qkv, self.heads, causal), wo, m, W, W, self.out.bias, residual=x, alpha=ao, out_shape=x.shape)
-            return self._mlp_hand(x, ops, W, mlp)
-        if rows is not None and mode == "f16x3" and ops.mlp_mode() == "block" and ops.block_fused_supported(W, mlp, self.heads, L):
-            # the pooled-row block still needs every token's keys and values: its QKV GEMM (all rows) in the hand-written kernel
-            # too, with the LayerNorm folded in when the block in front left its operand and statistics
-            m = B * L
-            if carry is not None and ops.ln_fold_enabled() and W % 32 == 0:
-                wq, aq, csq, bq = self._w_tiled_ln("qkv", self.ln1, ops, 1.0)
-                qkv = ops.linear_t_ln(carry[0], wq, m, 3 * W, W, bq, alpha=aq, out_shape=(B, L, 3 * W),
-                                      row_aff=ops.ln_finalize(carry[1], m, W, self.ln1.eps), colsum=csq)
-            else:
-                wq, aq = self._w_tiled("qkv", ops)
-                qkv = ops.linear_t(ops.layer_norm_t(x, self.ln1.weight, self.ln1.bias, self.ln1.eps), wq, m, 3 * W, W, self.qkv.bias,
-                                   alpha=aq, out_shape=(B, L, 3 * W))
         else:
             w, a_ = self._w_split("qkv", ops, mode)
             qkv = ops.linear_split(ops.layer_norm_split(x, self.ln1.weight, self.ln1.bias, self.ln1.eps, mode), w, self.qkv.bias, alpha=a_)
-        hip_attn = ops.attention_supported(W, self.heads, L)
-        if hip_attn and rows is None:
+        if p.out == "tiled":
+            # the output projection in the hand-written GEMM as well (LEMON_MLP=block, the default: see ops.mlp_mode): attention
+            # writes its tile-major operand
+            x = ops.linear_t(ops.attention_t(qkv, self.heads, causal), wo, m, W, W, self.out.bias, residual=x, alpha=ao, out_shape=x.shape)
+            return self._mlp_hand(x, ops, W, mlp)
+        if p.attn == "split":
             a6 = ops.attention_split(qkv, self.heads, causal, mode)      # the attention kernel stores the split operand itself
         else:
-            a = ops.attention(qkv, self.heads, causal) if hip_attn else self._sdpa(qkv, B, L, W, causal)
+            a = ops.attention(qkv, self.heads, causal) if p.attn == "f32" else self._sdpa(qkv, B, L, W, causal)
             if rows is not None:
                 a, x = a[rows].contiguous(), x[rows].contiguous()
             a6 = ops.split_operand(a, mode)
         w, a_ = self._w_split("out", ops, mode)
         x = ops.linear_split(a6, w, self.out.bias, residual=x, alpha=a_)
         s, act = self._act_scale(ops)
-        if hand in ("block", "fused") and ops.mlp_fused_supported(W, mlp):
+        if p.mlp == "tiled":
             return self._mlp_hand(x, ops, W, mlp)
         w, a_ = self._w_split("fc1", ops, mode)
         h = ops.linear_split(ops.layer_norm_split(x, self.ln2.weight, self.ln2.bias, self.ln2.eps, mode), w,
@@ -301,16 +291,9 @@ class Block(nn.Module):
         made here with one pass), and with `emit` this block's fc2 leaves the same for the next one."""
         from . import ops
         mlp = self.fc1.weight.shape[0]
-        if x is None:            # (full lean form: the block in front left its result as the operand only; it checked `ok`)
-            B, L, W = carry[2]
-            ok = True
-        else:
-            B, L, W = x.shape
-            ok = (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and W % 32 == 0 and mlp % 32 == 0
-                  and W <= ops.fused_width_max()
-                  and ops.gemm_mode() == "f16x3" and ops.mlp_mode() == "block" and ops.ln_fold_enabled()
-                  and ops.block_fused_supported(W, mlp, self.heads, L))
-        if not ok:
+        # (x None, the full lean form: the block in front left its result as the operand only, and the plan both share)
+        (B, L, W), p = (carry[2], carry[3]) if x is None else (x.shape, self._plan(x))
+        if not p.chain:
             return self(x, causal), None
         ops.select_attention_arithmetic("f16x3")
         m = B * L
@@ -324,7 +307,7 @@ class Block(nn.Module):
         # inside the chain the residual stream exists as the GEMMs' operand only (ops.chain_operand_residual): the next GEMM reads
         # it as its operand, the one behind it as its residual; fp32 is written where the caller asks for it (fp32_out: the last
         # chained block)
-        lean = ops.chain_operand_residual()
+        lean = p.lean
         res = dict(residual_t=xt) if lean == 2 else dict(residual=x)
         x, xt, st = ops.linear_t_chain(ops.attention_t(qkv, self.heads, causal), wo, m, W, W, self.out.bias, alpha=ao,
                                        out_shape=(B, L, W), fp32_out=not lean, **res)
@@ -335,7 +318,7 @@ class Block(nn.Module):
         w2, a2 = self._w_tiled("fc2", ops)
         res = dict(residual_t=xt) if lean else dict(residual=x)
         x, xt, st = ops.linear_t_chain(ht, w2, m, W, mlp, self.fc2.bias, alpha=a2 / s, out_shape=(B, L, W), fp32_out=fp32_out or lean < 2, **res)
-        return x, ((xt, st, (B, L, W)) if emit else None)
+        return x, ((xt, st, (B, L, W), p) if emit else None)
 
     def _sdpa(self, qkv, B, L, W, causal):
         q, k, v = qkv.view(B, L, 3, self.heads, W // self.heads).permute(2, 0, 3, 1, 4)
@@ -383,14 +366,8 @@ class VisionTower(nn.Module):
             from . import ops
             po = pixel_values
             w = self.patch.weight.reshape(self.patch.weight.shape[0], -1)
-            cache = self.__dict__.setdefault("_split_cache", {})
-            hit = cache.get(("patch", "tiled"))
-            if hit is None or hit[0] != (w.data_ptr(), self.patch.weight._version):
-                wscale = ops.weight_scale_f16x3(w)
-                hit = ((w.data_ptr(), self.patch.weight._version), ops.pack_weight_t(w.detach().contiguous(), wscale), 1.0 / wscale)
-                cache[("patch", "tiled")] = hit
-            x = ops.linear_t(po.at, hit[1], po.batch * po.n_patches, w.shape[0], po.k, alpha=hit[2],
-                             out_shape=(po.batch, po.n_patches, w.shape[0]))
+            wt, a_ = split_weight_cached(self, "patch", w, ops, "tiled")
+            x = ops.linear_t(po.at, wt, po.batch * po.n_patches, w.shape[0], po.k, alpha=a_, out_shape=(po.batch, po.n_patches, w.shape[0]))
         elif pixel_values.dim() == 3:
             # patch-major input [B, nP, 3*P*P] (lemon_preprocess_u8 with patch=P): the stride == kernel
             # convolution is a plain GEMM with the flattened filter bank, no im2col and no MIOpen

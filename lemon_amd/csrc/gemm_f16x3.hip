@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "split3.hpp"
+#include "gemm_f16x3_plan.hpp"
 
 using namespace lemon_split;
 
@@ -795,6 +796,18 @@ __global__ __launch_bounds__(256) void k_ln_finalize(const float *__restrict__ p
 }
 
 // ---- host-side state of the launcher ----
+namespace plan = lemon_gemm_plan;
+static_assert(plan::TM == TM && plan::TN == TN && plan::GM == GM && plan::ACT_GELU == LEMON_ACT_GELU, "gemm_f16x3_plan.hpp mirrors these");
+// the instantiations, indexed by plan::Form (the order of plan::FACTS): the one place that names them
+typedef void (*GemmKernel)(GemmParams);
+static constexpr GemmKernel KERNELS[] = {
+    k_gemm_f16x3t16<2, true, false>, k_gemm_f16x3t16<1, true, false>, k_gemm_f16x3t16<0, true, false>,
+    k_gemm_f16x3t16<0, false, true>, k_gemm_f16x3t16<0, false, true, 1>, k_gemm_f16x3t16<0, false, true, 2>, k_gemm_f16x3t16<0, false, true, 3>,
+    k_gemm_f16x3t16<2, false, false>, k_gemm_f16x3t16<1, false, false>, k_gemm_f16x3t16<0, false, false>,
+    k_gemm_f16x3t<2>, k_gemm_f16x3t<1>, k_gemm_f16x3t<0>,
+};
+static_assert(sizeof(KERNELS) / sizeof(KERNELS[0]) == plan::N_FORMS, "one kernel per plan::Form");
+thread_local int t_last_form = -1;     // the form this thread launched last (lemon_linear_f16x3t_last_kernel)
 constexpr int MAX_DEVICES = 64;
 std::mutex g_attr_mu;
 bool g_attr_set[MAX_DEVICES] = {};
@@ -865,7 +878,66 @@ extern "C" int lemon_unpack_act_f16x3t(const uint16_t *at_dev, int64_t rows, int
 static int linear_f16x3t_impl(const uint16_t *at_dev, const uint16_t *wt_dev, const float *bias_dev, const float *residual_dev,
                               int64_t m, int n, int k, float alpha, int act, int out_operand, void *out_dev,
                               const float *row_aff_dev, const float *colsum_dev, uint16_t *emit_t_dev, float *emit_stats_dev, void *stream_,
-                              const uint16_t *residual_t_dev = nullptr);
+                              const uint16_t *residual_t_dev = nullptr) {
+    LEMON_REQUIRE(m >= 0 && n > 0 && k > 0 && n % TN == 0 && k % 16 == 0, "m >= 0, n a multiple of 256, k a multiple of 16");
+    if (m == 0) return LEMON_OK;
+    LEMON_REQUIRE(at_dev && wt_dev && (out_dev || emit_t_dev), "null pointer");
+    LEMON_REQUIRE(((((uintptr_t)row_aff_dev) | ((uintptr_t)colsum_dev) | ((uintptr_t)emit_t_dev) | ((uintptr_t)emit_stats_dev)) & 15) == 0, "16-byte aligned pointers");
+    LEMON_REQUIRE(((((uintptr_t)at_dev) | ((uintptr_t)wt_dev) | ((uintptr_t)out_dev) | ((uintptr_t)bias_dev) | ((uintptr_t)residual_dev)) & 15) == 0,
+                  "16-byte aligned pointers");
+    LEMON_REQUIRE((act == LEMON_ACT_NONE && !out_operand) || ((act == LEMON_ACT_SILU || act == LEMON_ACT_GELU) && out_operand && !residual_dev),
+                  "supported forms: act none -> fp32 [m, n] (+ residual); act SiLU / GELU -> tile-major operand (no residual)");
+    LEMON_REQUIRE((m + TM - 1) / TM < ((int64_t)1 << 24), "m < 2^31");
+    GemmParams p;
+    p.at = reinterpret_cast<const char *>(at_dev); p.wt = reinterpret_cast<const char *>(wt_dev);
+    p.bias = bias_dev; p.residual = residual_dev; p.out = out_dev;
+    p.row_aff = reinterpret_cast<const float2 *>(row_aff_dev); p.colsum = colsum_dev;
+    p.emit_t = reinterpret_cast<unsigned short *>(emit_t_dev); p.emit_stats = emit_stats_dev;
+    p.residual_t = reinterpret_cast<const unsigned short *>(residual_t_dev);
+    p.m = m; p.n = n; p.alpha = alpha;
+    walk_override();
+    const plan::Walk w = plan::plan_walk(m, n, k, g_gm, g_gn);
+    LEMON_REQUIRE(w.vblocks < ((int64_t)1 << 31), "grid size");
+    p.ks = w.ks; p.m_tiles = w.m_tiles; p.n_tiles = w.n_tiles; p.gm = w.gm; p.gn = w.gn; p.vblocks = (int)w.vblocks;
+#ifdef LEMON_GEMM_PHASES
+    p.dbg = g_phase_dbg;
+#endif
+    const size_t lds = (size_t)NB * STAGE;
+    // the 72 KB of dynamic LDS need the attribute on every DEVICE this process launches on (it is per device, not per process)
+    int dev = 0;
+    LEMON_HIP_CHECK(hipGetDevice(&dev));
+    LEMON_REQUIRE(dev >= 0 && dev < MAX_DEVICES, "device index");
+    {
+        std::lock_guard<std::mutex> lock(g_attr_mu);
+        if (!g_attr_set[dev]) {
+            for (const GemmKernel kern : KERNELS)
+                LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            g_attr_set[dev] = true;
+        }
+    }
+    const plan::Form form = plan::select_form(mfma_shape(), w.ks, act, out_operand != 0, row_aff_dev != nullptr, emit_t_dev != nullptr,
+                                              out_dev != nullptr, residual_t_dev != nullptr);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_attr_mu);
+        if (g_prof.on) {
+            while (g_prof.used + 2 > g_prof.ev.size()) {       // every launch of a profiled region is bracketed
+                hipEvent_t e = nullptr;
+                LEMON_HIP_CHECK(hipEventCreate(&e));
+                g_prof.ev.push_back(e);
+            }
+            ev0 = g_prof.ev[g_prof.used]; ev1 = g_prof.ev[g_prof.used + 1];
+            g_prof.used += 2;
+            g_prof.flops.push_back(2.0 * (double)m * (double)n * 3.0 * (double)k);      // the kernel's own arithmetic: three fp16 products
+        }
+    }
+    if (ev0) LEMON_HIP_CHECK(hipEventRecord(ev0, (hipStream_t)stream_));
+    hipLaunchKernelGGL(KERNELS[form], dim3((unsigned)w.vblocks), dim3(256), lds, (hipStream_t)stream_, p);
+    t_last_form = form;
+    LEMON_HIP_CHECK(hipGetLastError());
+    if (ev1) LEMON_HIP_CHECK(hipEventRecord(ev1, (hipStream_t)stream_));
+    return LEMON_OK;
+}
 
 extern "C" int lemon_linear_f16x3t(const uint16_t *at_dev, const uint16_t *wt_dev, const float *bias_dev, const float *residual_dev,
                                    int64_t m, int n, int k, float alpha, int act, int out_operand, void *out_dev, void *stream_) {
@@ -898,109 +970,8 @@ extern "C" int lemon_linear_f16x3t_chain(const uint16_t *at_dev, const uint16_t 
                               emit_stats_dev, stream_, residual_t_dev);
 }
 
-static int linear_f16x3t_impl(const uint16_t *at_dev, const uint16_t *wt_dev, const float *bias_dev, const float *residual_dev,
-                              int64_t m, int n, int k, float alpha, int act, int out_operand, void *out_dev,
-                              const float *row_aff_dev, const float *colsum_dev, uint16_t *emit_t_dev, float *emit_stats_dev, void *stream_,
-                              const uint16_t *residual_t_dev) {
-    LEMON_REQUIRE(m >= 0 && n > 0 && k > 0 && n % TN == 0 && k % 16 == 0, "m >= 0, n a multiple of 256, k a multiple of 16");
-    if (m == 0) return LEMON_OK;
-    LEMON_REQUIRE(at_dev && wt_dev && (out_dev || emit_t_dev), "null pointer");
-    LEMON_REQUIRE(((((uintptr_t)row_aff_dev) | ((uintptr_t)colsum_dev) | ((uintptr_t)emit_t_dev) | ((uintptr_t)emit_stats_dev)) & 15) == 0, "16-byte aligned pointers");
-    LEMON_REQUIRE(((((uintptr_t)at_dev) | ((uintptr_t)wt_dev) | ((uintptr_t)out_dev) | ((uintptr_t)bias_dev) | ((uintptr_t)residual_dev)) & 15) == 0,
-                  "16-byte aligned pointers");
-    LEMON_REQUIRE((act == LEMON_ACT_NONE && !out_operand) || ((act == LEMON_ACT_SILU || act == LEMON_ACT_GELU) && out_operand && !residual_dev),
-                  "supported forms: act none -> fp32 [m, n] (+ residual); act SiLU / GELU -> tile-major operand (no residual)");
-    LEMON_REQUIRE((m + TM - 1) / TM < ((int64_t)1 << 24), "m < 2^31");
-    GemmParams p;
-    p.at = reinterpret_cast<const char *>(at_dev); p.wt = reinterpret_cast<const char *>(wt_dev);
-    p.bias = bias_dev; p.residual = residual_dev; p.out = out_dev;
-    p.row_aff = reinterpret_cast<const float2 *>(row_aff_dev); p.colsum = colsum_dev;
-    p.emit_t = reinterpret_cast<unsigned short *>(emit_t_dev); p.emit_stats = emit_stats_dev;
-    p.residual_t = reinterpret_cast<const unsigned short *>(residual_t_dev);
-    p.m = m; p.n = n; p.ks = k / 16; p.m_tiles = (int)((m + TM - 1) / TM); p.n_tiles = n / TN; p.alpha = alpha;
-    // super-block of the tile walk: gn = the largest divisor of the n-tile count up to 4 (a gn that does not divide it leaves
-    // every other XCD with half-empty super-blocks: +25 % time measured), gm so that an XCD's 64 resident workgroups cover one
-    // or two super-blocks.  Measured against 32 x 1 at the tower shapes (tools/micro/gemm_ab.hip walk): -1 ... -3 %; the
-    // operand re-fetches this saves (FETCH_SIZE 5.0 GB for fc1 at 32 x 1: the activations once per weight tile column) are
-    // served by the Infinity Cache either way.  LEMON_GEMM_WALK=gm,gn overrides.
-    walk_override();
-    if (g_gm > 0) { p.gm = g_gm; p.gn = g_gn > 0 ? g_gn : 1; }
-    else {
-        p.gn = p.n_tiles % 4 == 0 ? 4 : p.n_tiles % 3 == 0 ? 3 : p.n_tiles % 2 == 0 ? 2 : 1;
-        p.gm = p.gn == 1 ? GM : p.gn == 3 ? 8 : 16;
-    }
-    if (p.gn > p.n_tiles) p.gn = p.n_tiles;
-    const int64_t blocks = (int64_t)((p.m_tiles + p.gm - 1) / p.gm) * ((p.n_tiles + p.gn - 1) / p.gn);
-    int64_t grid = ((blocks + 7) / 8) * p.gm * p.gn * 8;
-    LEMON_REQUIRE(grid < ((int64_t)1 << 31), "grid size");
-    p.vblocks = (int)grid;
-#ifdef LEMON_GEMM_PHASES
-    p.dbg = g_phase_dbg;
-#endif
-    const size_t lds = (size_t)NB * STAGE;
-    // the 72 KB of dynamic LDS need the attribute on every DEVICE this process launches on (it is per device, not per process)
-    int dev = 0;
-    LEMON_HIP_CHECK(hipGetDevice(&dev));
-    LEMON_REQUIRE(dev >= 0 && dev < MAX_DEVICES, "device index");
-    {
-        std::lock_guard<std::mutex> lock(g_attr_mu);
-        if (!g_attr_set[dev]) {
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<0, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<1, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<0, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<1, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<0, false, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<0, false, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<0, false, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<2, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_f16x3t16<2, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            g_attr_set[dev] = true;
-        }
-    }
-    // matrix instruction: 16x16x32 where the k extent allows whole k32 steps (every tower width does), else 32x32x16;
-    // LEMON_GEMM_MFMA=32 forces the latter (A/B runs)
-    const bool mf16 = mfma_shape() == 16 && p.ks % 2 == 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_attr_mu);
-        if (g_prof.on) {
-            while (g_prof.used + 2 > g_prof.ev.size()) {       // every launch of a profiled region is bracketed
-                hipEvent_t e = nullptr;
-                LEMON_HIP_CHECK(hipEventCreate(&e));
-                g_prof.ev.push_back(e);
-            }
-            ev0 = g_prof.ev[g_prof.used]; ev1 = g_prof.ev[g_prof.used + 1];
-            g_prof.used += 2;
-            g_prof.flops.push_back(2.0 * (double)m * (double)n * 3.0 * (double)k);      // the kernel's own arithmetic: three fp16 products
-        }
-    }
-    if (ev0) LEMON_HIP_CHECK(hipEventRecord(ev0, (hipStream_t)stream_));
-    const bool fold = row_aff_dev != nullptr, emit = emit_t_dev != nullptr;
-    const bool gelu = act == LEMON_ACT_GELU;
-    if (fold || emit) {
-        if (fold && out_operand && gelu) hipLaunchKernelGGL((k_gemm_f16x3t16<2, true, false>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else if (fold && out_operand) hipLaunchKernelGGL((k_gemm_f16x3t16<1, true, false>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else if (fold) hipLaunchKernelGGL((k_gemm_f16x3t16<0, true, false>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else if (!residual_t_dev && out_dev) hipLaunchKernelGGL((k_gemm_f16x3t16<0, false, true>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else if (!residual_t_dev) hipLaunchKernelGGL((k_gemm_f16x3t16<0, false, true, 1>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else if (out_dev) hipLaunchKernelGGL((k_gemm_f16x3t16<0, false, true, 2>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else hipLaunchKernelGGL((k_gemm_f16x3t16<0, false, true, 3>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-    } else if (mf16) {
-        if (out_operand && gelu) hipLaunchKernelGGL((k_gemm_f16x3t16<2, false, false>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else if (out_operand) hipLaunchKernelGGL((k_gemm_f16x3t16<1, false, false>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else hipLaunchKernelGGL((k_gemm_f16x3t16<0, false, false>), dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-    } else {
-        if (out_operand && gelu) hipLaunchKernelGGL(k_gemm_f16x3t<2>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else if (out_operand) hipLaunchKernelGGL(k_gemm_f16x3t<1>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-        else hipLaunchKernelGGL(k_gemm_f16x3t<0>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream_, p);
-    }
-    LEMON_HIP_CHECK(hipGetLastError());
-    if (ev1) LEMON_HIP_CHECK(hipEventRecord(ev1, (hipStream_t)stream_));
-    return LEMON_OK;
+extern "C" const char *lemon_linear_f16x3t_last_kernel(void) {
+    return t_last_form < 0 ? "" : plan::FACTS[t_last_form].name;
 }
 
 extern "C" int lemon_linear_f16x3t_set_mfma(int shape) {

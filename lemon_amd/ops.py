@@ -8,6 +8,7 @@
 Inputs are torch CUDA tensors (device memory is torch's job; the arithmetic is the HIP
 library's).  Host inputs are rejected loudly: there is no CPU path in the product.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -45,6 +46,12 @@ def dev_f32(t, name="tensor"):
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _call(name, device, *args):
+    """lib.<name>(*args, stream) with `device` current; raises LemonHipError on a non-zero status"""
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.load(), name)(*args, stream_ptr(device)), name)
 
 
 def normalize_vectors(vectors):
@@ -176,31 +183,28 @@ def _ensure_linear_tuned(lib, device):
             lib.lemon_linear_load_tuned(path.encode())
 
 
-def linear(x, weight, bias=None, residual=None, act=None, alpha=1.0):
-    """y = act(alpha * x @ weight.T + bias) (+ residual) in ONE hipBLASLt GEMM (SiLU / residual add ride
-    in the epilogue; 'gelu', the exact one, is an in-place pass behind it).  x [..., k] float32 CUDA, weight [n, k]; act in
-    (None, 'silu', 'gelu')."""
-    assert x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32
-    x = x.contiguous()
-    weight = weight.contiguous()
-    k = x.shape[-1]
-    n = weight.shape[0]
-    assert weight.shape[1] == k
-    m = x.numel() // k
+def _linear_rows(name, x, weight, bias, residual, act, alpha):
+    """The body linear and linear_split share: x [..., k] . weight [n, k]^T through the library GEMM entry `name` -> float32 [..., n]."""
+    x, weight = x.contiguous(), weight.contiguous()
+    k, n = x.shape[-1], weight.shape[0]
     y = torch.empty(x.shape[:-1] + (n,), dtype=torch.float32, device=x.device)
     if residual is not None:
         assert residual.shape == y.shape and residual.dtype == torch.float32
         residual = residual.contiguous()
     if bias is not None:
         bias = bias.contiguous()
-    lib = _lib.load()
-    _ensure_linear_tuned(lib, x.device)
-    code = _ACT_CODE[act]
-    with torch.cuda.device(x.device):
-        _lib.check(lib.lemon_linear_f32(ptr(x), ptr(weight), ptr(bias) if bias is not None else None,
-                                        ptr(residual) if residual is not None else None, m, n, k, float(alpha), code, ptr(y),
-                                        stream_ptr(x.device)), "lemon_linear_f32")
+    _ensure_linear_tuned(_lib.load(), x.device)
+    _call(name, x.device, ptr(x), ptr(weight), ptr(bias), ptr(residual), x.numel() // k, n, k, float(alpha), _ACT_CODE[act], ptr(y))
     return y
+
+
+def linear(x, weight, bias=None, residual=None, act=None, alpha=1.0):
+    """y = act(alpha * x @ weight.T + bias) (+ residual) in ONE hipBLASLt GEMM (SiLU / residual add ride
+    in the epilogue; 'gelu', the exact one, is an in-place pass behind it).  x [..., k] float32 CUDA, weight [n, k]; act in
+    (None, 'silu', 'gelu')."""
+    assert x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32
+    assert weight.shape[1] == x.shape[-1]
+    return _linear_rows("lemon_linear_f32", x, weight, bias, residual, act, alpha)
 
 
 # ---- fp32-equivalent GEMMs on the 16-bit matrix cores (split operands: lemon_linear_bf16x6 / lemon_linear_f16x3) -----------
@@ -282,13 +286,10 @@ def split_operand(x, mode="bf16x6", weight=False, wscale=1.0):
     x = x.contiguous()
     k = x.shape[-1]
     y = torch.empty(x.shape[:-1] + (seg * k,), dtype=dtype, device=x.device)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        if mode == "bf16x6":
-            _lib.check(lib.lemon_split3_f32(ptr(x), x.numel() // k, k, int(bool(weight)), ptr(y), stream_ptr(x.device)), "lemon_split3_f32")
-        else:
-            _lib.check(lib.lemon_split_f16x3(ptr(x), x.numel() // k, k, int(bool(weight)), float(wscale), ptr(y), stream_ptr(x.device)),
-                       "lemon_split_f16x3")
+    if mode == "bf16x6":
+        _call("lemon_split3_f32", x.device, ptr(x), x.numel() // k, k, int(bool(weight)), ptr(y))
+    else:
+        _call("lemon_split_f16x3", x.device, ptr(x), x.numel() // k, k, int(bool(weight)), float(wscale), ptr(y))
     return y
 
 
@@ -320,23 +321,7 @@ def linear_split(xs, ws, bias=None, residual=None, act=None, alpha=1.0):
     """y = act(alpha * xs . ws^T + bias) (+ residual), float32, from split operands of one scheme (the dtype says which):
     bf16 [..., 6k] x [n, 6k] or fp16 [..., 3k] x [n, 3k].  f16x3: the caller folds 1 / wscale into alpha."""
     assert xs.is_cuda and xs.dtype == ws.dtype and xs.dtype in (torch.bfloat16, torch.float16) and xs.shape[-1] == ws.shape[1]
-    xs, ws = xs.contiguous(), ws.contiguous()
-    ks, n = xs.shape[-1], ws.shape[0]
-    m = xs.numel() // ks
-    y = torch.empty(xs.shape[:-1] + (n,), dtype=torch.float32, device=xs.device)
-    if residual is not None:
-        assert residual.shape == y.shape and residual.dtype == torch.float32
-        residual = residual.contiguous()
-    if bias is not None:
-        bias = bias.contiguous()
-    lib = _lib.load()
-    _ensure_linear_tuned(lib, xs.device)
-    code = _ACT_CODE[act]
-    fn, name = (lib.lemon_linear_bf16x6, "lemon_linear_bf16x6") if xs.dtype == torch.bfloat16 else (lib.lemon_linear_f16x3, "lemon_linear_f16x3")
-    with torch.cuda.device(xs.device):
-        _lib.check(fn(ptr(xs), ptr(ws), ptr(bias) if bias is not None else None, ptr(residual) if residual is not None else None,
-                      m, n, ks, float(alpha), code, ptr(y), stream_ptr(xs.device)), name)
-    return y
+    return _linear_rows("lemon_linear_bf16x6" if xs.dtype == torch.bfloat16 else "lemon_linear_f16x3", xs, ws, bias, residual, act, alpha)
 
 
 linear_split3 = linear_split
@@ -375,12 +360,16 @@ def set_attention_head_dims(mode):
     return int(prev)
 
 
-def attention_supported(width, heads, seq_len):
-    """Do the HIP attention kernels take this tower?  head_dim 64 always; multiples of 8 in 72 .. 128 with the head-dim mode on."""
+def _attention_takes(width, heads, seq_len, head_dims):
     if heads <= 0 or width % heads or seq_len > ATTENTION_MAX_SEQ:
         return False
     hd = width // heads
-    return hd == 64 or (attention_head_dims() != 0 and hd % 8 == 0 and 64 < hd <= 128)
+    return hd == 64 or (head_dims != 0 and hd % 8 == 0 and 64 < hd <= 128)
+
+
+def attention_supported(width, heads, seq_len):
+    """Do the HIP attention kernels take this tower?  head_dim 64 always; multiples of 8 in 72 .. 128 with the head-dim mode on."""
+    return _attention_takes(width, heads, seq_len, attention_head_dims())
 
 
 def fused_width_max():
@@ -394,6 +383,48 @@ def block_fused_supported(width, mlp, heads, seq_len):
     return mlp_fused_supported(width, mlp) and (3 * width) % 256 == 0 and attention_supported(width, heads, seq_len)
 
 
+# ---- which path a transformer block takes: the one place that decides (clip.Block and biomed.BertLayer branch on its fields) ----
+# mode: gemm_mode().  qkv: 'torch' (CPU / autograd; the rest is then 'torch' / 'sdpa' too), 'f32' (lemon_linear_f32), 'split' (the
+# library's split GEMMs), 'tiled' (the hand-written GEMM behind a LayerNorm kernel), 'tiled_ln' (the same, LayerNorm folded in).
+# attn: 'sdpa' (PyTorch), 'f32' (ops.attention), 'split' / 'tiled' (attention_split / attention_t write the operand).  out, mlp: the
+# output projection, fc1 + fc2 -- as qkv.  chain: forward_chain may chain the block, the residual stream at lean level `lean`.
+BlockPlan = collections.namedtuple("BlockPlan", "mode qkv attn out mlp chain lean")
+
+
+def block_plan(fused, width, mlp, heads, seq_len, pooled, carry, gemm_mode, mlp_mode, ln_fold, chain_res, head_dims, width_cap):
+    """Pure: the BlockPlan of one block.  fused: CUDA fp32 input without autograd; pooled: only some rows of the block's output are
+    wanted (the towers' last block); carry: the block in front left its operand and row statistics; width_cap: the widest
+    residual stream the caller's split paths take."""
+    if not fused:
+        return BlockPlan(gemm_mode, "torch", "sdpa", "torch", "torch", False, 0)
+    hip_attn = _attention_takes(width, heads, seq_len, head_dims)
+    if gemm_mode == "f32" or width % 4 or width > width_cap:
+        return BlockPlan(gemm_mode, "f32", "f32" if hip_attn else "sdpa", "f32", "f32", False, 0)
+    hand_mlp = gemm_mode == "f16x3" and mlp_fused_supported(width, mlp)      # (3 * width is then a multiple of 256 too)
+    hand = hand_mlp and mlp_mode == "block" and hip_attn
+    if hand and not pooled:
+        return BlockPlan(gemm_mode, "tiled", "tiled", "tiled", "tiled", bool(ln_fold), chain_res if ln_fold else 0)
+    # a pooled block still needs every token's keys and values: its QKV GEMM stays in the hand-written kernel, the rest runs for
+    # the pooled rows in the library
+    qkv = "split" if not hand else "tiled_ln" if carry and ln_fold else "tiled"
+    attn = "sdpa" if not hip_attn else "f32" if pooled else "split"
+    return BlockPlan(gemm_mode, qkv, attn, "split", "tiled" if hand_mlp and not pooled and mlp_mode != "lib" else "split", False, 0)
+
+
+def on_fused_path(x):
+    return x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
+
+
+def current_block_plan(fused, width, mlp, heads, seq_len, pooled=False, carry=False, width_cap=None, head_dims=None):
+    """block_plan under the knobs as they stand: LEMON_GEMM, LEMON_MLP, LEMON_LNFOLD, LEMON_CHAIN_RES and the thread's head-dim mode."""
+    if not fused:          # CPU / autograd: no knob is read and the library is not asked
+        return block_plan(False, width, mlp, heads, seq_len, pooled, carry, None, None, False, 0, 0, 0)
+    hd = attention_head_dims() if head_dims is None else head_dims
+    cap = (2048 if hd != 0 else 1024) if width_cap is None else width_cap           # (fused_width_max())
+    return block_plan(fused, width, mlp, heads, seq_len, pooled, carry, gemm_mode(), mlp_mode(), ln_fold_enabled(), chain_operand_residual(),
+                      hd, cap)
+
+
 def _tiled_rows(m):
     return (m + 127) // 128 * 128
 
@@ -403,10 +434,7 @@ def pack_weight_t(w, wscale):
     assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.shape[0] % 256 == 0 and w.shape[1] % 16 == 0
     w = w.contiguous()
     wt = torch.empty((w.shape[0] * w.shape[1] * 2,), dtype=torch.float16, device=w.device)
-    lib = _lib.load()
-    with torch.cuda.device(w.device):
-        _lib.check(lib.lemon_pack_weight_f16x3t(ptr(w), w.shape[0], w.shape[1], float(wscale), ptr(wt), stream_ptr(w.device)),
-                   "lemon_pack_weight_f16x3t")
+    _call("lemon_pack_weight_f16x3t", w.device, ptr(w), w.shape[0], w.shape[1], float(wscale), ptr(wt))
     return wt
 
 
@@ -417,37 +445,54 @@ def layer_norm_t(x, weight, bias, eps=1e-5):
     width = x.shape[-1]
     m = x.numel() // width
     at = torch.empty((_tiled_rows(m) * width * 2,), dtype=torch.float16, device=x.device)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.lemon_layernorm_f16x3t(ptr(x), ptr(weight.contiguous()), ptr(bias.contiguous()), float(eps), m, width, ptr(at),
-                                              stream_ptr(x.device)), "lemon_layernorm_f16x3t")
+    _call("lemon_layernorm_f16x3t", x.device, ptr(x), ptr(weight.contiguous()), ptr(bias.contiguous()), float(eps), m, width, ptr(at))
     return at
+
+
+def _linear_t(entry, at, wt, m, n, k, bias=None, residual=None, act=None, alpha=1.0, out_shape=None, row_aff=None, colsum=None, emit=False,
+              residual_t=None, fp32_out=True):
+    """What linear_t, linear_t_ln and linear_t_chain share (`entry`: '', '_ln', '_chain' of lemon_linear_f16x3t): validation, output
+    and emit allocation, contiguity, the call.  -> (out or None, emitted operand or None, its row-statistics partials or None)"""
+    assert at.is_cuda and at.dtype == torch.float16 and wt.dtype == torch.float16
+    assert at.numel() == _tiled_rows(m) * k * 2 and wt.numel() == n * k * 2 and (entry == "" or k % 32 == 0)
+    assert (row_aff is None) == (colsum is None) and not (emit and row_aff is not None)
+    assert residual is None or residual_t is None
+    dev = at.device
+    out = et = st = None
+    if act is not None:
+        assert act in ("silu", "gelu") and residual is None and not emit
+        out = torch.empty((_tiled_rows(m) * n * 2,), dtype=torch.float16, device=dev)
+    elif fp32_out:
+        out = torch.empty(out_shape if out_shape is not None else (m, n), dtype=torch.float32, device=dev)
+        assert out.numel() == m * n
+    if bias is not None:
+        bias = bias.contiguous()
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.numel() == m * n
+        residual = residual.contiguous()
+    if residual_t is not None:
+        assert residual_t.dtype == torch.float16 and residual_t.numel() == _tiled_rows(m) * n * 2
+    if row_aff is not None:
+        assert row_aff.dtype == torch.float32 and row_aff.numel() == 2 * m and colsum.dtype == torch.float32 and colsum.numel() == n
+        row_aff, colsum = row_aff.contiguous(), colsum.contiguous()
+    if emit:
+        et = torch.empty((_tiled_rows(m) * n * 2,), dtype=torch.float16, device=dev)
+        st = torch.empty((m, n // 128, 2), dtype=torch.float32, device=dev)
+    args = [ptr(at), ptr(wt), ptr(bias), ptr(residual)]
+    if entry == "_chain":
+        args += [ptr(residual_t), m, n, k, float(alpha), ptr(out), ptr(et), ptr(st)]
+    else:
+        args += [m, n, k, float(alpha), _ACT_CODE[act], int(act is not None), ptr(out)]
+        if entry == "_ln":
+            args += [ptr(row_aff), ptr(colsum), ptr(et), ptr(st)]
+    _call("lemon_linear_f16x3t" + entry, dev, *args)
+    return out, et, st
 
 
 def linear_t(at, wt, m, n, k, bias=None, residual=None, act=None, alpha=1.0, out_shape=None):
     """lemon_linear_f16x3t on tile-major operands: act None -> float32 [m, n] (view `out_shape`) = alpha x W^T + bias (+ residual);
     act 'silu' / 'gelu' -> the tile-major activation operand (k' = n) of act(alpha x W^T + bias)."""
-    assert at.is_cuda and at.dtype == torch.float16 and wt.dtype == torch.float16
-    assert at.numel() == _tiled_rows(m) * k * 2 and wt.numel() == n * k * 2
-    lib = _lib.load()
-    if bias is not None:
-        bias = bias.contiguous()
-    if act in ("silu", "gelu"):
-        assert residual is None
-        out = torch.empty((_tiled_rows(m) * n * 2,), dtype=torch.float16, device=at.device)
-    else:
-        assert act is None
-        out = torch.empty(out_shape if out_shape is not None else (m, n), dtype=torch.float32, device=at.device)
-        assert out.numel() == m * n
-        if residual is not None:
-            assert residual.dtype == torch.float32 and residual.numel() == m * n
-            residual = residual.contiguous()
-    with torch.cuda.device(at.device):
-        _lib.check(lib.lemon_linear_f16x3t(ptr(at), ptr(wt), ptr(bias) if bias is not None else None,
-                                           ptr(residual) if residual is not None else None, m, n, k, float(alpha),
-                                           _ACT_CODE[act], int(act is not None), ptr(out), stream_ptr(at.device)),
-                   "lemon_linear_f16x3t")
-    return out
+    return _linear_t("", at, wt, m, n, k, bias, residual, act, alpha, out_shape)[0]
 
 
 LN_FOLD_MAX_SHIFT = 8.0     # csrc/common.hpp LEMON_LN_FOLD_MAX_SHIFT: rows with |mean| rstd beyond it get a NaN row affine (-> fallback)
@@ -510,9 +555,7 @@ def rowstats_t(x, eps):
     m = x.numel() // width
     at = torch.empty((_tiled_rows(m) * width * 2,), dtype=torch.float16, device=x.device)
     aff = torch.empty((m, 2), dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.lemon_rowstats_f16x3t(ptr(x), float(eps), m, width, ptr(at), ptr(aff), stream_ptr(x.device)), "lemon_rowstats_f16x3t")
+    _call("lemon_rowstats_f16x3t", x.device, ptr(x), float(eps), m, width, ptr(at), ptr(aff))
     return at, aff
 
 
@@ -520,9 +563,7 @@ def ln_finalize(stats, m, width, eps):
     """[m, width / 128, 2] (mean, M2) partials of lemon_linear_f16x3t_ln's emit side -> (rstd, -mean rstd) [m, 2]."""
     assert stats.is_cuda and stats.dtype == torch.float32 and stats.numel() == m * (width // 128) * 2
     aff = torch.empty((m, 2), dtype=torch.float32, device=stats.device)
-    lib = _lib.load()
-    with torch.cuda.device(stats.device):
-        _lib.check(lib.lemon_ln_finalize(ptr(stats), m, width, float(eps), ptr(aff), stream_ptr(stats.device)), "lemon_ln_finalize")
+    _call("lemon_ln_finalize", stats.device, ptr(stats), m, width, float(eps), ptr(aff))
     return aff
 
 
@@ -530,37 +571,8 @@ def linear_t_ln(at, wt, m, n, k, bias=None, residual=None, act=None, alpha=1.0, 
     """linear_t with a folded LayerNorm on one side (lemon_linear_f16x3t_ln).  row_aff / colsum: this GEMM stands behind a LayerNorm
     whose input `at` holds (see fold_layernorm_weight / rowstats_t / ln_finalize).  emit: returns (out, out as the next GEMM's
     tile-major operand, its row-statistics partials [m, n / 128, 2])."""
-    assert at.is_cuda and at.dtype == torch.float16 and wt.dtype == torch.float16
-    assert at.numel() == _tiled_rows(m) * k * 2 and wt.numel() == n * k * 2 and k % 32 == 0
-    assert (row_aff is None) == (colsum is None) and not (emit and row_aff is not None)
-    lib = _lib.load()
-    if bias is not None:
-        bias = bias.contiguous()
-    if act in ("silu", "gelu"):
-        assert residual is None and not emit
-        out = torch.empty((_tiled_rows(m) * n * 2,), dtype=torch.float16, device=at.device)
-    else:
-        assert act is None
-        out = torch.empty(out_shape if out_shape is not None else (m, n), dtype=torch.float32, device=at.device)
-        assert out.numel() == m * n
-        if residual is not None:
-            assert residual.dtype == torch.float32 and residual.numel() == m * n
-            residual = residual.contiguous()
-    if row_aff is not None:
-        assert row_aff.dtype == torch.float32 and row_aff.numel() == 2 * m and colsum.dtype == torch.float32 and colsum.numel() == n
-        row_aff, colsum = row_aff.contiguous(), colsum.contiguous()
-    et = st = None
-    if emit:
-        et = torch.empty((_tiled_rows(m) * n * 2,), dtype=torch.float16, device=at.device)
-        st = torch.empty((m, n // 128, 2), dtype=torch.float32, device=at.device)
-    with torch.cuda.device(at.device):
-        _lib.check(lib.lemon_linear_f16x3t_ln(ptr(at), ptr(wt), ptr(bias) if bias is not None else None,
-                                              ptr(residual) if residual is not None else None, m, n, k, float(alpha),
-                                              _ACT_CODE[act], int(act is not None), ptr(out),
-                                              ptr(row_aff) if row_aff is not None else None, ptr(colsum) if colsum is not None else None,
-                                              ptr(et) if emit else None, ptr(st) if emit else None, stream_ptr(at.device)),
-                   "lemon_linear_f16x3t_ln")
-    return (out, et, st) if emit else out
+    res = _linear_t("_ln", at, wt, m, n, k, bias, residual, act, alpha, out_shape, row_aff, colsum, emit)
+    return res if emit else res[0]
 
 
 def chain_operand_residual():
@@ -580,30 +592,7 @@ def linear_t_chain(at, wt, m, n, k, bias=None, residual=None, residual_t=None, a
     """lemon_linear_f16x3t_chain: alpha x W^T + bias + residual -> (fp32 [m, n] or None, the same as the next GEMM's tile-major
     operand, its row-statistics partials [m, n / 128, 2]); the residual is fp32 [m, n] (`residual`) or a tile-major operand
     (`residual_t`)."""
-    assert at.is_cuda and at.dtype == torch.float16 and wt.dtype == torch.float16
-    assert at.numel() == _tiled_rows(m) * k * 2 and wt.numel() == n * k * 2 and k % 32 == 0
-    assert residual is None or residual_t is None
-    lib = _lib.load()
-    if bias is not None:
-        bias = bias.contiguous()
-    out = None
-    if fp32_out:
-        out = torch.empty(out_shape if out_shape is not None else (m, n), dtype=torch.float32, device=at.device)
-        assert out.numel() == m * n
-    if residual is not None:
-        assert residual.dtype == torch.float32 and residual.numel() == m * n
-        residual = residual.contiguous()
-    if residual_t is not None:
-        assert residual_t.dtype == torch.float16 and residual_t.numel() == _tiled_rows(m) * n * 2
-    et = torch.empty((_tiled_rows(m) * n * 2,), dtype=torch.float16, device=at.device)
-    st = torch.empty((m, n // 128, 2), dtype=torch.float32, device=at.device)
-    with torch.cuda.device(at.device):
-        _lib.check(lib.lemon_linear_f16x3t_chain(ptr(at), ptr(wt), ptr(bias) if bias is not None else None,
-                                                 ptr(residual) if residual is not None else None,
-                                                 ptr(residual_t) if residual_t is not None else None, m, n, k, float(alpha),
-                                                 ptr(out) if out is not None else None, ptr(et), ptr(st), stream_ptr(at.device)),
-                   "lemon_linear_f16x3t_chain")
-    return out, et, st
+    return _linear_t("_chain", at, wt, m, n, k, bias, residual, None, alpha, out_shape, emit=True, residual_t=residual_t, fp32_out=fp32_out)
 
 
 def gemm_profiling(on):
@@ -672,9 +661,7 @@ def attention_t(qkv, heads, causal=False, lengths=None):
 def unpack_act_t(at, m, k):
     """tile-major activation operand -> float32 [m, k] (hi + lo 2^-11)."""
     y = torch.empty((m, k), dtype=torch.float32, device=at.device)
-    lib = _lib.load()
-    with torch.cuda.device(at.device):
-        _lib.check(lib.lemon_unpack_act_f16x3t(ptr(at), m, k, ptr(y), stream_ptr(at.device)), "lemon_unpack_act_f16x3t")
+    _call("lemon_unpack_act_f16x3t", at.device, ptr(at), m, k, ptr(y))
     return y
 
 
@@ -684,10 +671,7 @@ def layer_norm(x, weight, bias, eps=1e-5):
     x = x.contiguous()
     width = x.shape[-1]
     y = torch.empty_like(x)
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.lemon_layernorm_f32(ptr(x), ptr(weight.contiguous()), ptr(bias.contiguous()), float(eps),
-                                           x.numel() // width, width, ptr(y), stream_ptr(x.device)), "lemon_layernorm_f32")
+    _call("lemon_layernorm_f32", x.device, ptr(x), ptr(weight.contiguous()), ptr(bias.contiguous()), float(eps), x.numel() // width, width, ptr(y))
     return y
 
 
@@ -698,12 +682,8 @@ def vision_tokens_ln(patches, cls, pos, ln_weight, ln_bias, eps=1e-5):
     patches = patches.contiguous()
     B, nP, W = patches.shape
     y = torch.empty((B, nP + 1, W), dtype=torch.float32, device=patches.device)
-    lib = _lib.load()
-    with torch.cuda.device(patches.device):
-        _lib.check(lib.lemon_vision_tokens_ln(ptr(patches), ptr(cls.contiguous()), ptr(pos.contiguous()),
-                                              ptr(ln_weight.contiguous()) if ln_weight is not None else None,
-                                              ptr(ln_bias.contiguous()) if ln_bias is not None else None, float(eps), B, nP + 1, W, ptr(y),
-                                              stream_ptr(patches.device)), "lemon_vision_tokens_ln")
+    ln = [ptr(t.contiguous()) if t is not None else None for t in (ln_weight, ln_bias)]
+    _call("lemon_vision_tokens_ln", patches.device, ptr(patches), ptr(cls.contiguous()), ptr(pos.contiguous()), *ln, float(eps), B, nP + 1, W, ptr(y))
     return y
 
 
@@ -712,11 +692,8 @@ def text_tokens(input_ids, seq_len, tok_weight, pos):
     assert input_ids.is_cuda and input_ids.dtype == torch.int64 and input_ids.dim() == 2 and input_ids.stride(1) == 1
     B, W = input_ids.shape[0], tok_weight.shape[1]
     y = torch.empty((B, seq_len, W), dtype=torch.float32, device=input_ids.device)
-    lib = _lib.load()
-    with torch.cuda.device(input_ids.device):
-        _lib.check(lib.lemon_text_tokens(ptr(input_ids), input_ids.stride(0), ptr(tok_weight.contiguous()), ptr(pos.contiguous()), B,
-                                         int(seq_len), W, tok_weight.shape[0], ptr(y), stream_ptr(input_ids.device)),
-                   "lemon_text_tokens")
+    _call("lemon_text_tokens", input_ids.device, ptr(input_ids), input_ids.stride(0), ptr(tok_weight.contiguous()), ptr(pos.contiguous()), B,
+          int(seq_len), W, tok_weight.shape[0], ptr(y))
     return y
 
 
@@ -774,7 +751,6 @@ def attention_split(qkv, heads, causal=False, mode="bf16x6", lengths=None):
 
 def attention_split3(qkv, heads, causal=False):
     return attention_split(qkv, heads, causal, "bf16x6")
-
 
 
 def paired_distance(metric, a, b):

@@ -37,7 +37,7 @@ TM = 128                      # rows of an activation tile (split3.hpp TILE_A_RO
 FOLD_MAX_SHIFT = 8.0          # common.hpp LEMON_LN_FOLD_MAX_SHIFT
 EPS = 1e-5
 
-# The 13 instantiations the dispatcher launches (linear_f16x3t_impl, gemm_f16x3.hip:982-999) and the ABI arguments that reach
+# The 13 instantiations the dispatcher launches (select_form and FACTS of csrc/gemm_f16x3_plan.hpp) and the ABI arguments that reach
 # each: `abi` plain = lemon_linear_f16x3t, ln = lemon_linear_f16x3t_ln, chain = lemon_linear_f16x3t_chain; `fold` passes
 # row_aff + colsum; `emit` passes emit_t + emit_stats; `out` whether out_dev is non-null; `res_t` the residual as a tile-major
 # operand; `mfma` the matrix shape the plain forms are pinned to (lemon_linear_f16x3t_set_mfma: the 32x32 forms are reached
@@ -328,6 +328,7 @@ def test_gemm_form_against_float64(hip, form, m, n, k, bias, res):
     spec = FORMS[form]
     inp = _inputs(form, m, n, k, bias, res, seed=1000 * form + 7 * m + n + k)
     outs = _launch(form, m, n, k, inp)
+    assert _lib().load().lemon_linear_f16x3t_last_kernel().decode("ascii") == spec["kernel"]      # the form ran the kernel it names
     for name, (buf, nw) in outs.items():
         assert _tail_intact(buf, nw), f"form {form} {spec['kernel']}: write past the end of `{name}`"
     u, S, far = _reference(form, m, n, k, inp)
@@ -368,9 +369,18 @@ def test_gemm_form_against_float64(hip, form, m, n, k, bias, res):
     print(f"[gemm forms] {tag} bias={bias} res={res}: worst err {worst:.3f} x 2^-21 S")
 
 
+def _facts_names():
+    """the reported names of FACTS[] in csrc/gemm_f16x3_plan.hpp"""
+    text = open(os.path.join(ROOT, "lemon_amd", "csrc", "gemm_f16x3_plan.hpp")).read()
+    body = text[text.index("FACTS[N_FORMS] = {"):]
+    return [ln.split('"')[1] for ln in body[:body.index("};")].splitlines() if ln.strip().startswith('{"')]
+
+
 def test_form_table_is_complete():
     # every instantiation of the dispatcher once in the table, and every form through all eight n-tile counts
     assert sorted(FORMS) == list(range(1, 14)) and len({f["kernel"] for f in FORMS.values()}) == 13
+    names = _facts_names()
+    assert len(names) == 13 and {f["kernel"] for f in FORMS.values()} == set(names)
     for f in FORMS:
         cs = _cases(f)
         assert sorted(c[2] for c in cs) == list(N_ALL)
