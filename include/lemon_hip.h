@@ -179,6 +179,10 @@ int lemon_attention_set_stream_min(int seq_len);
 int lemon_attention_set_head_dims(int mode);
 /* The calling thread's current mode. */
 int lemon_attention_get_head_dims(void);
+/* The kernel instantiation the calling thread's last lemon_attention_* call launched, as csrc/attention_plan.hpp names it (e.g.
+ * "k_attention_hd64_short<1, 2, true>"); "" before any launch; a refused call and one with batch == 0 leave it as it was.  Host
+ * state only.  For tests and tools. */
+const char *lemon_attention_last_kernel(void);
 /* The same attention with the result written as the 3-way bf16 split activation operand of lemon_linear_bf16x6 (below):
  * out6_dev [batch*seq_len, 6*heads*64] bf16, 16-byte aligned.  The fp32 result is split at the store, not recomputed. */
 int lemon_attention_split3(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,

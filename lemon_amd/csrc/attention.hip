@@ -20,8 +20,6 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <mutex>
-#include <algorithm>
 
 #include "common.hpp"
 #include "split3.hpp"
@@ -428,182 +426,101 @@ __global__ __launch_bounds__(64 * S16_WMAX, 4) void k_attention_hd64_stream_f16(
 
 }  // namespace
 
-// Arithmetic of the two products: 1 = split products on the fp16 matrix cores (q, k, v and the probabilities carried as fp16
-// pairs: inputs must stay inside +-65 504, see include/lemon_hip.h), 0 = v_mfma_f32_32x32x2_f32 (no range limit).
-// Per calling THREAD (round 5: it was one unsynchronised process-wide int, so two embedders in different GEMM modes -- or a bf16x6
-// re-embedding next to an f16x3 pass -- could pick each other's kernel): set by lemon_attention_set_f16, which the host mirror
-// calls in front of every tower pass; $LEMON_ATTN_F16=0 starts every thread with 0.
-static int attn_f16_default() {
-    static const int v = [] { const char *e = getenv("LEMON_ATTN_F16"); return (e && e[0] == '0') ? 0 : 1; }();
-    return v;
-}
-static thread_local int g_attn_f16 = attn_f16_default();
+// ---- host side: attention_plan.hpp decides, lemon_attention_launch (common.hpp) launches from the unit's one table ----
+namespace plan = lemon_attn_plan;
+static_assert(plan::HD == HD && plan::PITCH == PITCH && plan::MAX_SEQ == LEMON_ATTENTION_MAX_SEQ && plan::E_INVALID == LEMON_E_INVALID &&
+              plan::STREAM_WMAX == STREAM_WMAX && plan::STREAM_TB == STREAM_TB && plan::STREAM_KB == STREAM_KB && plan::S32_WMAX == S32_WMAX &&
+              plan::S32_TB == S32_TB && plan::S32_KB == S32_KB && plan::S16_WMAX == S16_WMAX && plan::S16_TB == S16_TB && plan::S16_KB == S16_KB,
+              "attention_plan.hpp mirrors attention_hd64.hpp, lemon_hip.h and the streaming kernels' geometry");
+static_assert(S32_KB <= STREAM_KB && S16_KB <= STREAM_KB, "the plan's 32-bit-offset guard is written for the larger key block");
 
-static thread_local int g_attn_old_general = 0;   // lemon_attention_set_f16(2): fp16 arithmetic with the FIRST general kernel (tests: bit equality)
+// the instantiations, four output forms (SPLIT 0 .. 3) per plan::Form of this unit, in the order of plan::FACTS[].slot
+typedef void (*AttnKernel)(const float *, int, int, int, float *);
+static constexpr AttnKernel KERNELS[] = {
+    k_attention_hd64_short<1, 0, false>, k_attention_hd64_short<1, 1, false>, k_attention_hd64_short<1, 2, false>, k_attention_hd64_short<1, 3, false>,
+    k_attention_hd64_short<1, 0, true>, k_attention_hd64_short<1, 1, true>, k_attention_hd64_short<1, 2, true>, k_attention_hd64_short<1, 3, true>,
+    k_attention_hd64_short<2, 0, false>, k_attention_hd64_short<2, 1, false>, k_attention_hd64_short<2, 2, false>, k_attention_hd64_short<2, 3, false>,
+    k_attention_hd64_short<2, 0, true>, k_attention_hd64_short<2, 1, true>, k_attention_hd64_short<2, 2, true>, k_attention_hd64_short<2, 3, true>,
+    k_attention_hd64<0, false>, k_attention_hd64<1, false>, k_attention_hd64<2, false>, k_attention_hd64<3, false>,
+    k_attention_hd64<0, true>, k_attention_hd64<1, true>, k_attention_hd64<2, true>, k_attention_hd64<3, true>,
+    k_attention_hd64_f16<0>, k_attention_hd64_f16<1>, k_attention_hd64_f16<2>, k_attention_hd64_f16<3>,
+    k_attention_hd64_stream<0>, k_attention_hd64_stream<1>, k_attention_hd64_stream<2>, k_attention_hd64_stream<3>,
+    k_attention_hd64_stream_f16<0>, k_attention_hd64_stream_f16<1>, k_attention_hd64_stream_f16<2>, k_attention_hd64_stream_f16<3>,
+};
+constexpr int N_KERNELS = sizeof(KERNELS) / sizeof(KERNELS[0]);
+static_assert(N_KERNELS == 4 * (plan::FACTS[plan::STREAM_F16].slot + 1) && plan::FACTS[plan::HDX_96].unit == plan::UNIT_HD, "four kernels per plan::Form of this unit");
+static LemonLdsAttr g_attr[N_KERNELS];
+
+// The calling thread's knobs (plan::Knobs says what they select) and the kernel it launched last.  Per calling THREAD (round 5:
+// the arithmetic was one unsynchronised process-wide int, so two embedders in different GEMM modes -- or a bf16x6 re-embedding next
+// to an f16x3 pass -- could pick each other's kernel): the host mirror calls lemon_attention_set_f16 in front of every tower pass.
+// Every thread starts with $LEMON_ATTN_F16 (0: fp32 arithmetic), $LEMON_ATTN_HEAD_DIMS (1 or 2) and the two tuning knobs.
+LemonAttnThread &lemon_attention_thread() {
+    static const plan::Knobs start = [] {
+        const char *f16 = getenv("LEMON_ATTN_F16"), *hd = getenv("LEMON_ATTN_HEAD_DIMS"), *sh = getenv("LEMON_ATTN_SHORT"), *ge = getenv("LEMON_ATTN_GENERAL");
+        return plan::Knobs{(f16 && f16[0] == '0') ? 0 : 1, plan::ONE_WG_MAX_SEQ, (hd && (hd[0] == '1' || hd[0] == '2') && !hd[1]) ? hd[0] - '0' : 0,
+                           sh && sh[0] == '0', ge && !strcmp(ge, "old")};
+    }();
+    thread_local LemonAttnThread t = {start, ""};
+    return t;
+}
 
 extern "C" int lemon_attention_set_f16(int on) {
-    g_attn_old_general = on == 2;
-    const int prev = g_attn_f16;
-    g_attn_f16 = on ? 1 : 0;
-    return prev;
+    return std::exchange(lemon_attention_thread().knobs.arithmetic, on == 2 ? 2 : on ? 1 : 0) != 0;
 }
 
-// the calling thread's selection as lemon_attention_set_f16 took it (0 / 1 / 2), for attention_varlen.hip
-int lemon_attention_f16_mode() { return g_attn_f16 ? (g_attn_old_general ? 2 : 1) : 0; }
-
-// Sequences longer than this take the streaming kernels (per calling thread, like the arithmetic switch)
-static thread_local int g_attn_stream_min = 288;
-
 extern "C" int lemon_attention_set_stream_min(int seq_len) {
-    if (seq_len < 64 || seq_len > 288) {
+    if (seq_len < 64 || seq_len > plan::ONE_WG_MAX_SEQ) {
         lemon_set_error("lemon_attention_set_stream_min: seq_len must be in 64 .. 288");
         return LEMON_E_INVALID;
     }
-    const int prev = g_attn_stream_min;
-    g_attn_stream_min = seq_len;
-    return prev;
+    return std::exchange(lemon_attention_thread().knobs.stream_min, seq_len);
 }
-
-// Head dims other than 64 (attention_hd.hip), per calling thread: 0 = head_dim must be 64 (the default), 1 = multiples of 8 in
-// 72 .. 128 go to k_attention_hdx_stream, 2 = head_dim 64 goes there as well (the equality test, A/B timing);
-// $LEMON_ATTN_HEAD_DIMS starts every thread with its value
-static int attn_head_dims_default() {
-    static const int v = [] { const char *e = getenv("LEMON_ATTN_HEAD_DIMS"); return (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : 0; }();
-    return v;
-}
-static thread_local int g_attn_head_dims = attn_head_dims_default();
 
 extern "C" int lemon_attention_set_head_dims(int mode) {
     if (mode < 0 || mode > 2) {
         lemon_set_error("lemon_attention_set_head_dims: mode must be 0, 1 or 2");
         return LEMON_E_INVALID;
     }
-    const int prev = g_attn_head_dims;
-    g_attn_head_dims = mode;
-    return prev;
+    return std::exchange(lemon_attention_thread().knobs.head_dims, mode);
 }
 
-extern "C" int lemon_attention_get_head_dims(void) { return g_attn_head_dims; }
+extern "C" int lemon_attention_get_head_dims(void) { return lemon_attention_thread().knobs.head_dims; }
+extern "C" const char *lemon_attention_last_kernel(void) { return lemon_attention_thread().last_kernel; }
 
-// seq_len > g_attn_stream_min (> 64): grid (batch * heads, query blocks), see k_attention_hd64_stream
-template <int SPLIT>
-static int attention_stream(const float *qkv_dev, int64_t batch, int seq_len, int heads, int causal, float *out_dev, void *stream) {
-    // the staging loops address a key block with 32-bit byte offsets: 128 tokens of 3 * heads * 256 bytes
-    static_assert(S32_KB <= STREAM_KB && S16_KB <= STREAM_KB, "the offset guard below is written for the larger key block");
-    LEMON_REQUIRE((int64_t)STREAM_KB * 3 * heads * HD * 4 < (int64_t)1 << 32, "heads < 43 690 (32-bit offsets inside a key block)");
-    const int tj = (seq_len + 31) / 32;
-    const bool f16 = g_attn_f16 != 0;
-    const int wmax = f16 ? S16_WMAX : S32_WMAX;
-    const int nqb = (tj + wmax - 1) / wmax, waves = (tj + nqb - 1) / nqb;
-    const size_t lds = f16 ? (size_t)4 * S16_KB * 128 : (size_t)2 * S32_KB * PITCH * sizeof(float);
-    {
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        LEMON_HIP_CHECK(hipGetDevice(&dev));
-        LEMON_REQUIRE(dev >= 0 && dev < 64, "device index");
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_hd64_stream<SPLIT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_hd64_stream_f16<SPLIT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            attr_set[dev] = true;
-        }
-    }
-    const dim3 grid((unsigned)(batch * heads), (unsigned)nqb);
-    if (f16) hipLaunchKernelGGL((k_attention_hd64_stream_f16<SPLIT>), grid, dim3(64 * waves), lds, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-    else hipLaunchKernelGGL((k_attention_hd64_stream<SPLIT>), grid, dim3(64 * waves), lds, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-    LEMON_HIP_CHECK(hipGetLastError());
-    return LEMON_OK;
-}
-
-template <int SPLIT>
-static int attention_impl(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
-                          int causal, float *out_dev, void *stream) {
-    LEMON_REQUIRE(batch >= 0 && seq_len > 0 && heads > 0, "batch >= 0, seq_len > 0, heads > 0");
-    const bool hdx = g_attn_head_dims != 0 && head_dim % 8 == 0 && head_dim <= 128 && (head_dim > HD || (head_dim == HD && g_attn_head_dims == 2));
-    LEMON_REQUIRE(head_dim == HD || hdx, "head_dim must be 64");
-    LEMON_REQUIRE(seq_len <= LEMON_ATTENTION_MAX_SEQ, "seq_len <= LEMON_ATTENTION_MAX_SEQ = 4096");
+// split = the output form 0 .. 3 (out_dev: see the entries)
+static int attention_entry(int split, const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim, int causal, float *out_dev,
+                           void *stream) {
+    const plan::Plan p = plan::plan(lemon_attention_thread().knobs, batch, seq_len, heads, head_dim, split, false);
+    if (p.early) return lemon_attention_refuse(p.early);
     if (batch == 0) return LEMON_OK;
     LEMON_REQUIRE(qkv_dev && out_dev, "null pointer");
     LEMON_REQUIRE((((uintptr_t)qkv_dev) & 15) == 0 && (((uintptr_t)out_dev) & 15) == 0, "16-byte alignment");
-    LEMON_REQUIRE(batch * heads < (int64_t)1 << 31, "batch * heads < 2^31");
-    if (hdx) return lemon_attention_hdx(qkv_dev, batch, seq_len, heads, head_dim, causal, out_dev, SPLIT, (hipStream_t)stream);
-    const int tj = (seq_len + 31) / 32;
-    static const bool short_off = [] { const char *e = getenv("LEMON_ATTN_SHORT"); return e && e[0] == '0'; }();   // tuning knob
-    const dim3 grid((unsigned)(batch * heads));
-    if (tj <= 2 && !short_off) {
-        const bool f16_off = g_attn_f16 == 0;
-        if (f16_off) {
-            if (tj == 1) hipLaunchKernelGGL((k_attention_hd64_short<1, SPLIT, false>), grid, dim3(64), 0, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-            else         hipLaunchKernelGGL((k_attention_hd64_short<2, SPLIT, false>), grid, dim3(128), 0, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-        } else {
-            if (tj == 1) hipLaunchKernelGGL((k_attention_hd64_short<1, SPLIT, true>), grid, dim3(64), 0, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-            else         hipLaunchKernelGGL((k_attention_hd64_short<2, SPLIT, true>), grid, dim3(128), 0, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-        }
-        LEMON_HIP_CHECK(hipGetLastError());
-        return LEMON_OK;
-    }
-    if (seq_len > g_attn_stream_min) return attention_stream<SPLIT>(qkv_dev, batch, seq_len, heads, causal, out_dev, stream);
-    // 64 < L <= 288.  Split-fp16 arithmetic: the kernel that splits K and V once at staging (k_attention_hd64_f16);
-    // LEMON_ATTN_GENERAL=old keeps the first version (fp32 K / V in LDS, re-split by every wave) for A/B runs and the equality test
-    static const bool old_general = [] { const char *e = getenv("LEMON_ATTN_GENERAL"); return e && !strcmp(e, "old"); }();
-    const bool staged = g_attn_f16 != 0 && !old_general && !g_attn_old_general;
-    // staged kernel: four planes of one key block (ceil(tj / 2) tiles when tj > 5), but never less than the fp32 [32 tj][64]
-    // image Q and the output pass through
-    const int tb = (tj <= 5 || tj > 8) ? tj : (tj + 1) / 2;
-    const size_t lds_staged = std::max((size_t)4 * 32 * tb * 128, (size_t)32 * tj * 256);
-    const size_t lds = staged ? lds_staged : (size_t)2 * 32 * tj * PITCH * sizeof(float);
-    {   // the attribute is per DEVICE (and per instantiation): one flag per device index, under a lock
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        LEMON_HIP_CHECK(hipGetDevice(&dev));
-        LEMON_REQUIRE(dev >= 0 && dev < 64, "device index");
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_hd64<SPLIT, true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_hd64<SPLIT, false>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_hd64_f16<SPLIT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[dev] = true;
-        }
-    }
-    if (staged) {
-        hipLaunchKernelGGL((k_attention_hd64_f16<SPLIT>), grid, dim3(64 * tj), lds, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-        LEMON_HIP_CHECK(hipGetLastError());
-        return LEMON_OK;
-    }
-    const bool f16_off_g = g_attn_f16 == 0;
-    if (f16_off_g) hipLaunchKernelGGL((k_attention_hd64<SPLIT, false>), grid, dim3(64 * tj), lds, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-    else hipLaunchKernelGGL((k_attention_hd64<SPLIT, true>), grid, dim3(64 * tj), lds, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
-    LEMON_HIP_CHECK(hipGetLastError());
-    return LEMON_OK;
+    if (p.late) return lemon_attention_refuse(p.late);
+    if (plan::FACTS[p.form].unit == plan::UNIT_HD) return lemon_attention_hdx(p, split, qkv_dev, seq_len, heads, causal, out_dev, (hipStream_t)stream);
+    return lemon_attention_launch(KERNELS, g_attr, p, split, (hipStream_t)stream, qkv_dev, seq_len, heads, causal, out_dev);
 }
 
 extern "C" int lemon_attention_f32(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                    int causal, float *out_dev, void *stream) {
-    return attention_impl<0>(qkv_dev, batch, seq_len, heads, head_dim, causal, out_dev, stream);
+    return attention_entry(0, qkv_dev, batch, seq_len, heads, head_dim, causal, out_dev, stream);
 }
 
 // lemon_attention_f32 whose output is the split activation operand of lemon_linear_bf16x6: out6_dev [batch*seq_len, 6*heads*64] bf16
 extern "C" int lemon_attention_split3(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                       int causal, uint16_t *out6_dev, void *stream) {
-    return attention_impl<1>(qkv_dev, batch, seq_len, heads, head_dim, causal, reinterpret_cast<float *>(out6_dev), stream);
+    return attention_entry(1, qkv_dev, batch, seq_len, heads, head_dim, causal, reinterpret_cast<float *>(out6_dev), stream);
 }
 
 // ... of lemon_linear_f16x3: out3_dev [batch*seq_len, 3*heads*64] fp16
 extern "C" int lemon_attention_f16x3(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                      int causal, uint16_t *out3_dev, void *stream) {
-    return attention_impl<2>(qkv_dev, batch, seq_len, heads, head_dim, causal, reinterpret_cast<float *>(out3_dev), stream);
+    return attention_entry(2, qkv_dev, batch, seq_len, heads, head_dim, causal, reinterpret_cast<float *>(out3_dev), stream);
 }
 
 // ... as the tile-major fp16 activation operand of lemon_linear_f16x3t (the output projection in the hand-written GEMM):
 // outt_dev holds ceil(batch*seq_len / 128) * 128 x heads*64 x 2 halves, 16-byte aligned
 extern "C" int lemon_attention_f16x3t(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                       int causal, uint16_t *outt_dev, void *stream) {
-    return attention_impl<3>(qkv_dev, batch, seq_len, heads, head_dim, causal, reinterpret_cast<float *>(outt_dev), stream);
+    return attention_entry(3, qkv_dev, batch, seq_len, heads, head_dim, causal, reinterpret_cast<float *>(outt_dev), stream);
 }

@@ -15,7 +15,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include <mutex>
 
 #include "common.hpp"
 #include "split3.hpp"
@@ -190,45 +189,23 @@ __global__ __launch_bounds__(64 * X_WMAX, HDP == 96 ? 3 : 2) void k_attention_hd
     }
 }
 
-template <int HDP, int SPLIT>
-int launch(const float *qkv_dev, int64_t batch, int seq_len, int heads, int hd, int causal, float *out_dev, hipStream_t stream) {
-    const int tj = (seq_len + 31) / 32;
-    const int nqb = (tj + X_WMAX - 1) / X_WMAX, waves = (tj + nqb - 1) / nqb;
-    const size_t lds = (size_t)2 * X_KB * (HDP + 4) * sizeof(float);
-    if (lds > 64 * 1024) {   // (HDP 128) the attribute is per DEVICE and per instantiation: one flag per device index, under a lock
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        LEMON_HIP_CHECK(hipGetDevice(&dev));
-        LEMON_REQUIRE(dev >= 0 && dev < 64, "device index");
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_hdx_stream<HDP, SPLIT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set[dev] = true;
-        }
-    }
-    const float c_exp = (float)(1.44269504088896340736 / sqrt((double)hd));       // log2(e) / sqrt(hd)
-    const dim3 grid((unsigned)(batch * heads), (unsigned)nqb);
-    hipLaunchKernelGGL((k_attention_hdx_stream<HDP, SPLIT>), grid, dim3(64 * waves), lds, stream, qkv_dev, seq_len, heads, hd, causal, c_exp, out_dev);
-    LEMON_HIP_CHECK(hipGetLastError());
-    return LEMON_OK;
-}
+namespace plan = lemon_attn_plan;
+static_assert(plan::X_WMAX == X_WMAX && plan::X_TB == X_TB && plan::X_KB == X_KB && plan::HD == HD && plan::HDX_NARROW == 96 && plan::HDX_MAX == 128 &&
+              plan::hdx_lds(96) == 2 * X_KB * (96 + 4) * (int)sizeof(float), "attention_plan.hpp mirrors the kernel's geometry, LDS pitch and the HDP each hd takes");
+
+// the instantiations, four output forms (SPLIT 0 .. 3) per plan::Form of this unit, in the order of plan::FACTS[].slot
+typedef void (*HdxKernel)(const float *, int, int, int, int, float, float *);
+constexpr HdxKernel KERNELS[] = {
+    k_attention_hdx_stream<96, 0>, k_attention_hdx_stream<96, 1>, k_attention_hdx_stream<96, 2>, k_attention_hdx_stream<96, 3>,
+    k_attention_hdx_stream<128, 0>, k_attention_hdx_stream<128, 1>, k_attention_hdx_stream<128, 2>, k_attention_hdx_stream<128, 3>,
+};
+constexpr int N_KERNELS = sizeof(KERNELS) / sizeof(KERNELS[0]);
+static_assert(N_KERNELS == 4 * (plan::FACTS[plan::HDX_128].slot + 1) && plan::FACTS[plan::HDX_96].slot == 0, "four kernels per plan::Form of this unit");
+LemonLdsAttr g_attr[N_KERNELS];
 
 }  // namespace
 
-// attention_impl (attention.hip) has checked batch, seq_len, the pointers and batch * heads; split = the output form 0 .. 3
-int lemon_attention_hdx(const float *qkv_dev, int64_t batch, int seq_len, int heads, int hd, int causal, float *out_dev, int split,
-                        hipStream_t stream) {
-    LEMON_REQUIRE(hd % 8 == 0 && hd >= 64 && hd <= 128, "head_dim a multiple of 8 in 64 .. 128");
-    LEMON_REQUIRE((int64_t)X_KB * 3 * heads * hd * 4 < (int64_t)1 << 32, "64 * 3 * heads * head_dim * 4 < 2^32 (32-bit offsets inside a key block)");
-    LEMON_REQUIRE(split != 3 || (heads * hd) % 16 == 0, "tile-major output: heads * head_dim a multiple of 16");
-    const bool wide = hd > 96;
-    switch (split) {
-    case 0: return wide ? launch<128, 0>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream) : launch<96, 0>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream);
-    case 1: return wide ? launch<128, 1>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream) : launch<96, 1>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream);
-    case 2: return wide ? launch<128, 2>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream) : launch<96, 2>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream);
-    case 3: return wide ? launch<128, 3>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream) : launch<96, 3>(qkv_dev, batch, seq_len, heads, hd, causal, out_dev, stream);
-    }
-    LEMON_REQUIRE(false, "output form 0 .. 3");
+int lemon_attention_hdx(const plan::Plan &p, int split, const float *qkv_dev, int seq_len, int heads, int causal, float *out_dev, hipStream_t stream) {
+    const float c_exp = (float)(1.44269504088896340736 / sqrt((double)p.hd));       // log2(e) / sqrt(hd)
+    return lemon_attention_launch(KERNELS, g_attr, p, split, stream, qkv_dev, seq_len, heads, p.hd, causal, c_exp, out_dev);
 }

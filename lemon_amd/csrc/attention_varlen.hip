@@ -13,8 +13,6 @@
 // entry points and their dispatch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <mutex>
-#include <algorithm>
 
 #include "common.hpp"
 #include "attention_hd64.hpp"
@@ -40,54 +38,35 @@ __global__ __launch_bounds__(576, 4) void k_attnvl_f16(const float *__restrict__
     attention_staged<SPLIT, true>(qkv, L, H, 0, lengths, out);
 }
 
-template <int SPLIT>
-int attention_varlen_impl(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim, const int32_t *lengths_dev,
-                          float *out_dev, void *stream) {
-    LEMON_REQUIRE(batch >= 0 && seq_len > 0 && heads > 0, "batch >= 0, seq_len > 0, heads > 0");
-    LEMON_REQUIRE(head_dim == HD, "per-sequence lengths: head_dim must be 64 (in every lemon_attention_set_head_dims mode)");
-    LEMON_REQUIRE(seq_len <= 288, "per-sequence lengths: seq_len <= 288 (the streaming kernels take no lengths)");
+namespace plan = lemon_attn_plan;
+static_assert(plan::HD == HD && plan::PITCH == PITCH, "attention_plan.hpp mirrors attention_hd64.hpp");
+
+// the instantiations, four output forms (SPLIT 0 .. 3) per plan::Form of this unit, in the order of plan::FACTS[].slot
+typedef void (*VarlenKernel)(const float *, int, int, const int *, float *);
+constexpr VarlenKernel KERNELS[] = {
+    k_attnvl_short<1, 0, false>, k_attnvl_short<1, 1, false>, k_attnvl_short<1, 2, false>, k_attnvl_short<1, 3, false>,
+    k_attnvl_short<1, 0, true>, k_attnvl_short<1, 1, true>, k_attnvl_short<1, 2, true>, k_attnvl_short<1, 3, true>,
+    k_attnvl_short<2, 0, false>, k_attnvl_short<2, 1, false>, k_attnvl_short<2, 2, false>, k_attnvl_short<2, 3, false>,
+    k_attnvl_short<2, 0, true>, k_attnvl_short<2, 1, true>, k_attnvl_short<2, 2, true>, k_attnvl_short<2, 3, true>,
+    k_attnvl_f32<0>, k_attnvl_f32<1>, k_attnvl_f32<2>, k_attnvl_f32<3>,
+    k_attnvl_f16<0>, k_attnvl_f16<1>, k_attnvl_f16<2>, k_attnvl_f16<3>,
+};
+constexpr int N_KERNELS = sizeof(KERNELS) / sizeof(KERNELS[0]);
+static_assert(N_KERNELS == 4 * (plan::FACTS[plan::VL_F16].slot + 1) && plan::FACTS[plan::VL_SHORT1_F32].slot == 0, "four kernels per plan::Form of this unit");
+LemonLdsAttr g_attr[N_KERNELS];
+
+
+// split = the output form 0 .. 3 (out_dev: see the entries)
+int varlen_entry(int split, const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim, const int32_t *lengths_dev, float *out_dev,
+                 void *stream) {
+    const plan::Plan p = plan::plan(lemon_attention_thread().knobs, batch, seq_len, heads, head_dim, split, true);
+    if (p.early) return lemon_attention_refuse(p.early);
     if (batch == 0) return LEMON_OK;
     LEMON_REQUIRE(qkv_dev && out_dev, "null pointer");
     LEMON_REQUIRE((((uintptr_t)qkv_dev) & 15) == 0 && (((uintptr_t)out_dev) & 15) == 0, "16-byte alignment");
     LEMON_REQUIRE((((uintptr_t)lengths_dev) & 3) == 0, "lengths: 4-byte alignment");
-    LEMON_REQUIRE(batch * heads < (int64_t)1 << 31, "batch * heads < 2^31");
-    LEMON_REQUIRE((int64_t)288 * 3 * heads * HD * 4 < (int64_t)1 << 32, "heads < 19 418 (32-bit offsets inside a head's slice)");
-    const int tj = (seq_len + 31) / 32;
-    const bool f16 = lemon_attention_f16_mode() != 0;
-    const dim3 grid((unsigned)(batch * heads));
-    hipStream_t st = (hipStream_t)stream;
-    if (tj <= 2) {
-        if (f16) {
-            if (tj == 1) hipLaunchKernelGGL((k_attnvl_short<1, SPLIT, true>), grid, dim3(64), 0, st, qkv_dev, seq_len, heads, lengths_dev, out_dev);
-            else         hipLaunchKernelGGL((k_attnvl_short<2, SPLIT, true>), grid, dim3(128), 0, st, qkv_dev, seq_len, heads, lengths_dev, out_dev);
-        } else {
-            if (tj == 1) hipLaunchKernelGGL((k_attnvl_short<1, SPLIT, false>), grid, dim3(64), 0, st, qkv_dev, seq_len, heads, lengths_dev, out_dev);
-            else         hipLaunchKernelGGL((k_attnvl_short<2, SPLIT, false>), grid, dim3(128), 0, st, qkv_dev, seq_len, heads, lengths_dev, out_dev);
-        }
-        LEMON_HIP_CHECK(hipGetLastError());
-        return LEMON_OK;
-    }
-    const int tb = (tj <= 5 || tj > 8) ? tj : (tj + 1) / 2;
-    const size_t lds = f16 ? std::max((size_t)4 * 32 * tb * 128, (size_t)32 * tj * 256) : (size_t)2 * 32 * tj * PITCH * sizeof(float);
-    {   // the attribute is per DEVICE (and per instantiation): one flag per device index, under a lock
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        LEMON_HIP_CHECK(hipGetDevice(&dev));
-        LEMON_REQUIRE(dev >= 0 && dev < 64, "device index");
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attnvl_f32<SPLIT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attnvl_f16<SPLIT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[dev] = true;
-        }
-    }
-    if (f16) hipLaunchKernelGGL((k_attnvl_f16<SPLIT>), grid, dim3(64 * tj), lds, st, qkv_dev, seq_len, heads, lengths_dev, out_dev);
-    else hipLaunchKernelGGL((k_attnvl_f32<SPLIT>), grid, dim3(64 * tj), lds, st, qkv_dev, seq_len, heads, lengths_dev, out_dev);
-    LEMON_HIP_CHECK(hipGetLastError());
-    return LEMON_OK;
+    if (p.late) return lemon_attention_refuse(p.late);
+    return lemon_attention_launch(KERNELS, g_attr, p, split, (hipStream_t)stream, qkv_dev, seq_len, heads, lengths_dev, out_dev);
 }
 
 }  // namespace
@@ -96,23 +75,23 @@ int attention_varlen_impl(const float *qkv_dev, int64_t batch, int seq_len, int 
 extern "C" int lemon_attention_f32_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                           const int32_t *lengths_dev, float *out_dev, void *stream) {
     if (!lengths_dev) return lemon_attention_f32(qkv_dev, batch, seq_len, heads, head_dim, 0, out_dev, stream);
-    return attention_varlen_impl<0>(qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, out_dev, stream);
+    return varlen_entry(0, qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, out_dev, stream);
 }
 
 extern "C" int lemon_attention_split3_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                              const int32_t *lengths_dev, uint16_t *out6_dev, void *stream) {
     if (!lengths_dev) return lemon_attention_split3(qkv_dev, batch, seq_len, heads, head_dim, 0, out6_dev, stream);
-    return attention_varlen_impl<1>(qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, reinterpret_cast<float *>(out6_dev), stream);
+    return varlen_entry(1, qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, reinterpret_cast<float *>(out6_dev), stream);
 }
 
 extern "C" int lemon_attention_f16x3_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                             const int32_t *lengths_dev, uint16_t *out3_dev, void *stream) {
     if (!lengths_dev) return lemon_attention_f16x3(qkv_dev, batch, seq_len, heads, head_dim, 0, out3_dev, stream);
-    return attention_varlen_impl<2>(qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, reinterpret_cast<float *>(out3_dev), stream);
+    return varlen_entry(2, qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, reinterpret_cast<float *>(out3_dev), stream);
 }
 
 extern "C" int lemon_attention_f16x3t_varlen(const float *qkv_dev, int64_t batch, int seq_len, int heads, int head_dim,
                                              const int32_t *lengths_dev, uint16_t *outt_dev, void *stream) {
     if (!lengths_dev) return lemon_attention_f16x3t(qkv_dev, batch, seq_len, heads, head_dim, 0, outt_dev, stream);
-    return attention_varlen_impl<3>(qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, reinterpret_cast<float *>(outt_dev), stream);
+    return varlen_entry(3, qkv_dev, batch, seq_len, heads, head_dim, lengths_dev, reinterpret_cast<float *>(outt_dev), stream);
 }

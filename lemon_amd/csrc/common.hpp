@@ -7,8 +7,10 @@
 #include <string.h>
 #include <float.h>
 #include "../../include/lemon_hip.h"
+#include "attention_plan.hpp"
 #include <vector>
 #include <utility>
+#include <mutex>
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -155,8 +157,38 @@ int lemon_dedup_queries(lemon_index_t *idx, const float *q_dev, int64_t nq, hipS
 int lemon_gather_query_rows(const float *q_dev, const int *rep_dev, int64_t U, int d, float *out_dev, hipStream_t stream);
 int lemon_expand_results(const float *Dr, const int64_t *Ir, const int *group_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
                          hipStream_t stream);
-// attention at head dims 64 .. 128 (attention_hd.hip), called by attention_impl (attention.hip) after its argument checks
-int lemon_attention_hdx(const float *qkv_dev, int64_t batch, int seq_len, int heads, int hd, int causal, float *out_dev, int split,
+// ---- attention: what its three units share (attention_plan.hpp decides, each unit launches from its own table) ----
+// the calling thread's knobs and the reported name of the kernel it launched last ("" before any launch): attention.hip
+struct LemonAttnThread { lemon_attn_plan::Knobs knobs; const char *last_kernel; };
+LemonAttnThread &lemon_attention_thread();
+inline int lemon_attention_refuse(lemon_attn_plan::Refusal why) {
+    lemon_set_error("%s", lemon_attn_plan::MESSAGES[why]);
+    return lemon_attn_plan::E_INVALID;
+}
+// Launch a unit's kernels[4 * slot + split] as the plan says.  Dynamic LDS beyond 64 KB needs
+// hipFuncAttributeMaxDynamicSharedMemorySize per DEVICE and per kernel: attr_set holds one row of flags (a flag per device index)
+// per kernel of the table, set under one lock in front of the kernel's first launch on the current device.
+struct LemonLdsAttr { bool set[64]; };
+inline std::mutex g_lemon_lds_attr_mu;
+template <typename Kernel, typename... Args>
+int lemon_attention_launch(const Kernel *kernels, LemonLdsAttr *attr_set, const lemon_attn_plan::Plan &p, int split, hipStream_t stream, Args... args) {
+    const lemon_attn_plan::FormFacts &f = lemon_attn_plan::FACTS[p.form];
+    const int i = 4 * f.slot + split;
+    if (f.attr) {
+        int dev = 0;
+        LEMON_HIP_CHECK(hipGetDevice(&dev));
+        LEMON_REQUIRE(dev >= 0 && dev < 64, "device index");
+        std::lock_guard<std::mutex> lock(g_lemon_lds_attr_mu);
+        if (!attr_set[i].set[dev]) {
+            LEMON_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, f.attr));
+            attr_set[i].set[dev] = true;
+        }
+    }
+    hipLaunchKernelGGL(kernels[i], dim3(p.grid_x, p.grid_y), dim3(p.threads), p.lds, stream, args...);
+    lemon_attention_thread().last_kernel = f.name[split];
+    LEMON_HIP_CHECK(hipGetLastError());
+    return LEMON_OK;
+}
+// the launch of a plan whose form belongs to attention_hd.hip, for the entries of attention.hip (after their checks)
+int lemon_attention_hdx(const lemon_attn_plan::Plan &p, int split, const float *qkv_dev, int seq_len, int heads, int causal, float *out_dev,
                         hipStream_t stream);
-// the calling thread's lemon_attention_set_f16 selection, 0 / 1 / 2 (attention.hip), read by attention_varlen.hip
-int lemon_attention_f16_mode();

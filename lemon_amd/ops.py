@@ -232,20 +232,14 @@ class gemm_mode_forced:
         return False
 
 
-_attn_f16_state = None            # (kept for callers that reset it; the library is asked every time now)
-
-
 def select_attention_arithmetic(mode):
     """The attention kernels' arithmetic follows the GEMM mode: split products on the fp16 matrix cores with 'f16x3' (inputs
     must stay inside the fp16 range, like the GEMM operands of that mode), v_mfma_f32_32x32x2_f32 with 'bf16x6' (the mode whose
     point is to have no range limit) and 'f32'.  $LEMON_ATTN_F16=0 keeps the fp32 form in every mode.  The library keeps the
     selection per calling thread (lemon_attention_set_f16) and this is called in front of every tower pass WITHOUT a host-side
     cache: a direct lemon_attention_set_f16 call, another embedder or another thread cannot leave a stale choice behind."""
-    global _attn_f16_state
     import os
-    want = 1 if (mode == "f16x3" and os.environ.get("LEMON_ATTN_F16", "1") != "0") else 0
-    _lib.load().lemon_attention_set_f16(want)
-    _attn_f16_state = want
+    _lib.load().lemon_attention_set_f16(1 if (mode == "f16x3" and os.environ.get("LEMON_ATTN_F16", "1") != "0") else 0)
 
 
 def gemm_mode():
@@ -360,11 +354,16 @@ def set_attention_head_dims(mode):
     return int(prev)
 
 
+def _attention_limits(hd, seq_len, head_dims, varlen=False):
+    """The limits of csrc/attention_plan.hpp: head_dim 64, or with the head-dim mode on a multiple of 8 in 72 .. 128 (never with
+    per-sequence lengths); seq_len up to ATTENTION_MAX_SEQ, with lengths up to what the one-workgroup kernels hold."""
+    if varlen:
+        return hd == 64 and seq_len <= ATTENTION_VARLEN_MAX_SEQ
+    return seq_len <= ATTENTION_MAX_SEQ and (hd == 64 or (head_dims != 0 and hd % 8 == 0 and 64 < hd <= 128))
+
+
 def _attention_takes(width, heads, seq_len, head_dims):
-    if heads <= 0 or width % heads or seq_len > ATTENTION_MAX_SEQ:
-        return False
-    hd = width // heads
-    return hd == 64 or (head_dims != 0 and hd % 8 == 0 and 64 < hd <= 128)
+    return heads > 0 and width % heads == 0 and _attention_limits(width // heads, seq_len, head_dims)
 
 
 def attention_supported(width, heads, seq_len):
@@ -613,7 +612,7 @@ ATTENTION_VARLEN_MAX_SEQ = 288     # the one-workgroup kernels: the streaming ke
 
 def attention_varlen_supported(width, heads, seq_len):
     """Do the lemon_attention_*_varlen entry points (a key length per sequence) take this tower at this token count?"""
-    return heads > 0 and width == 64 * heads and 1 <= seq_len <= ATTENTION_VARLEN_MAX_SEQ
+    return heads > 0 and width % heads == 0 and seq_len >= 1 and _attention_limits(width // heads, seq_len, 0, varlen=True)
 
 
 def attention_lengths(lengths, batch, device):
@@ -630,32 +629,37 @@ def attention_lengths(lengths, batch, device):
 
 def _varlen_args(lengths, causal, B, L, heads, hd, device):
     assert not causal, "per-sequence lengths: bidirectional attention only (padding behind a caption is invisible under a causal mask)"
-    if not (hd == 64 and L <= ATTENTION_VARLEN_MAX_SEQ):
+    if not _attention_limits(hd, L, 0, varlen=True):
         raise ValueError(f"attention with per-sequence lengths: head_dim 64 and seq_len <= {ATTENTION_VARLEN_MAX_SEQ} "
                          f"(got head_dim {hd}, seq_len {L}); see ops.attention_varlen_supported")
     return attention_lengths(lengths, B, device)
 
 
-def attention_t(qkv, heads, causal=False, lengths=None):
-    """attention() whose output is the tile-major fp16 activation operand of lemon_linear_f16x3t (rows = B*L, k = W = heads*head_dim,
-    a multiple of 16).  lengths: see attention()."""
-    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3
+def _attention(form, qkv, heads, causal, lengths):
+    """The one attention call behind attention (form 'f32'), attention_split ('split3' / 'f16x3') and attention_t ('f16x3t'): shape
+    checks, the output of that form, the entry with or without per-sequence lengths."""
+    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and (form != "f32" or qkv.is_contiguous())
     qkv = qkv.contiguous()
     B, L, W3 = qkv.shape
     W = W3 // 3
     hd = W // heads
-    assert W3 == 3 * W and W == heads * hd and W % 16 == 0 and L <= ATTENTION_MAX_SEQ
-    out = torch.empty((_tiled_rows(B * L) * W * 2,), dtype=torch.float16, device=qkv.device)
-    lib = _lib.load()
+    assert W3 == 3 * W and W == heads * hd and (form != "f16x3t" or W % 16 == 0) and L <= ATTENTION_MAX_SEQ
+    if form == "f16x3t":
+        out = torch.empty((_tiled_rows(B * L) * W * 2,), dtype=torch.float16, device=qkv.device)
+    else:
+        dtype, seg = (torch.float32, 1) if form == "f32" else _SCHEMES["bf16x6" if form == "split3" else form]
+        out = torch.empty((B, L, seg * W), dtype=dtype, device=qkv.device)
+    name = "lemon_attention_" + form + ("_varlen" if lengths is not None else "")
     with torch.cuda.device(qkv.device):
-        if lengths is not None:
-            ln = _varlen_args(lengths, causal, B, L, heads, hd, qkv.device)
-            _lib.check(lib.lemon_attention_f16x3t_varlen(ptr(qkv), B, L, heads, hd, ptr(ln), ptr(out), stream_ptr(qkv.device)),
-                       "lemon_attention_f16x3t_varlen")
-            return out
-        _lib.check(lib.lemon_attention_f16x3t(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out), stream_ptr(qkv.device)),
-                   "lemon_attention_f16x3t")
+        how = ptr(_varlen_args(lengths, causal, B, L, heads, hd, qkv.device)) if lengths is not None else int(bool(causal))
+        _lib.check(getattr(_lib.load(), name)(ptr(qkv), B, L, heads, hd, how, ptr(out), stream_ptr(qkv.device)), name.replace("split3", "bf16x6"))
     return out
+
+
+def attention_t(qkv, heads, causal=False, lengths=None):
+    """attention() whose output is the tile-major fp16 activation operand of lemon_linear_f16x3t (rows = B*L, k = W = heads*head_dim,
+    a multiple of 16).  lengths: see attention()."""
+    return _attention("f16x3t", qkv, heads, causal, lengths)
 
 
 def unpack_act_t(at, m, k):
@@ -708,45 +712,13 @@ def attention(qkv, heads, causal=False, lengths=None):
     lengths: None, or the key count of every sequence -- an int32 CUDA tensor [B], or a host sequence (uploaded without a
     synchronisation): sequence b attends to its first clamp(lengths[b], 1, L) tokens only and its rows beyond them come out as
     zeros (lemon_attention_*_varlen: bidirectional, head_dim 64, L <= 288, see attention_varlen_supported)."""
-    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.dim() == 3
-    B, L, W3 = qkv.shape
-    W = W3 // 3
-    hd = W // heads
-    assert W3 == 3 * W and W == heads * hd and L <= ATTENTION_MAX_SEQ
-    out = torch.empty((B, L, W), dtype=torch.float32, device=qkv.device)
-    lib = _lib.load()
-    with torch.cuda.device(qkv.device):
-        if lengths is not None:
-            ln = _varlen_args(lengths, causal, B, L, heads, hd, qkv.device)
-            _lib.check(lib.lemon_attention_f32_varlen(ptr(qkv), B, L, heads, hd, ptr(ln), ptr(out), stream_ptr(qkv.device)),
-                       "lemon_attention_f32_varlen")
-            return out
-        _lib.check(lib.lemon_attention_f32(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out),
-                                           stream_ptr(qkv.device)), "lemon_attention_f32")
-    return out
+    return _attention("f32", qkv, heads, causal, lengths)
 
 
 def attention_split(qkv, heads, causal=False, mode="bf16x6", lengths=None):
     """attention() whose output is the split activation operand of `mode`: [B, L, 6*W] bf16 (lemon_attention_split3) or
     [B, L, 3*W] fp16 (lemon_attention_f16x3).  lengths: see attention()."""
-    dtype, seg = _SCHEMES[mode]
-    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3
-    qkv = qkv.contiguous()
-    B, L, W3 = qkv.shape
-    W = W3 // 3
-    hd = W // heads
-    assert W3 == 3 * W and W == heads * hd and L <= ATTENTION_MAX_SEQ
-    out = torch.empty((B, L, seg * W), dtype=dtype, device=qkv.device)
-    lib = _lib.load()
-    fn = lib.lemon_attention_split3 if mode == "bf16x6" else lib.lemon_attention_f16x3
-    with torch.cuda.device(qkv.device):
-        if lengths is not None:
-            ln = _varlen_args(lengths, causal, B, L, heads, hd, qkv.device)
-            fnv = lib.lemon_attention_split3_varlen if mode == "bf16x6" else lib.lemon_attention_f16x3_varlen
-            _lib.check(fnv(ptr(qkv), B, L, heads, hd, ptr(ln), ptr(out), stream_ptr(qkv.device)), "lemon_attention_" + mode + "_varlen")
-            return out
-        _lib.check(fn(ptr(qkv), B, L, heads, hd, int(bool(causal)), ptr(out), stream_ptr(qkv.device)), "lemon_attention_" + mode)
-    return out
+    return _attention({"bf16x6": "split3", "f16x3": "f16x3"}[mode], qkv, heads, causal, lengths)
 
 
 def attention_split3(qkv, heads, causal=False):

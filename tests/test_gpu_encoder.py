@@ -341,7 +341,6 @@ def test_attention_range_and_small_magnitudes_on_head_dim_64(hip, L, H, causal):
                     assert bool(torch.isfinite(got).all()) and float((got - want).abs().max()) <= tol, (name, f16, float((got - want).abs().max()), tol)
     finally:
         lib.lemon_attention_set_f16(prev)
-        ops._attn_f16_state = None
 
 
 def test_fused_mlp_and_library_mlp_give_the_same_embeddings(hip, monkeypatch):
