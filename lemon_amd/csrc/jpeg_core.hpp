@@ -38,6 +38,16 @@ LEMON_JPEG_HD bool jpeg_geometry(int64_t w, int64_t h, int64_t ncomp, int64_t hs
     return true;
 }
 
+// Record block (planar: luma plane, then the two chroma planes) of block `slot` of interleaved MCU m: the luma blocks of the
+// MCU row by row (hs x vs of them, `luma` in all), then Cb, then Cr; mx MCUs per row.  With one component hs = vs = luma = 1.
+// Callers: lemon_jpeg_par::par_block_addr (jpeg_par.hpp), lemon_jpeg_prog::prog_block_addr (jpeg_prog_par.hpp).
+LEMON_JPEG_HD int64_t jpeg_mcu_block_addr(const JpegGeom &g, int32_t mx, int hs, int vs, int luma, int64_t m, int slot) {
+    const int64_t yy = m / mx, xx = m - yy * mx;
+    if (slot >= luma) return (slot == luma ? g.n0 : g.n0 + g.nc) + yy * g.bwc + xx;
+    const int by = slot / hs, bx = slot - by * hs;
+    return (yy * vs + by) * g.bw0 + xx * hs + bx;
+}
+
 // ---- jidctint: CONST_BITS = 13, PASS1_BITS = 2.  One 1-D step, outputs before the rounding shift.
 LEMON_JPEG_HD void jpeg_idct_1d(int32_t in0, int32_t in1, int32_t in2, int32_t in3, int32_t in4, int32_t in5, int32_t in6, int32_t in7,
                                 int32_t out[8]) {

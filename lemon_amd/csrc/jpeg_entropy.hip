@@ -62,8 +62,7 @@ inline int64_t jent_carve(char *base, int64_t batch, int64_t groups, int64_t int
 // the image's descriptor against the buffers' extents, then its packet (jpeg_par.hpp::par_open)
 __device__ __forceinline__ bool jent_open(const JentParams &p, int64_t i, ParImage &im) {
     const int64_t *d = p.desc + 8 * i;
-    if (d[0] < 0 || (d[0] & 15) != 0 || d[1] < 0 || d[0] > p.pk_bytes || d[1] > p.pk_bytes - d[0]) return false;
-    if (d[2] < 0 || (d[2] & 15) != 0 || d[2] > p.rec_bytes) return false;
+    if (!jpeg_dev_extents(d, p.pk_bytes, p.rec_bytes)) return false;
     if (d[4] < 0 || d[6] < 0 || d[4] > p.total_groups || d[6] > p.total_groups - d[4]) return false;
     if (d[5] < 0 || d[3] < 1 || d[5] > p.total_intervals || d[3] > p.total_intervals - d[5]) return false;
     if (!par_open(p.pk + d[0], d[1], p.rec_bytes - d[2], im)) return false;
@@ -131,8 +130,8 @@ __device__ __forceinline__ void jent_lane(const JentParams &p, const ParImage &i
     l.len = p.ws.ivl_len[ivl0 + t];
     l.d = im.scan + p.ws.ivl_start[ivl0 + t];
     l.end_bit = 8 * (l.len < (i + 1) * S ? l.len : (i + 1) * S);
-    l.mcu0 = im.restart ? t * im.restart : 0;
-    l.total = (im.restart && im.mcus - l.mcu0 > im.restart ? im.restart : im.mcus - l.mcu0) * im.spm;
+    const McuRange r = interval_mcus(im.restart, im.mcus, t);
+    l.mcu0 = r.first; l.total = r.count * im.spm;
     l.guess = par_state(8 * i * S, 0, 0);
     l.first = i == 0;
     l.last = i + 1 == par_lanes_of(l.len, (int32_t)S);
@@ -190,11 +189,7 @@ __global__ __launch_bounds__(JENT_T) void k_jent_zero(JentParams p) {
     const int64_t i = blockIdx.x;
     ParImage im;
     if (!p.ws.img[4 * i] || !jent_open(p, i, im)) return;
-    uint8_t *rec = p.rec + p.desc[8 * i + 2];
-    const int64_t n16 = (LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks) / 16;
-    const uint4 *q = reinterpret_cast<const uint4 *>(im.pkt + kQuantOff);
-    for (int64_t k = (int64_t)blockIdx.y * JENT_T + threadIdx.x; k < n16; k += (int64_t)JENT_ZY * JENT_T)
-        reinterpret_cast<uint4 *>(rec)[k] = k < LEMON_JPEG_QUANT_BYTES / 16 ? q[k] : make_uint4(0, 0, 0, 0);
+    jpeg_dev_new_record(p.rec + p.desc[8 * i + 2], im.pkt, im.g, (int64_t)blockIdx.y * JENT_T + threadIdx.x, (int64_t)JENT_ZY * JENT_T);
 }
 
 __global__ __launch_bounds__(JENT_T) void k_jent_sync(JentParams p, int round) {
@@ -335,15 +330,8 @@ __global__ __launch_bounds__(JENT_T) void k_jent_check(JentParams p) {
     const int64_t i = blockIdx.x;
     ParImage im;
     if (!p.ws.img[4 * i] || !jent_open(p, i, im)) return;
-    const uint8_t *rec = p.rec + p.desc[8 * i + 2];
-    const uint16_t *quant = reinterpret_cast<const uint16_t *>(rec);
-    const int16_t *coef = reinterpret_cast<const int16_t *>(rec + LEMON_JPEG_QUANT_BYTES);
-    bool bad = false;
-    for (int64_t b = (int64_t)blockIdx.y * JENT_T + threadIdx.x; b < im.g.blocks; b += (int64_t)JENT_ZY * JENT_T) {
-        const int c = b < im.g.n0 ? 0 : (b < im.g.n0 + im.g.nc ? 1 : 2);
-        if (par_check_block(coef + 64 * b, quant + 64 * c) != LEMON_JPEG_OK) bad = true;
-    }
-    if (bad) atomicMax(p.status + i, (int)LEMON_JPEG_ENVELOPE);
+    if (!par_envelope_blocks(p.rec + p.desc[8 * i + 2], im.g, (int64_t)blockIdx.y * JENT_T + threadIdx.x, (int64_t)JENT_ZY * JENT_T))
+        atomicMax(p.status + i, (int)LEMON_JPEG_ENVELOPE);
 }
 
 }  // namespace

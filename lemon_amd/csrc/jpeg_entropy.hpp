@@ -5,6 +5,9 @@
 //
 // The input is untrusted: every read is checked against the end of the buffer, every table index is validated, and anything
 // the decoder does not fully support is DECLINED with a status code (the caller then decodes with PIL), never guessed at.
+// Four pieces here serve every JPEG path, the progressive and the device ones included, so that a check exists once:
+// jpeg_build_huff (a Huffman table from counts and values), read_to_sos (the marker-segment loop), frame_checks (sampling,
+// colour ids, geometry) and envelope_verdict / block_in_envelope (the arithmetic envelope of a finished block).
 //
 // Record written for an accepted file (LemonJpegInfo::record_bytes = 384 + 128 * blocks):
 //   uint16 quant[3][64]      the quantisation table of each component, natural order (unused components: zeros)
@@ -42,24 +45,30 @@ static const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-struct Huff {
-    bool defined = false;
-    uint8_t vals[256];
+// ---- Huffman tables.  The ONE construction and validation of a table from (16 counts, values); every path that reads a DHT
+// segment or a packet's specification goes through it.  Callers: read_to_sos below (both parsers), par_build_huff
+// (jpeg_par.hpp: the baseline kernels and their host loop), prog_build_huff (jpeg_prog_par.hpp: the progressive ones).
+struct ParHuff {                      // what the device decodes with
+    uint16_t look[512];               // 9-bit prefix -> (length << 8 | value), 0 when the code is longer
     int32_t maxcode[18];              // largest code of each length, -1 when none
     int32_t valptr[17];               // index of the first value of each length, minus its first code
-    uint16_t look[512];               // 9-bit prefix -> (length << 8 | value), 0 when the code is longer
-    // AC tables: 10-bit prefix -> a whole (run, size) symbol WITH its magnitude bits when both fit the prefix:
-    // value << 16 | is_coefficient << 12 | run << 8 | bits consumed; 0 when they do not fit
-    int32_t fast[1024];
+    uint8_t vals[256];
 };
 
-// counts[1..16], n values.  False when the counts do not describe a prefix code.
-static inline bool build_huff(const uint8_t *counts, const uint8_t *vals, int n, Huff &h) {
-    memset(h.look, 0, sizeof(h.look));
-    memcpy(h.vals, vals, (size_t)n);
+// counts[0..15]: codes of length 1..16; vals[0, avail): their values.  Always initialises all of `h`; false when the counts ask
+// for more than 256 values or for values past `avail`, or describe no prefix code (`h` then holds the lengths before the fault).
+LEMON_JPEG_HD bool jpeg_build_huff(const uint8_t *counts, const uint8_t *vals, int64_t avail, ParHuff &h) {
+    for (int i = 0; i < 512; ++i) h.look[i] = 0;
+    for (int i = 0; i < 256; ++i) h.vals[i] = 0;
+    for (int l = 0; l < 17; ++l) { h.maxcode[l] = -1; h.valptr[l] = 0; }
+    h.maxcode[17] = 0x7fffffff;
+    int32_t total = 0;
+    for (int l = 0; l < 16; ++l) total += counts[l];
+    if (total > 256 || total > avail) return false;
+    for (int i = 0; i < total; ++i) h.vals[i] = vals[i];
     int32_t code = 0, k = 0;
     for (int l = 1; l <= 16; ++l) {
-        const int c = counts[l];
+        const int c = counts[l - 1];
         if (code + c > (1 << l)) return false;
         h.valptr[l] = k - code;
         h.maxcode[l] = c ? code + c - 1 : -1;
@@ -71,8 +80,17 @@ static inline bool build_huff(const uint8_t *counts, const uint8_t *vals, int n,
         code += c; k += c;
         code <<= 1;
     }
-    h.maxcode[17] = 0x7fffffff;
-    h.defined = true;
+    return true;
+}
+
+struct Huff : ParHuff {               // the sequential pass's table: ParHuff plus
+    bool defined = false;
+    // AC tables: 10-bit prefix -> a whole (run, size) symbol WITH its magnitude bits when both fit the prefix:
+    // value << 16 | is_coefficient << 12 | run << 8 | bits consumed; 0 when they do not fit
+    int32_t fast[1024];
+};
+
+static inline void build_fast(Huff &h) {
     for (int32_t i = 0; i < 1024; ++i) {
         h.fast[i] = 0;
         const uint32_t e = h.look[i >> 1];
@@ -87,7 +105,6 @@ static inline bool build_huff(const uint8_t *counts, const uint8_t *vals, int n,
         if (v < (1 << (sz - 1))) v -= (1 << sz) - 1;
         h.fast[i] = (int32_t)((uint32_t)v << 16) | (1 << 12) | (r << 8) | (l + sz);
     }
-    return true;
 }
 
 struct Frame {
@@ -97,16 +114,21 @@ struct Frame {
     int32_t restart = 0;
     bool q_defined[4] = {false, false, false, false};
     uint16_t q[4][64];                // natural order
-    Huff dc[4], ac[4];
     size_t scan = 0;                  // first byte of the entropy-coded segment
 };
 
 static inline int rd16(const uint8_t *d, size_t p) { return (d[p] << 8) | d[p + 1]; }
 
-// Markers from SOI up to and including SOS.  Fills `info` (geometry, quantisers, record size) when it returns LEMON_JPEG_OK.
-static inline int parse_header(const uint8_t *d, size_t n, Frame &f, LemonJpegInfo *info) {
-    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return LEMON_JPEG_NOT_JPEG;
-    size_t p = 2;
+// The ONE marker-segment loop.  From the marker at d[p] on it applies DQT, DHT, DRI, SOFn, APP0 "JFIF" and APP14 "Adobe" to `f`
+// and skips the other APPn and COM, up to the next SOS: LEMON_JPEG_OK with its payload in s[0, sl) and p behind the segment.
+// sof2: the frame must be SOF2 (progressive), else SOF0 / SOF1; every other process is LEMON_JPEG_PROCESS.  after_scan (a
+// progressive file past its first scan): EOI ends the loop too (`eoi`), and a JFIF marker no longer counts.  A DHT table that
+// is a prefix code of at most 256 values inside its segment (and, for DC, of categories <= 11) is handed to
+// on_table(tc, th, table, offset of its 16 counts in d).  Callers: parse_header below, lemon_jpeg_prog::parse (jpeg_prog.hpp).
+template <class OnTable>
+static inline int read_to_sos(const uint8_t *d, size_t n, size_t &p, Frame &f, bool sof2, bool after_scan, OnTable on_table,
+                              const uint8_t *&s, size_t &sl, bool &eoi) {
+    eoi = false;
     for (;;) {
         if (p + 2 > n) return LEMON_JPEG_TRUNCATED;
         if (d[p] != 0xFF) return LEMON_JPEG_MARKER;
@@ -114,18 +136,20 @@ static inline int parse_header(const uint8_t *d, size_t n, Frame &f, LemonJpegIn
         if (p + 2 > n) return LEMON_JPEG_TRUNCATED;
         const int m = d[p + 1];
         p += 2;
-        if (m == 0xC2 || m == 0xC3 || (m >= 0xC5 && m <= 0xCF && m != 0xC4 && m != 0xC8) || m == 0xDC || m == 0xDE || m == 0xDF)
-            return LEMON_JPEG_PROCESS;
-        const bool segment = m == 0xC0 || m == 0xC1 || m == 0xC4 || m == 0xDA || m == 0xDB || m == 0xDD || (m >= 0xE0 && m <= 0xEF) || m == 0xFE;
-        if (!segment) return LEMON_JPEG_MARKER;         // SOI again, EOI, RSTn, TEM, reserved: none belongs in the header
+        if (m == 0xD9 && after_scan) { eoi = true; return LEMON_JPEG_OK; }
+        const bool sof = sof2 ? m == 0xC2 : (m == 0xC0 || m == 0xC1);
+        if (!sof && ((m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8) || m == 0xDC || m == 0xDE || m == 0xDF))
+            return LEMON_JPEG_PROCESS;                  // another SOFn, DAC, DNL, DHP, EXP
+        const bool segment = sof || m == 0xC4 || m == 0xDA || m == 0xDB || m == 0xDD || (m >= 0xE0 && m <= 0xEF) || m == 0xFE;
+        if (!segment) return LEMON_JPEG_MARKER;         // SOI again, EOI, RSTn, TEM, reserved: none belongs between segments
         if (p + 2 > n) return LEMON_JPEG_TRUNCATED;
         const size_t len = (size_t)rd16(d, p);
         if (len < 2 || len > n - p) return LEMON_JPEG_TRUNCATED;
-        const uint8_t *s = d + p + 2;
-        const size_t sl = len - 2;
+        s = d + p + 2;
+        sl = len - 2;
         p += len;
         if (m == 0xE0) {
-            if (sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) f.jfif = true;
+            if (!after_scan && sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) f.jfif = true;
         } else if (m == 0xEE) {
             if (sl >= 5 && memcmp(s, "Adobe", 5) == 0) return LEMON_JPEG_COLOUR;
         } else if (m == 0xDB) {
@@ -144,20 +168,19 @@ static inline int parse_header(const uint8_t *d, size_t n, Frame &f, LemonJpegIn
                 if (sl - o < 17) return LEMON_JPEG_TABLE;
                 const int tc = s[o] >> 4, th = s[o] & 15;
                 if (tc > 1 || th > 3) return LEMON_JPEG_TABLE;
-                uint8_t counts[17];
+                ParHuff t;
+                if (!jpeg_build_huff(s + o + 1, s + o + 17, (int64_t)(sl - o - 17), t)) return LEMON_JPEG_TABLE;
                 int total = 0;
-                counts[0] = 0;
-                for (int l = 1; l <= 16; ++l) { counts[l] = s[o + l]; total += counts[l]; }
-                if (total > 256 || sl - o - 17 < (size_t)total) return LEMON_JPEG_TABLE;
+                for (int l = 1; l <= 16; ++l) total += s[o + l];
                 for (int i = 0; i < total; ++i)
-                    if (tc == 0 && s[o + 17 + i] > 11) return LEMON_JPEG_TABLE;     // a DC category beyond 8-bit samples
-                if (!build_huff(counts, s + o + 17, total, tc ? f.ac[th] : f.dc[th])) return LEMON_JPEG_TABLE;
+                    if (tc == 0 && t.vals[i] > 11) return LEMON_JPEG_TABLE;         // a DC category beyond 8-bit samples
+                on_table(tc, th, t, (size_t)(s + o + 1 - d));
                 o += 17 + (size_t)total;
             }
         } else if (m == 0xDD) {
             if (sl != 2) return LEMON_JPEG_TABLE;
             f.restart = rd16(s, 0);
-        } else if (m == 0xC0 || m == 0xC1) {
+        } else if (sof) {
             if (f.have_sof) return LEMON_JPEG_MARKER;
             if (sl < 6) return LEMON_JPEG_TRUNCATED;
             if (s[0] != 8) return LEMON_JPEG_PRECISION;
@@ -171,21 +194,15 @@ static inline int parse_header(const uint8_t *d, size_t n, Frame &f, LemonJpegIn
             }
             f.have_sof = true; f.sof1 = m == 0xC1;
         } else if (m == 0xDA) {
-            if (!f.have_sof) return LEMON_JPEG_MARKER;
-            if (sl < 1 || s[0] != f.nc || sl != (size_t)(4 + 2 * f.nc)) return LEMON_JPEG_SCAN;
-            for (int c = 0; c < f.nc; ++c) {
-                if (s[1 + 2 * c] != f.id[c]) return LEMON_JPEG_SCAN;
-                f.td[c] = s[2 + 2 * c] >> 4; f.ta[c] = s[2 + 2 * c] & 15;
-                const int lim = f.sof1 ? 3 : 1;
-                if (f.td[c] > lim || f.ta[c] > lim || !f.dc[f.td[c]].defined || !f.ac[f.ta[c]].defined) return LEMON_JPEG_TABLE;
-                if (!f.q_defined[f.tq[c]]) return LEMON_JPEG_TABLE;
-            }
-            if (s[1 + 2 * f.nc] != 0 || s[2 + 2 * f.nc] != 63 || s[3 + 2 * f.nc] != 0) return LEMON_JPEG_SCAN;
-            f.scan = p;
-            break;
+            return f.have_sof ? LEMON_JPEG_OK : LEMON_JPEG_MARKER;
         }
         // APPn other than the two above, COM: skipped
     }
+}
+
+// What a frame must satisfy beyond its segments' own syntax: sampling, colour ids, geometry; fills the geometry fields of
+// `info` (not the quantisers).  Callers: parse_header (after its SOS), lemon_jpeg_prog::parse (at its first SOS).
+static inline int frame_checks(const Frame &f, LemonJpegInfo *info) {
     int hs = 1, vs = 1;
     if (f.nc == 3) {
         hs = f.hs[0]; vs = f.vs[0];
@@ -202,6 +219,40 @@ static inline int parse_header(const uint8_t *d, size_t n, Frame &f, LemonJpegIn
     info->mcus_x = f.nc == 3 ? g.bwc : g.bw0; info->mcus_y = f.nc == 3 ? g.bhc : g.bh0;
     info->blocks = g.blocks;
     info->record_bytes = LEMON_JPEG_QUANT_BYTES + 128 * g.blocks;
+    return LEMON_JPEG_OK;
+}
+
+struct BaseFile {                     // a baseline file's frame and the tables its one scan decodes with
+    Frame f;
+    Huff dc[4], ac[4];
+};
+
+// Markers from SOI up to and including SOS.  Fills `info` (geometry, quantisers, record size) when it returns LEMON_JPEG_OK.
+static inline int parse_header(const uint8_t *d, size_t n, BaseFile &bf, LemonJpegInfo *info) {
+    Frame &f = bf.f;
+    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return LEMON_JPEG_NOT_JPEG;
+    size_t p = 2, sl = 0;
+    const uint8_t *s = nullptr;
+    bool eoi;
+    const int rc = read_to_sos(d, n, p, f, false, false, [&bf](int tc, int th, const ParHuff &t, size_t) {
+        Huff &h = tc ? bf.ac[th] : bf.dc[th];
+        static_cast<ParHuff &>(h) = t;
+        h.defined = true;
+        build_fast(h);
+    }, s, sl, eoi);
+    if (rc != LEMON_JPEG_OK) return rc;
+    if (sl < 1 || s[0] != f.nc || sl != (size_t)(4 + 2 * f.nc)) return LEMON_JPEG_SCAN;
+    for (int c = 0; c < f.nc; ++c) {
+        if (s[1 + 2 * c] != f.id[c]) return LEMON_JPEG_SCAN;
+        f.td[c] = s[2 + 2 * c] >> 4; f.ta[c] = s[2 + 2 * c] & 15;
+        const int lim = f.sof1 ? 3 : 1;
+        if (f.td[c] > lim || f.ta[c] > lim || !bf.dc[f.td[c]].defined || !bf.ac[f.ta[c]].defined) return LEMON_JPEG_TABLE;
+        if (!f.q_defined[f.tq[c]]) return LEMON_JPEG_TABLE;
+    }
+    if (s[1 + 2 * f.nc] != 0 || s[2 + 2 * f.nc] != 63 || s[3 + 2 * f.nc] != 0) return LEMON_JPEG_SCAN;
+    f.scan = p;
+    const int fc = frame_checks(f, info);
+    if (fc != LEMON_JPEG_OK) return fc;
     memset(info->quant, 0, sizeof(info->quant));
     for (int c = 0; c < f.nc; ++c) memcpy(info->quant[c], f.q[f.tq[c]], 128);
     return LEMON_JPEG_OK;
@@ -294,7 +345,29 @@ static inline int32_t receive_extend(Bits &b, int s) {
 // An image with a block outside is declined (LEMON_JPEG_ENVELOPE).
 static const int32_t kEnvelopeQuick = 4000;
 
-static inline int decode_scan(const uint8_t *d, size_t n, const Frame &f, LemonJpegInfo *info, uint8_t *record) {
+// The ONE verdict on a finished block: D = |d[0]|, A = the sum of |d| over the other 63 dequantised coefficients.  `exact`
+// counts the blocks that needed the exact form.  Callers: decode_scan (which sums D and A while it decodes), block_in_envelope.
+LEMON_JPEG_HD bool envelope_verdict(int64_t D, int64_t A, const int16_t *blk, const uint16_t *qt, int32_t &exact) {
+    if (D + 2 * A <= kEnvelopeQuick) return true;
+    ++exact;
+    return jpeg_block_in_envelope(blk, qt);
+}
+
+// ... of a block in memory; `max_abs` takes the largest |d| seen (|d| <= 32768 * 65535 < 2^31).  Callers: par_envelope_blocks
+// (jpeg_par.hpp: the host loops and the kernels of both parallel passes), lemon_jpeg_prog::seq_decode (jpeg_prog.hpp).
+LEMON_JPEG_HD bool block_in_envelope(const int16_t *blk, const uint16_t *qt, int32_t &max_abs, int32_t &exact) {
+    int64_t A = 0;
+    int32_t D = 0;
+    for (int i = 0; i < 64; ++i) {
+        const int32_t v = blk[i], a = (v < 0 ? -v : v) * (int32_t)qt[i];
+        if (a > max_abs) max_abs = a;
+        if (i) A += a; else D = a;
+    }
+    return envelope_verdict(D, A, blk, qt, exact);
+}
+
+static inline int decode_scan(const uint8_t *d, size_t n, const BaseFile &bf, LemonJpegInfo *info, uint8_t *record) {
+    const Frame &f = bf.f;
     JpegGeom g;
     if (!jpeg_geometry(info->width, info->height, info->components, info->hs, info->vs, g)) return LEMON_JPEG_DIMENSION;
     memcpy(record, info->quant, LEMON_JPEG_QUANT_BYTES);
@@ -309,7 +382,6 @@ static inline int decode_scan(const uint8_t *d, size_t n, const Frame &f, LemonJ
     int32_t pred[3] = {0, 0, 0};
     int32_t max_abs = 0, exact = 0;
     int64_t todo = f.restart, mcu = 0;
-    const int64_t mcus = (int64_t)mx * my;
     for (int32_t yy = 0; yy < my; ++yy)
         for (int32_t xx = 0; xx < mx; ++xx, ++mcu) {
             if (f.restart && todo == 0) {
@@ -326,7 +398,7 @@ static inline int decode_scan(const uint8_t *d, size_t n, const Frame &f, LemonJ
                 todo = f.restart;
             }
             for (int c = 0; c < nc; ++c) {
-                const Huff &hd = f.dc[f.td[c]], &ha = f.ac[f.ta[c]];
+                const Huff &hd = bf.dc[f.td[c]], &ha = bf.ac[f.ta[c]];
                 const uint16_t *qt = info->quant[c];
                 for (int by = 0; by < ch[c]; ++by)
                     for (int bx = 0; bx < cw[c]; ++bx) {
@@ -380,15 +452,11 @@ static inline int decode_scan(const uint8_t *d, size_t n, const Frame &f, LemonJ
                             ++k;
                         }
                         if (b.overrun()) return LEMON_JPEG_STREAM;
-                        if ((int64_t)D + 2 * A > kEnvelopeQuick) {
-                            ++exact;
-                            if (!jpeg_block_in_envelope(blk, qt)) return LEMON_JPEG_ENVELOPE;
-                        }
+                        if (!envelope_verdict(D, A, blk, qt, exact)) return LEMON_JPEG_ENVELOPE;
                     }
             }
             if (f.restart) --todo;
         }
-    (void)mcus;
     // after the last MCU: padding only, then (fill bytes and) EOI
     if (b.overrun() || b.real_bits() >= 8) return LEMON_JPEG_STREAM;
     b.fill();
@@ -407,7 +475,7 @@ static inline int decode_scan(const uint8_t *d, size_t n, const Frame &f, LemonJ
 static inline int lemon_jpeg_info_impl(const uint8_t *data, int64_t n, LemonJpegInfo *info) {
     memset(info, 0, sizeof(*info));
     if (!data || n < 0) return info->status = LEMON_JPEG_NOT_JPEG;
-    lemon_jpeg::Frame *f = new lemon_jpeg::Frame();
+    lemon_jpeg::BaseFile *f = new lemon_jpeg::BaseFile();
     const int rc = lemon_jpeg::parse_header(data, (size_t)n, *f, info);
     delete f;
     return info->status = rc;
@@ -418,7 +486,7 @@ static inline int lemon_jpeg_info_impl(const uint8_t *data, int64_t n, LemonJpeg
 static inline int lemon_jpeg_entropy_impl(const uint8_t *data, int64_t n, uint8_t *record, int64_t record_cap, LemonJpegInfo *info) {
     memset(info, 0, sizeof(*info));
     if (!data || n < 0) return info->status = LEMON_JPEG_NOT_JPEG;
-    lemon_jpeg::Frame *f = new lemon_jpeg::Frame();
+    lemon_jpeg::BaseFile *f = new lemon_jpeg::BaseFile();
     int rc = lemon_jpeg::parse_header(data, (size_t)n, *f, info);
     if (rc == LEMON_JPEG_OK && (!record || info->record_bytes > record_cap)) rc = LEMON_JPEG_BUFFER;
     if (rc == LEMON_JPEG_OK) rc = lemon_jpeg::decode_scan(data, (size_t)n, *f, info, record);

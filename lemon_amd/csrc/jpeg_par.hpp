@@ -2,6 +2,9 @@
 // per-symbol decode step that the device kernels (jpeg_entropy.hip) and the host loop (lemon_jpeg_entropy_par_host) share.
 // `LEMON_JPEG_HD` functions compile for both; the host loop below runs the lanes one after another with the same workgroup
 // and round structure as the kernels, so both give the same record AND the same status.  Plain C++17, no HIP needed.
+// Also here, for the progressive path too (jpeg_prog.hpp, jpeg_prog_par.hpp, jpeg_prog.hip): the scan walker of both packers
+// (walk_scan), the geometry both packets open with (packet_geometry), interval_mcus, the envelope loop and the record
+// initialisation of both passes.  The Huffman table builder is jpeg_entropy.hpp's (jpeg_build_huff), the parsers' own.
 //
 // Packet (little endian, every section at a multiple of 16, the whole a multiple of 16 bytes):
 //   int32  head[32]          kPk* indices below: magic, geometry, restart interval, interval count, scan bytes, section offsets,
@@ -35,6 +38,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <vector>
+
 #include "jpeg_entropy.hpp"
 
 // (include/lemon_hip.h: LEMON_JPEG_SYNC, LEMON_JPEG_PACKET_BOUND = header 128 + quantisers 384 + tables 2176 + section padding,
@@ -64,10 +69,56 @@ static inline void huff_spec(const lemon_jpeg::Huff &h, uint8_t *spec) {
     memcpy(spec + 16, h.vals, (size_t)k);
 }
 
+// The ONE walk over the entropy-coded bytes of a scan, from d[p] to the marker that ends it (p is left at that marker's FF, fill
+// bytes skipped; the caller decides which marker it accepts).  It destuffs FF 00, sequences RSTn modulo 8 over `nivl` intervals
+// and declines (LEMON_JPEG_STREAM) an empty interval, a fill byte before data, a wrong or surplus RSTn, and an end before the
+// last interval.  COPY writes the destuffed bytes to out[0, cap) (LEMON_JPEG_BUFFER when they do not fit); with several
+// intervals on_end(ivl, o) receives the destuffed offset o at which interval ivl ends.  Callers: pack below (baseline: one
+// scan, must end at EOI), lemon_jpeg_prog::parse (COPY = false: sizes only) and lemon_jpeg_prog::pack (jpeg_prog.hpp).
+template <bool COPY, class OnEnd>
+static inline int walk_scan(const uint8_t *d, size_t n, size_t &p, int32_t restart, int64_t nivl, uint8_t *out, int64_t cap, OnEnd on_end,
+                            int64_t &bytes) {
+    int64_t o = 0, ivl = 0, start = 0;
+    bool fill = false;
+    for (;;) {
+        if (p >= n) return LEMON_JPEG_STREAM;
+        if (d[p] != 0xFF) {                                          // the run of plain bytes up to the next FF, at once
+            if (fill) return LEMON_JPEG_STREAM;
+            const void *ff = memchr(d + p, 0xFF, n - p);
+            const int64_t run = ff ? (int64_t)(static_cast<const uint8_t *>(ff) - (d + p)) : (int64_t)(n - p);
+            if (COPY) {
+                if (run > cap - o) return LEMON_JPEG_BUFFER;
+                memcpy(out + o, d + p, (size_t)run);
+            }
+            o += run; p += (size_t)run;
+            continue;
+        }
+        if (p + 1 >= n) return LEMON_JPEG_STREAM;
+        const uint8_t m = d[p + 1];
+        if (m == 0xFF) { fill = true; ++p; continue; }               // a fill byte: only a marker may follow
+        if (m == 0) {
+            if (fill) return LEMON_JPEG_STREAM;
+            if (COPY) {
+                if (o >= cap) return LEMON_JPEG_BUFFER;
+                out[o] = 0xFF;
+            }
+            ++o; p += 2;
+            continue;
+        }
+        if (o == start) return LEMON_JPEG_STREAM;                    // an interval without a byte
+        const bool rst = m >= 0xD0 && m <= 0xD7;
+        if (rst ? (!restart || ivl + 1 >= nivl || m != (uint8_t)(0xD0 + (ivl & 7))) : ivl != nivl - 1) return LEMON_JPEG_STREAM;
+        if (nivl > 1) on_end(ivl, o);
+        if (!rst) { bytes = o; return LEMON_JPEG_OK; }
+        ++ivl; start = o; p += 2; fill = false;
+    }
+}
+
 static inline int pack(const uint8_t *d, size_t n, uint8_t *pkt, int64_t cap, LemonJpegInfo *info, int64_t *packet_bytes,
-                       lemon_jpeg::Frame &f) {
+                       lemon_jpeg::BaseFile &bf) {
     using namespace lemon_jpeg;
-    int rc = parse_header(d, n, f, info);
+    const Frame &f = bf.f;
+    int rc = parse_header(d, n, bf, info);
     if (rc != LEMON_JPEG_OK) return rc;
     if (!pkt || n >= ((size_t)1 << 31)) return LEMON_JPEG_BUFFER;
     const int64_t mcus = (int64_t)info->mcus_x * info->mcus_y;
@@ -76,115 +127,47 @@ static inline int pack(const uint8_t *d, size_t n, uint8_t *pkt, int64_t cap, Le
     if (scan_off > cap) return nivl * 3 > (int64_t)n ? LEMON_JPEG_STREAM : LEMON_JPEG_BUFFER;   // (more intervals than bytes)
     memset(pkt, 0, (size_t)scan_off);
     uint16_t *len16 = reinterpret_cast<uint16_t *>(pkt + kLenOff);
-    // the intervals of 65535 bytes or more are appended after the scan; until then they are kept here (8 bytes each, found at
-    // most once per 64 KB of input)
-    uint32_t *big = nullptr;
-    int64_t nbig = 0, big_cap = 0;
+    // the intervals of 65535 bytes or more are appended after the scan (8 bytes each, found at most once per 64 KB of input)
+    std::vector<uint32_t> big;
     size_t p = f.scan;
-    int64_t o = scan_off, ivl = 0, start = scan_off;
-    bool fill = false;
-    rc = LEMON_JPEG_OK;
-    for (;;) {
-        if (p >= n) { rc = LEMON_JPEG_STREAM; break; }
-        const uint8_t c = d[p];
-        if (c != 0xFF) {                                             // the run of plain bytes up to the next FF, at once
-            if (fill) { rc = LEMON_JPEG_STREAM; break; }
-            const void *ff = memchr(d + p, 0xFF, n - p);
-            const int64_t run = ff ? (int64_t)(static_cast<const uint8_t *>(ff) - (d + p)) : (int64_t)(n - p);
-            if (run > cap - o) { rc = LEMON_JPEG_BUFFER; break; }
-            memcpy(pkt + o, d + p, (size_t)run);
-            o += run; p += (size_t)run;
-            continue;
-        }
-        if (p + 1 >= n) { rc = LEMON_JPEG_STREAM; break; }
-        const uint8_t m = d[p + 1];
-        if (m == 0xFF) { fill = true; ++p; continue; }               // a fill byte: only a marker may follow
-        if (m == 0) {
-            if (fill) { rc = LEMON_JPEG_STREAM; break; }
-            if (o >= cap) { rc = LEMON_JPEG_BUFFER; break; }
-            pkt[o++] = 0xFF; p += 2;
-            continue;
-        }
+    int64_t scan_bytes = 0, start = 0;
+    rc = walk_scan<true>(d, n, p, f.restart, nivl, pkt + scan_off, cap - scan_off, [&](int64_t ivl, int64_t o) {
         const int64_t len = o - start;
-        const bool eoi = m == 0xD9;
-        const bool rst = f.restart && ivl + 1 < nivl && m == (uint8_t)(0xD0 + (ivl & 7));
-        if (len == 0 || (eoi && ivl != nivl - 1) || (!eoi && !rst)) { rc = LEMON_JPEG_STREAM; break; }
-        if (nivl > 1) {
-            len16[ivl] = (uint16_t)(len < 0xFFFF ? len : 0xFFFF);
-            if (len >= 0xFFFF) {
-                if (nbig == big_cap) {
-                    big_cap = big_cap ? 2 * big_cap : 16;
-                    uint32_t *g = new uint32_t[2 * big_cap];
-                    if (big) { memcpy(g, big, (size_t)nbig * 8); delete[] big; }
-                    big = g;
-                }
-                big[2 * nbig] = (uint32_t)ivl; big[2 * nbig + 1] = (uint32_t)len; ++nbig;
-            }
-        }
-        if (eoi) break;
-        ++ivl; start = o; p += 2; fill = false;
-    }
-    const int64_t scan_bytes = o - scan_off;
+        start = o;
+        len16[ivl] = (uint16_t)(len < 0xFFFF ? len : 0xFFFF);
+        if (len >= 0xFFFF) { big.push_back((uint32_t)ivl); big.push_back((uint32_t)len); }
+    }, scan_bytes);
+    if (rc != LEMON_JPEG_OK) return rc;
+    if (d[p + 1] != 0xD9) return LEMON_JPEG_STREAM;                  // one scan: nothing but EOI may end it
+    const int64_t nbig = (int64_t)big.size() / 2, o = scan_off + scan_bytes;
     const int64_t big_off = (o + 15) & ~(int64_t)15;
     const int64_t total = (big_off + 8 * nbig + 15) & ~(int64_t)15;
-    if (rc == LEMON_JPEG_OK && total > cap) rc = LEMON_JPEG_BUFFER;
-    if (rc == LEMON_JPEG_OK) {
-        memset(pkt + o, 0, (size_t)(total - o));
-        if (nbig) memcpy(pkt + big_off, big, (size_t)nbig * 8);
-        int32_t head[kPkHeadInts];
-        memset(head, 0, sizeof(head));
-        head[kPkMagic] = kMagic; head[kPkWidth] = info->width; head[kPkHeight] = info->height;
-        head[kPkComponents] = info->components; head[kPkHs] = info->hs; head[kPkVs] = info->vs; head[kPkRestart] = f.restart;
-        head[kPkIntervals] = (int32_t)nivl; head[kPkScanBytes] = (int32_t)scan_bytes; head[kPkLenOff] = kLenOff;
-        head[kPkScanOff] = (int32_t)scan_off; head[kPkBigOff] = (int32_t)big_off; head[kPkBig] = (int32_t)nbig;
-        head[kPkTotal] = (int32_t)total;
-        for (int c = 0; c < info->components; ++c) { head[kPkTd0 + c] = f.td[c]; head[kPkTa0 + c] = f.ta[c]; }
-        memcpy(pkt, head, sizeof(head));
-        memcpy(pkt + kQuantOff, info->quant, LEMON_JPEG_QUANT_BYTES);
-        for (int s = 0; s < 4; ++s) {
-            huff_spec(f.dc[s], pkt + kHuffOff + s * kHuffSpec);
-            huff_spec(f.ac[s], pkt + kHuffOff + (4 + s) * kHuffSpec);
-        }
-        if (packet_bytes) *packet_bytes = total;
+    if (total > cap) return LEMON_JPEG_BUFFER;
+    memset(pkt + o, 0, (size_t)(total - o));
+    if (nbig) memcpy(pkt + big_off, big.data(), (size_t)nbig * 8);
+    int32_t head[kPkHeadInts];
+    memset(head, 0, sizeof(head));
+    head[kPkMagic] = kMagic; head[kPkWidth] = info->width; head[kPkHeight] = info->height;
+    head[kPkComponents] = info->components; head[kPkHs] = info->hs; head[kPkVs] = info->vs; head[kPkRestart] = f.restart;
+    head[kPkIntervals] = (int32_t)nivl; head[kPkScanBytes] = (int32_t)scan_bytes; head[kPkLenOff] = kLenOff;
+    head[kPkScanOff] = (int32_t)scan_off; head[kPkBigOff] = (int32_t)big_off; head[kPkBig] = (int32_t)nbig;
+    head[kPkTotal] = (int32_t)total;
+    for (int c = 0; c < info->components; ++c) { head[kPkTd0 + c] = f.td[c]; head[kPkTa0 + c] = f.ta[c]; }
+    memcpy(pkt, head, sizeof(head));
+    memcpy(pkt + kQuantOff, info->quant, LEMON_JPEG_QUANT_BYTES);
+    for (int s = 0; s < 4; ++s) {
+        huff_spec(bf.dc[s], pkt + kHuffOff + s * kHuffSpec);
+        huff_spec(bf.ac[s], pkt + kHuffOff + (4 + s) * kHuffSpec);
     }
-    delete[] big;
-    return rc;
+    if (packet_bytes) *packet_bytes = total;
+    return LEMON_JPEG_OK;
 }
 
 // ------------------------------------------------------------------------------------------- shared decode step (host + device)
-struct ParHuff {                      // what build_huff derives from (counts, values), without the AC fast table
-    uint16_t look[512];               // 9-bit prefix -> (length << 8 | value), 0 when the code is longer
-    int32_t maxcode[18];
-    int32_t valptr[17];
-    uint8_t vals[256];
-};
+using lemon_jpeg::ParHuff;
 
-// spec: 16 counts, 256 values.  False when the counts describe no prefix code or more than 256 values.
-LEMON_JPEG_HD bool par_build_huff(const uint8_t *spec, ParHuff &h) {
-    for (int i = 0; i < 512; ++i) h.look[i] = 0;
-    for (int i = 0; i < 256; ++i) h.vals[i] = spec[16 + i];
-    int32_t total = 0;
-    for (int l = 0; l < 16; ++l) total += spec[l];
-    bool ok = total <= 256;
-    int32_t code = 0, k = 0;
-    h.maxcode[0] = -1; h.valptr[0] = 0;
-    for (int l = 1; l <= 16; ++l) {
-        const int c = ok ? spec[l - 1] : 0;
-        if (code + c > (1 << l)) { ok = false; }
-        const int cc = ok ? c : 0;
-        h.valptr[l] = k - code;
-        h.maxcode[l] = cc ? code + cc - 1 : -1;
-        if (l <= 9)
-            for (int i = 0; i < cc; ++i) {
-                const int32_t first = (code + i) << (9 - l);
-                for (int32_t j = 0; j < (1 << (9 - l)); ++j) h.look[first + j] = (uint16_t)((l << 8) | spec[16 + k + i]);
-            }
-        code += cc; k += cc;
-        code <<= 1;
-    }
-    h.maxcode[17] = 0x7fffffff;
-    return ok;
-}
+// spec: 16 counts, 256 values (a specification of the packet)
+LEMON_JPEG_HD bool par_build_huff(const uint8_t *spec, ParHuff &h) { return lemon_jpeg::jpeg_build_huff(spec, spec + 16, 256, h); }
 
 // 32 bits of the interval d[0, len) from bit position `bit` on, MSB first; zeros past the end.  A window of 8 bytes is kept and
 // reloaded (one 8-byte load while 8 bytes remain, else byte by byte) when `bit` leaves its first 32 bits.
@@ -233,12 +216,39 @@ LEMON_JPEG_HD int32_t par_extend(uint32_t w, int l, int s) {         // s >= 1 m
     return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
-struct ParImage {                     // a validated packet
-    int32_t w, h, nc, hs, vs, restart, nivl, nbig;
-    int32_t spm, luma;                // blocks per MCU, of which luma
-    int32_t mx, my;
-    int64_t mcus, scan_bytes;
+// The geometry both packet formats open with: head ints 1..5 are width, height, components, hs, vs (int 0 is the magic).
+struct PacketGeom {
+    int32_t w, h, nc, hs, vs;
+    int32_t spm, luma;                // blocks per interleaved MCU, of which luma
+    int32_t mx, my;                   // the MCU grid
+    int64_t mcus;
     JpegGeom g;
+};
+
+// false when the head describes no accepted geometry or the record it needs exceeds `rec_room`.  Callers: par_open below,
+// lemon_jpeg_prog::prog_open (jpeg_prog_par.hpp).
+LEMON_JPEG_HD bool packet_geometry(const int32_t *hd, int64_t rec_room, PacketGeom &im) {
+    im.w = hd[1]; im.h = hd[2]; im.nc = hd[3]; im.hs = hd[4]; im.vs = hd[5];
+    if (!jpeg_geometry(im.w, im.h, im.nc, im.hs, im.vs, im.g)) return false;
+    if (rec_room < LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks) return false;
+    im.luma = im.nc == 3 ? im.hs * im.vs : 1;
+    im.spm = im.nc == 3 ? im.luma + 2 : 1;
+    im.mx = im.nc == 3 ? im.g.bwc : im.g.bw0; im.my = im.nc == 3 ? im.g.bhc : im.g.bh0;
+    im.mcus = (int64_t)im.mx * im.my;
+    return true;
+}
+
+// Restart interval t of a scan of `mcus` MCUs -> its first MCU and its MCU count (restart 0: one interval).  Callers: the lanes
+// of lemon_jpeg_entropy_par_host_impl and jent_lane (jpeg_entropy.hip), prog_item (jpeg_prog_par.hpp), seq_decode (jpeg_prog.hpp).
+struct McuRange { int64_t first, count; };
+LEMON_JPEG_HD McuRange interval_mcus(int32_t restart, int64_t mcus, int64_t t) {
+    const int64_t mcu0 = restart ? t * restart : 0;
+    return {mcu0, restart && mcus - mcu0 > restart ? restart : mcus - mcu0};
+}
+
+struct ParImage : PacketGeom {        // a validated packet
+    int32_t restart, nivl, nbig;
+    int64_t scan_bytes;
     const uint8_t *pkt, *scan;
     const uint16_t *len16;
     const uint32_t *big;
@@ -252,14 +262,8 @@ LEMON_JPEG_HD bool par_open(const uint8_t *pkt, int64_t bytes, int64_t rec_room,
     if (!pkt || bytes < kLenOff || (((uintptr_t)pkt) & 15) != 0) return false;
     const int32_t *hd = reinterpret_cast<const int32_t *>(pkt);
     if (hd[kPkMagic] != kMagic) return false;
-    im.w = hd[kPkWidth]; im.h = hd[kPkHeight]; im.nc = hd[kPkComponents]; im.hs = hd[kPkHs]; im.vs = hd[kPkVs];
+    if (!packet_geometry(hd, rec_room, im)) return false;
     im.restart = hd[kPkRestart]; im.nivl = hd[kPkIntervals]; im.nbig = hd[kPkBig]; im.scan_bytes = hd[kPkScanBytes];
-    if (!jpeg_geometry(im.w, im.h, im.nc, im.hs, im.vs, im.g)) return false;
-    if (rec_room < LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks) return false;
-    im.luma = im.nc == 3 ? im.hs * im.vs : 1;
-    im.spm = im.nc == 3 ? im.luma + 2 : 1;
-    im.mx = im.nc == 3 ? im.g.bwc : im.g.bw0; im.my = im.nc == 3 ? im.g.bhc : im.g.bh0;
-    im.mcus = (int64_t)im.mx * im.my;
     if (im.restart < 0 || im.restart > 65535) return false;
     const int64_t nivl = im.restart ? (im.mcus + im.restart - 1) / im.restart : 1;
     if (im.nivl != nivl || im.scan_bytes < 0 || im.nbig < 0 || im.nbig > im.nivl) return false;
@@ -303,13 +307,7 @@ LEMON_JPEG_HD int par_comp_of_slot(const ParImage &im, int slot) { return slot <
 
 // record block (planar, jpeg_entropy.hpp) of block b of the scan order, counted from MCU mcu0
 LEMON_JPEG_HD int64_t par_block_addr(const ParImage &im, int64_t mcu0, int64_t b) {
-    const int64_t m = mcu0 + b / im.spm;
-    const int slot = (int)(b % im.spm);
-    const int64_t yy = m / im.mx, xx = m - yy * im.mx;
-    if (slot >= im.luma) return (slot == im.luma ? im.g.n0 : im.g.n0 + im.g.nc) + yy * im.g.bwc + xx;
-    const int cw = im.nc == 3 ? im.hs : 1, ch = im.nc == 3 ? im.vs : 1;
-    const int by = slot / cw, bx = slot - by * cw;
-    return (yy * ch + by) * im.g.bw0 + xx * cw + bx;
+    return jpeg_mcu_block_addr(im.g, im.mx, im.hs, im.vs, im.luma, mcu0 + b / im.spm, (int)(b % im.spm));
 }
 
 // record block of block q of component c in scan order, and whether a restart interval begins with it
@@ -428,18 +426,46 @@ LEMON_JPEG_HD int par_final_lane(const ParHuff *huff, const ParImage &im, const 
     return st == stored_exit ? LEMON_JPEG_OK : LEMON_JPEG_SYNC;
 }
 
-// decode_scan's per-block checks on a finished block (DC already summed): 0 or LEMON_JPEG_ENVELOPE
-LEMON_JPEG_HD int par_check_block(const int16_t *blk, const uint16_t *qt) {
-    const int32_t dc = blk[0];
-    const int64_t D = (int64_t)(dc < 0 ? -dc : dc) * qt[0];
-    int64_t A = 0;
-    for (int i = 1; i < 64; ++i) {
-        const int32_t v = blk[i];
-        A += (int64_t)(v < 0 ? -v : v) * qt[i];
+// decode_scan's envelope check on the finished blocks first, first + stride, ... of a record (quantisers at its head, DC
+// values summed): false when one lies outside.  Callers: both host loops (every block: 0, 1) and, one thread each with a grid
+// stride, k_jent_check (jpeg_entropy.hip) and k_jprog_check (jpeg_prog.hip).
+LEMON_JPEG_HD bool par_envelope_blocks(const uint8_t *rec, const JpegGeom &g, int64_t first, int64_t stride) {
+    const uint16_t *quant = reinterpret_cast<const uint16_t *>(rec);
+    const int16_t *coef = reinterpret_cast<const int16_t *>(rec + LEMON_JPEG_QUANT_BYTES);
+    bool ok = true;
+    int32_t max_abs = 0, exact = 0;
+    for (int64_t b = first; b < g.blocks; b += stride) {
+        const int c = b < g.n0 ? 0 : (b < g.n0 + g.nc ? 1 : 2);
+        if (!lemon_jpeg::block_in_envelope(coef + 64 * b, quant + 64 * c, max_abs, exact)) ok = false;
     }
-    if (D + 2 * A <= lemon_jpeg::kEnvelopeQuick) return LEMON_JPEG_OK;
-    return jpeg_block_in_envelope(blk, qt) ? LEMON_JPEG_OK : LEMON_JPEG_ENVELOPE;
+    return ok;
 }
+
+// A record before its first coefficient: zeros behind the packet's quantisers (both packets keep them at byte 128).  Returns
+// the coefficients.  Callers: both host loops below and in jpeg_prog_par.hpp, lemon_jpeg_prog::seq_decode (jpeg_prog.hpp).
+static inline int16_t *par_new_record(uint8_t *record, const uint8_t *pkt, const JpegGeom &g) {
+    memset(record, 0, (size_t)(LEMON_JPEG_QUANT_BYTES + 128 * g.blocks));
+    memcpy(record, pkt + kQuantOff, LEMON_JPEG_QUANT_BYTES);
+    return reinterpret_cast<int16_t *>(record + LEMON_JPEG_QUANT_BYTES);
+}
+
+#if defined(__HIPCC__)
+// ---- what the kernels of jpeg_entropy.hip and jpeg_prog.hip share beyond the step functions (their grids differ)
+// an image's descriptor (packet offset, packet bytes, record offset, ...) against the extents of the two buffers (jent_open,
+// jprog_open)
+__device__ __forceinline__ bool jpeg_dev_extents(const int64_t *d, int64_t pk_bytes, int64_t rec_bytes) {
+    if (d[0] < 0 || (d[0] & 15) != 0 || d[1] < 0 || d[0] > pk_bytes || d[1] > pk_bytes - d[0]) return false;
+    return d[2] >= 0 && (d[2] & 15) == 0 && d[2] <= rec_bytes;
+}
+
+// par_new_record, 16 bytes per thread: units first, first + stride, ... of the record (k_jent_zero, k_jprog_zero)
+__device__ __forceinline__ void jpeg_dev_new_record(uint8_t *rec, const uint8_t *pkt, const JpegGeom &g, int64_t first, int64_t stride) {
+    const int64_t n16 = (LEMON_JPEG_QUANT_BYTES + 128 * g.blocks) / 16;
+    const uint4 *q = reinterpret_cast<const uint4 *>(pkt + kQuantOff);
+    for (int64_t k = first; k < n16; k += stride)
+        reinterpret_cast<uint4 *>(rec)[k] = k < LEMON_JPEG_QUANT_BYTES / 16 ? q[k] : make_uint4(0, 0, 0, 0);
+}
+#endif
 
 LEMON_JPEG_HD int32_t par_subseq(int32_t subseq) { return subseq == 0 ? LEMON_JPEG_SUBSEQ_DEFAULT : subseq; }
 LEMON_JPEG_HD bool par_subseq_ok(int32_t subseq) {
@@ -454,7 +480,7 @@ static inline int lemon_jpeg_pack_impl(const uint8_t *data, int64_t n, uint8_t *
     memset(info, 0, sizeof(*info));
     if (packet_bytes) *packet_bytes = 0;
     if (!data || n < 0) return info->status = LEMON_JPEG_NOT_JPEG;
-    lemon_jpeg::Frame *f = new lemon_jpeg::Frame();
+    lemon_jpeg::BaseFile *f = new lemon_jpeg::BaseFile();
     const int rc = lemon_jpeg_par::pack(data, (size_t)n, packet, cap, info, packet_bytes, *f);
     delete f;
     return info->status = rc;
@@ -499,8 +525,8 @@ static inline int lemon_jpeg_entropy_par_host_impl(const uint8_t *packet, int64_
             const int64_t i = j - ivl_lane0[t];
             l.d = im.scan + ivl_start[t]; l.len = ivl_start[t + 1] - ivl_start[t];
             l.end_bit = 8 * (l.len < (i + 1) * S ? l.len : (i + 1) * S);
-            l.mcu0 = im.restart ? t * im.restart : 0;
-            l.total = (im.restart && im.mcus - l.mcu0 > im.restart ? im.restart : im.mcus - l.mcu0) * im.spm;
+            const McuRange r = interval_mcus(im.restart, im.mcus, t);
+            l.mcu0 = r.first; l.total = r.count * im.spm;
             l.guess = par_state(8 * i * S, 0, 0);
             l.first = i == 0; l.last = j + 1 == ivl_lane0[t + 1];
         }
@@ -529,14 +555,11 @@ static inline int lemon_jpeg_entropy_par_host_impl(const uint8_t *packet, int64_
         first_blk[j] = run;
         run += cnt[j];
     }
-    memset(record, 0, (size_t)(LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks));
-    memcpy(record, packet + kQuantOff, LEMON_JPEG_QUANT_BYTES);
-    int16_t *coef = reinterpret_cast<int16_t *>(record + LEMON_JPEG_QUANT_BYTES);
+    int16_t *coef = par_new_record(record, packet, im.g);
     for (int64_t j = 0; j < lanes; ++j) {
         const int rc = par_final_lane(huff, im, L[j], L[j].first ? L[j].guess : exitst[j - 1], entry[j], exitst[j], first_blk[j], coef);
         if (rc > st) st = rc;
     }
-    const uint16_t *quant = reinterpret_cast<const uint16_t *>(record);
     for (int c = 0; c < im.nc; ++c) {
         const int64_t nb = c == 0 ? im.g.n0 : im.g.nc;
         int64_t run = 0;
@@ -546,10 +569,9 @@ static inline int lemon_jpeg_entropy_par_host_impl(const uint8_t *packet, int64_
             run = (head ? 0 : run) + b[0];
             if (run < -32768 || run > 32767) { if (LEMON_JPEG_CODE > st) st = LEMON_JPEG_CODE; }
             b[0] = (int16_t)run;
-            const int rc = par_check_block(b, quant + 64 * c);
-            if (rc > st) st = rc;
         }
     }
+    if (!par_envelope_blocks(record, im.g, 0, 1) && LEMON_JPEG_ENVELOPE > st) st = LEMON_JPEG_ENVELOPE;
     *status = st;
     delete[] huff; delete[] ivl_start; delete[] ivl_lane0; delete[] L; delete[] entry; delete[] exitst; delete[] cnt;
     delete[] first_blk; delete[] wgexit;

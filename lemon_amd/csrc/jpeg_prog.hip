@@ -50,8 +50,7 @@ inline int64_t jprog_carve(char *base, int64_t batch, int64_t items, int32_t lev
 // the image's descriptor against the buffers' extents, then its packet head (jpeg_prog_par.hpp::prog_open)
 __device__ __forceinline__ bool jprog_open(const JprogParams &p, int64_t i, ProgImage &im) {
     const int64_t *d = p.desc + 8 * i;
-    if (d[0] < 0 || (d[0] & 15) != 0 || d[1] < 0 || d[0] > p.pk_bytes || d[1] > p.pk_bytes - d[0]) return false;
-    if (d[2] < 0 || (d[2] & 15) != 0 || d[2] > p.rec_bytes) return false;
+    if (!lemon_jpeg_par::jpeg_dev_extents(d, p.pk_bytes, p.rec_bytes)) return false;
     if (d[3] < 0 || d[4] < 1 || d[3] > p.total_items || d[4] > p.total_items - d[3]) return false;
     if (!prog_open(p.pk + d[0], d[1], p.rec_bytes - d[2], im)) return false;
     return im.items == d[4] && im.levels <= p.levels;
@@ -123,11 +122,8 @@ __global__ __launch_bounds__(JPROG_ZT) void k_jprog_zero(JprogParams p) {
     const int64_t i = blockIdx.x;
     ProgImage im;
     if (!p.ws.img[i] || !jprog_open(p, i, im)) return;
-    uint8_t *rec = p.rec + p.desc[8 * i + 2];
-    const int64_t n16 = (LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks) / 16;
-    const uint4 *q = reinterpret_cast<const uint4 *>(im.pkt + kQuantOff);
-    for (int64_t k = (int64_t)blockIdx.y * JPROG_ZT + threadIdx.x; k < n16; k += (int64_t)JPROG_ZY * JPROG_ZT)
-        reinterpret_cast<uint4 *>(rec)[k] = k < LEMON_JPEG_QUANT_BYTES / 16 ? q[k] : make_uint4(0, 0, 0, 0);
+    lemon_jpeg_par::jpeg_dev_new_record(p.rec + p.desc[8 * i + 2], im.pkt, im.g, (int64_t)blockIdx.y * JPROG_ZT + threadIdx.x,
+                                        (int64_t)JPROG_ZY * JPROG_ZT);
 }
 
 __global__ __launch_bounds__(JPROG_T) void k_jprog_level(JprogParams p, int level) {
@@ -168,15 +164,9 @@ __global__ __launch_bounds__(JPROG_ZT) void k_jprog_check(JprogParams p) {
             return;
         }
     }
-    const uint8_t *rec = p.rec + p.desc[8 * i + 2];
-    const uint16_t *quant = reinterpret_cast<const uint16_t *>(rec);
-    const int16_t *coef = reinterpret_cast<const int16_t *>(rec + LEMON_JPEG_QUANT_BYTES);
-    bool bad = false;
-    for (int64_t b = (int64_t)blockIdx.y * JPROG_ZT + threadIdx.x; b < im.g.blocks; b += (int64_t)JPROG_ZY * JPROG_ZT) {
-        const int c = b < im.g.n0 ? 0 : (b < im.g.n0 + im.g.nc ? 1 : 2);
-        if (lemon_jpeg_par::par_check_block(coef + 64 * b, quant + 64 * c) != LEMON_JPEG_OK) bad = true;
-    }
-    if (bad) atomicMax(p.status + i, (int)LEMON_JPEG_ENVELOPE);
+    if (!lemon_jpeg_par::par_envelope_blocks(p.rec + p.desc[8 * i + 2], im.g, (int64_t)blockIdx.y * JPROG_ZT + threadIdx.x,
+                                             (int64_t)JPROG_ZY * JPROG_ZT))
+        atomicMax(p.status + i, (int)LEMON_JPEG_ENVELOPE);
 }
 
 }  // namespace

@@ -21,7 +21,9 @@
 //                           an int16 does not hold after the shift by Al
 // The Huffman pass itself reads the packet (so the packer's checks ARE the host pass's marker checks) and walks the work items of
 // jpeg_prog_par.hpp level by level with the verdict rule stated there, but decodes every block the way libjpeg's jdphuff.c does:
-// coefficient by coefficient in place.  Only the bit window and the Huffman step are shared with the device form.
+// coefficient by coefficient in place.  Of the decode, only the bit window and the Huffman step are shared with the device form.
+// The marker segments between the scans are read by jpeg_entropy.hpp's read_to_sos and judged by its frame_checks, the scans'
+// bytes are walked by jpeg_par.hpp's walk_scan: the baseline path's own functions.
 #pragma once
 #include <stdlib.h>
 
@@ -49,85 +51,9 @@ struct ProgFile {
     int64_t items = 0, spec_bytes = 0, ends_bytes = 0, data_bytes = 0;
 };
 
-// Walks the entropy-coded bytes of one scan from d[p] to the marker that ends it (p is left at that marker's FF), checking the
-// marker structure; COPY writes the destuffed bytes to out[0, cap) and, with several intervals, every interval's end to `ends`.
-template <bool COPY>
-static inline int walk_scan(const uint8_t *d, size_t n, size_t &p, int32_t restart, int64_t nivl, uint8_t *out, int64_t cap, uint32_t *ends,
-                            int64_t &bytes) {
-    int64_t o = 0, ivl = 0, start = 0;
-    bool fill = false;
-    for (;;) {
-        if (p >= n) return LEMON_JPEG_STREAM;
-        if (d[p] != 0xFF) {
-            if (fill) return LEMON_JPEG_STREAM;
-            const void *ff = memchr(d + p, 0xFF, n - p);
-            const int64_t run = ff ? (int64_t)(static_cast<const uint8_t *>(ff) - (d + p)) : (int64_t)(n - p);
-            if (COPY) {
-                if (run > cap - o) return LEMON_JPEG_BUFFER;
-                memcpy(out + o, d + p, (size_t)run);
-            }
-            o += run; p += (size_t)run;
-            continue;
-        }
-        if (p + 1 >= n) return LEMON_JPEG_STREAM;
-        const uint8_t m = d[p + 1];
-        if (m == 0xFF) { fill = true; ++p; continue; }
-        if (m == 0) {
-            if (fill) return LEMON_JPEG_STREAM;
-            if (COPY) {
-                if (o >= cap) return LEMON_JPEG_BUFFER;
-                out[o] = 0xFF;
-            }
-            ++o; p += 2;
-            continue;
-        }
-        if (o == start) return LEMON_JPEG_STREAM;                    // an interval without a byte
-        if (m >= 0xD0 && m <= 0xD7) {
-            if (!restart || ivl + 1 >= nivl || m != (uint8_t)(0xD0 + (ivl & 7))) return LEMON_JPEG_STREAM;
-            if (COPY) ends[ivl] = (uint32_t)o;
-            ++ivl; start = o; p += 2; fill = false;
-            continue;
-        }
-        if (ivl != nivl - 1) return LEMON_JPEG_STREAM;
-        if (COPY && nivl > 1) ends[ivl] = (uint32_t)o;
-        bytes = o;
-        return LEMON_JPEG_OK;
-    }
-}
-
-static inline bool counts_ok(const uint8_t *counts16) {
-    int32_t code = 0;
-    for (int l = 1; l <= 16; ++l) {
-        if (code + counts16[l - 1] > (1 << l)) return false;
-        code = (code + counts16[l - 1]) << 1;
-    }
-    return true;
-}
-
-// the header checks that parse_header makes after its marker loop, at the first SOS
-static inline int first_scan_checks(ProgFile &pf, LemonJpegInfo *info) {
-    lemon_jpeg::Frame &f = pf.f;
-    int hs = 1, vs = 1;
-    if (f.nc == 3) {
-        hs = f.hs[0]; vs = f.vs[0];
-        if (f.hs[1] != 1 || f.vs[1] != 1 || f.hs[2] != 1 || f.vs[2] != 1) return LEMON_JPEG_SAMPLING;
-        if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return LEMON_JPEG_SAMPLING;
-        if (!f.jfif && !(f.id[0] == 1 && f.id[1] == 2 && f.id[2] == 3)) return LEMON_JPEG_COLOUR;
-    } else if (f.hs[0] < 1 || f.hs[0] > 4 || f.vs[0] < 1 || f.vs[0] > 4) {
-        return LEMON_JPEG_SAMPLING;
-    }
-    JpegGeom g;
-    if (!jpeg_geometry(f.w, f.h, f.nc, hs, vs, g)) return LEMON_JPEG_DIMENSION;
-    info->width = f.w; info->height = f.h; info->components = f.nc; info->hs = hs; info->vs = vs;
-    info->mcus_x = f.nc == 3 ? g.bwc : g.bw0; info->mcus_y = f.nc == 3 ? g.bhc : g.bh0;
-    info->blocks = g.blocks;
-    info->record_bytes = LEMON_JPEG_QUANT_BYTES + 128 * g.blocks;
-    return LEMON_JPEG_OK;
-}
-
-// All markers from SOI to EOI (first_only: to the first SOS, for lemon_jpeg_prog_info).
+// All markers from SOI to EOI (first_only: to the first SOS, for lemon_jpeg_prog_info).  The segments between the scans are
+// lemon_jpeg::read_to_sos's (jpeg_entropy.hpp); a DHT table it found valid is remembered by its offset in the file.
 static inline int parse(const uint8_t *d, size_t n, ProgFile &pf, LemonJpegInfo *info, bool first_only) {
-    using lemon_jpeg::rd16;
     lemon_jpeg::Frame &f = pf.f;
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return LEMON_JPEG_NOT_JPEG;
     if (n >= ((size_t)1 << 31)) return LEMON_JPEG_BUFFER;
@@ -135,155 +61,98 @@ static inline int parse(const uint8_t *d, size_t n, ProgFile &pf, LemonJpegInfo 
     memset(pf.quant, 0, sizeof(pf.quant));
     size_t p = 2;
     for (;;) {
-        if (p + 2 > n) return LEMON_JPEG_TRUNCATED;
-        if (d[p] != 0xFF) return LEMON_JPEG_MARKER;
-        while (p + 1 < n && d[p + 1] == 0xFF) ++p;
-        if (p + 2 > n) return LEMON_JPEG_TRUNCATED;
-        const int m = d[p + 1];
-        p += 2;
-        if (m == 0xD9 && pf.scans > 0) break;
-        if (m == 0xC0 || m == 0xC1 || m == 0xC3 || (m >= 0xC5 && m <= 0xCF && m != 0xC8) || m == 0xDC || m == 0xDE || m == 0xDF)
-            return LEMON_JPEG_PROCESS;
-        const bool segment = m == 0xC2 || m == 0xC4 || m == 0xDA || m == 0xDB || m == 0xDD || (m >= 0xE0 && m <= 0xEF) || m == 0xFE;
-        if (!segment) return LEMON_JPEG_MARKER;
-        if (p + 2 > n) return LEMON_JPEG_TRUNCATED;
-        const size_t len = (size_t)rd16(d, p);
-        if (len < 2 || len > n - p) return LEMON_JPEG_TRUNCATED;
-        const uint8_t *s = d + p + 2;
-        const size_t sl = len - 2;
-        p += len;
-        if (m == 0xE0) {
-            if (pf.scans == 0 && sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) f.jfif = true;
-        } else if (m == 0xEE) {
-            if (sl >= 5 && memcmp(s, "Adobe", 5) == 0) return LEMON_JPEG_COLOUR;
-        } else if (m == 0xDB) {
-            size_t o = 0;
-            while (o < sl) {
-                const int pq = s[o] >> 4, tq = s[o] & 15;
-                if (pq != 0 || tq > 3) return LEMON_JPEG_TABLE;
-                if (sl - o < 65) return LEMON_JPEG_TABLE;
-                for (int k = 0; k < 64; ++k) f.q[tq][lemon_jpeg::kZigzag[k]] = s[o + 1 + k];
-                f.q_defined[tq] = true;
-                o += 65;
-            }
-        } else if (m == 0xC4) {
-            size_t o = 0;
-            while (o < sl) {
-                if (sl - o < 17) return LEMON_JPEG_TABLE;
-                const int tc = s[o] >> 4, th = s[o] & 15;
-                if (tc > 1 || th > 3) return LEMON_JPEG_TABLE;
-                int total = 0;
-                for (int l = 1; l <= 16; ++l) total += s[o + l];
-                if (total > 256 || sl - o - 17 < (size_t)total) return LEMON_JPEG_TABLE;
-                for (int i = 0; i < total; ++i)
-                    if (tc == 0 && s[o + 17 + i] > 11) return LEMON_JPEG_TABLE;
-                if (!counts_ok(s + o + 1)) return LEMON_JPEG_TABLE;
-                FileTable &t = tc ? pf.ac[th] : pf.dc[th];
-                t.defined = true; t.at = (size_t)(s + o + 1 - d); t.pool = -1;
-                o += 17 + (size_t)total;
-            }
-        } else if (m == 0xDD) {
-            if (sl != 2) return LEMON_JPEG_TABLE;
-            f.restart = rd16(s, 0);
-        } else if (m == 0xC2) {
-            if (f.have_sof) return LEMON_JPEG_MARKER;
-            if (sl < 6) return LEMON_JPEG_TRUNCATED;
-            if (s[0] != 8) return LEMON_JPEG_PRECISION;
-            f.h = rd16(s, 1); f.w = rd16(s, 3); f.nc = s[5];
-            if (f.h == 0 || f.w == 0) return LEMON_JPEG_DIMENSION;
-            if (f.nc != 1 && f.nc != 3) return LEMON_JPEG_COMPONENTS;
-            if (sl != (size_t)(6 + 3 * f.nc)) return LEMON_JPEG_TRUNCATED;
-            for (int c = 0; c < f.nc; ++c) {
-                f.id[c] = s[6 + 3 * c]; f.hs[c] = s[7 + 3 * c] >> 4; f.vs[c] = s[7 + 3 * c] & 15; f.tq[c] = s[8 + 3 * c];
-                if (f.tq[c] > 3) return LEMON_JPEG_TABLE;
-            }
-            f.have_sof = true;
-        } else if (m == 0xDA) {
-            if (!f.have_sof) return LEMON_JPEG_MARKER;
-            if (pf.scans == 0) {
-                const int rc = first_scan_checks(pf, info);
-                if (rc != LEMON_JPEG_OK) return rc;
-            }
-            if (pf.scans == 64) return LEMON_JPEG_SCAN;
-            const int ns = sl >= 1 ? s[0] : 0;
-            if ((ns != 1 && ns != f.nc) || sl != (size_t)(4 + 2 * ns)) return LEMON_JPEG_SCAN;
-            FileScan &sc = pf.scan[pf.scans];
-            int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
-            if (ns == 1) {
-                sc.comp = -1;
-                for (int c = 0; c < f.nc; ++c)
-                    if (s[1] == f.id[c]) { sc.comp = c; break; }
-                if (sc.comp < 0) return LEMON_JPEG_SCAN;
-                td[0] = s[2] >> 4; ta[0] = s[2] & 15;
-            } else {
-                sc.comp = -1;
-                for (int c = 0; c < ns; ++c) {
-                    if (s[1 + 2 * c] != f.id[c]) return LEMON_JPEG_SCAN;
-                    td[c] = s[2 + 2 * c] >> 4; ta[c] = s[2 + 2 * c] & 15;
-                }
-            }
-            for (int c = 0; c < ns; ++c)
-                if (td[c] > 3 || ta[c] > 3) return LEMON_JPEG_TABLE;
-            sc.ss = s[1 + 2 * ns]; sc.se = s[2 + 2 * ns]; sc.ah = s[3 + 2 * ns] >> 4; sc.al = s[3 + 2 * ns] & 15;
-            if (sc.ss == 0 ? sc.se != 0 : (sc.se < sc.ss || sc.se > 63 || ns != 1)) return LEMON_JPEG_SCAN;
-            if ((sc.ah != 0 && sc.al != sc.ah - 1) || sc.al > 13) return LEMON_JPEG_SCAN;
-            for (int j = 0; j < ns; ++j) {
-                const int c = ns == 1 ? sc.comp : j;
-                if (sc.ss > 0 && pf.sent[c][0] < 0) return LEMON_JPEG_SCAN;
-                for (int k = sc.ss; k <= sc.se; ++k) {
-                    if (sc.ah == 0 ? pf.sent[c][k] >= 0 : pf.sent[c][k] != sc.ah) return LEMON_JPEG_SCAN;
-                    pf.sent[c][k] = (int8_t)sc.al;
-                }
-                if (!pf.latched[c]) {
-                    if (!f.q_defined[f.tq[c]]) return LEMON_JPEG_TABLE;
-                    memcpy(pf.quant[c], f.q[f.tq[c]], 128);
-                    pf.latched[c] = true;
-                }
-            }
-            sc.t[0] = sc.t[1] = sc.t[2] = -1;
-            if (!(sc.ss == 0 && sc.ah != 0))
-                for (int j = 0; j < ns; ++j) {
-                    FileTable &t = sc.ss == 0 ? pf.dc[td[j]] : pf.ac[ta[j]];
-                    if (!t.defined) return LEMON_JPEG_TABLE;
-                    if (t.pool < 0) {
-                        if (pf.pool == 192) return LEMON_JPEG_TABLE;
-                        int total = 0;
-                        for (int l = 0; l < 16; ++l) total += d[t.at + l];
-                        pf.spec_bytes += 16 + total;
-                        pf.pool_at[pf.pool] = t.at;
-                        t.pool = pf.pool++;
-                    }
-                    sc.t[j] = t.pool;
-                }
-            if (ns == 1 && f.nc == 1) sc.comp = 0;
-            sc.level = 0;
-            for (int e = 0; e < pf.scans; ++e) {
-                const FileScan &b = pf.scan[e];
-                if ((sc.comp < 0 || b.comp < 0 || sc.comp == b.comp) && sc.ss <= b.se && b.ss <= sc.se && b.level + 1 > sc.level)
-                    sc.level = b.level + 1;
-            }
-            if (sc.level + 1 > pf.levels) pf.levels = sc.level + 1;
-            int64_t mcus = (int64_t)info->mcus_x * info->mcus_y;
-            if (sc.comp >= 0 && f.nc == 3) {
-                const int32_t cw = sc.comp == 0 ? f.w : (f.w + info->hs - 1) / info->hs, ch = sc.comp == 0 ? f.h : (f.h + info->vs - 1) / info->vs;
-                mcus = (int64_t)((cw + 7) / 8) * ((ch + 7) / 8);
-            } else if (f.nc == 1) {
-                mcus = (int64_t)((f.w + 7) / 8) * ((f.h + 7) / 8);
-            }
-            sc.restart = f.restart;
-            sc.nivl = sc.restart ? (mcus + sc.restart - 1) / sc.restart : 1;
-            sc.start = p;
-            ++pf.scans;
-            if (first_only) {
-                memcpy(info->quant, pf.quant, sizeof(pf.quant));
-                return LEMON_JPEG_OK;
-            }
-            const int rc = walk_scan<false>(d, n, p, sc.restart, sc.nivl, nullptr, 0, nullptr, sc.bytes);
+        const uint8_t *s = nullptr;
+        size_t sl = 0;
+        bool eoi;
+        const int hrc = lemon_jpeg::read_to_sos(d, n, p, f, true, pf.scans > 0, [&pf](int tc, int th, const ParHuff &, size_t at) {
+            FileTable &t = tc ? pf.ac[th] : pf.dc[th];
+            t.defined = true; t.at = at; t.pool = -1;
+        }, s, sl, eoi);
+        if (hrc != LEMON_JPEG_OK) return hrc;
+        if (eoi) break;
+        if (pf.scans == 0) {
+            const int rc = lemon_jpeg::frame_checks(f, info);
             if (rc != LEMON_JPEG_OK) return rc;
-            pf.items += (sc.nivl + LEMON_JPEG_PROG_GROUP - 1) / LEMON_JPEG_PROG_GROUP;
-            pf.data_bytes += sc.bytes;
-            if (sc.nivl > 1) pf.ends_bytes += 4 * sc.nivl;
         }
+        if (pf.scans == 64) return LEMON_JPEG_SCAN;
+        const int ns = sl >= 1 ? s[0] : 0;
+        if ((ns != 1 && ns != f.nc) || sl != (size_t)(4 + 2 * ns)) return LEMON_JPEG_SCAN;
+        FileScan &sc = pf.scan[pf.scans];
+        int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+        if (ns == 1) {
+            sc.comp = -1;
+            for (int c = 0; c < f.nc; ++c)
+                if (s[1] == f.id[c]) { sc.comp = c; break; }
+            if (sc.comp < 0) return LEMON_JPEG_SCAN;
+            td[0] = s[2] >> 4; ta[0] = s[2] & 15;
+        } else {
+            sc.comp = -1;
+            for (int c = 0; c < ns; ++c) {
+                if (s[1 + 2 * c] != f.id[c]) return LEMON_JPEG_SCAN;
+                td[c] = s[2 + 2 * c] >> 4; ta[c] = s[2 + 2 * c] & 15;
+            }
+        }
+        for (int c = 0; c < ns; ++c)
+            if (td[c] > 3 || ta[c] > 3) return LEMON_JPEG_TABLE;
+        sc.ss = s[1 + 2 * ns]; sc.se = s[2 + 2 * ns]; sc.ah = s[3 + 2 * ns] >> 4; sc.al = s[3 + 2 * ns] & 15;
+        if (sc.ss == 0 ? sc.se != 0 : (sc.se < sc.ss || sc.se > 63 || ns != 1)) return LEMON_JPEG_SCAN;
+        if ((sc.ah != 0 && sc.al != sc.ah - 1) || sc.al > 13) return LEMON_JPEG_SCAN;
+        for (int j = 0; j < ns; ++j) {
+            const int c = ns == 1 ? sc.comp : j;
+            if (sc.ss > 0 && pf.sent[c][0] < 0) return LEMON_JPEG_SCAN;
+            for (int k = sc.ss; k <= sc.se; ++k) {
+                if (sc.ah == 0 ? pf.sent[c][k] >= 0 : pf.sent[c][k] != sc.ah) return LEMON_JPEG_SCAN;
+                pf.sent[c][k] = (int8_t)sc.al;
+            }
+            if (!pf.latched[c]) {
+                if (!f.q_defined[f.tq[c]]) return LEMON_JPEG_TABLE;
+                memcpy(pf.quant[c], f.q[f.tq[c]], 128);
+                pf.latched[c] = true;
+            }
+        }
+        sc.t[0] = sc.t[1] = sc.t[2] = -1;
+        if (!(sc.ss == 0 && sc.ah != 0))
+            for (int j = 0; j < ns; ++j) {
+                FileTable &t = sc.ss == 0 ? pf.dc[td[j]] : pf.ac[ta[j]];
+                if (!t.defined) return LEMON_JPEG_TABLE;
+                if (t.pool < 0) {
+                    if (pf.pool == 192) return LEMON_JPEG_TABLE;
+                    int total = 0;
+                    for (int l = 0; l < 16; ++l) total += d[t.at + l];
+                    pf.spec_bytes += 16 + total;
+                    pf.pool_at[pf.pool] = t.at;
+                    t.pool = pf.pool++;
+                }
+                sc.t[j] = t.pool;
+            }
+        if (ns == 1 && f.nc == 1) sc.comp = 0;
+        sc.level = 0;
+        for (int e = 0; e < pf.scans; ++e) {
+            const FileScan &b = pf.scan[e];
+            if ((sc.comp < 0 || b.comp < 0 || sc.comp == b.comp) && sc.ss <= b.se && b.ss <= sc.se && b.level + 1 > sc.level)
+                sc.level = b.level + 1;
+        }
+        if (sc.level + 1 > pf.levels) pf.levels = sc.level + 1;
+        int64_t mcus = (int64_t)info->mcus_x * info->mcus_y;
+        if (sc.comp >= 0 && f.nc == 3) {
+            const int32_t cw = sc.comp == 0 ? f.w : (f.w + info->hs - 1) / info->hs, ch = sc.comp == 0 ? f.h : (f.h + info->vs - 1) / info->vs;
+            mcus = (int64_t)((cw + 7) / 8) * ((ch + 7) / 8);
+        } else if (f.nc == 1) {
+            mcus = (int64_t)((f.w + 7) / 8) * ((f.h + 7) / 8);
+        }
+        sc.restart = f.restart;
+        sc.nivl = sc.restart ? (mcus + sc.restart - 1) / sc.restart : 1;
+        sc.start = p;
+        ++pf.scans;
+        if (first_only) {
+            memcpy(info->quant, pf.quant, sizeof(pf.quant));
+            return LEMON_JPEG_OK;
+        }
+        const int rc = lemon_jpeg_par::walk_scan<false>(d, n, p, sc.restart, sc.nivl, nullptr, 0, [](int64_t, int64_t) {}, sc.bytes);
+        if (rc != LEMON_JPEG_OK) return rc;
+        pf.items += (sc.nivl + LEMON_JPEG_PROG_GROUP - 1) / LEMON_JPEG_PROG_GROUP;
+        pf.data_bytes += sc.bytes;
+        if (sc.nivl > 1) pf.ends_bytes += 4 * sc.nivl;
     }
     for (int c = 0; c < f.nc; ++c)
         for (int k = 0; k < 64; ++k)
@@ -332,7 +201,9 @@ static inline int pack(const uint8_t *d, size_t n, const ProgFile &pf, const Lem
         memcpy(pkt + kScanOff + 4 * kScanInts * s, row, sizeof(row));
         size_t p = sc.start;
         int64_t bytes = 0;
-        const int rc = walk_scan<true>(d, n, p, sc.restart, sc.nivl, pkt + data_off + dof, sc.bytes, reinterpret_cast<uint32_t *>(pkt + eo), bytes);
+        uint32_t *ends = reinterpret_cast<uint32_t *>(pkt + eo);
+        const int rc = lemon_jpeg_par::walk_scan<true>(d, n, p, sc.restart, sc.nivl, pkt + data_off + dof, sc.bytes,
+                                                       [ends](int64_t ivl, int64_t o) { ends[ivl] = (uint32_t)o; }, bytes);
         if (rc != LEMON_JPEG_OK || bytes != sc.bytes) return rc != LEMON_JPEG_OK ? rc : (int)LEMON_JPEG_STREAM;
         dof += sc.bytes;
         if (sc.nivl > 1) eo += 4 * sc.nivl;
@@ -403,8 +274,7 @@ static inline int seq_interval(const ProgImage &im, const ProgScan &sc, const Pa
                     bit += l;
                     if (bit > total) return LEMON_JPEG_STREAM;
                 } else {
-                    eobrun = 1 << r;
-                    if (r) eobrun += (int32_t)((w << l) >> (32 - r));
+                    eobrun = prog_eob_run(w, l, r);
                     bit += l + r;
                     if (bit > total || eobrun > nblk - b) return LEMON_JPEG_STREAM;
                     --eobrun;
@@ -425,8 +295,7 @@ static inline int seq_interval(const ProgImage &im, const ProgScan &sc, const Pa
                     s = ((w << l) >> 31) ? p1 : m1;
                     bit += l + 1;
                 } else if (r != 15) {
-                    eobrun = 1 << r;
-                    if (r) eobrun += (int32_t)((w << l) >> (32 - r));
+                    eobrun = prog_eob_run(w, l, r);
                     bit += l + r;
                     if (bit > total || eobrun > nblk - b) return LEMON_JPEG_STREAM;
                     break;
@@ -467,9 +336,7 @@ static inline int seq_interval(const ProgImage &im, const ProgScan &sc, const Pa
 static inline int seq_decode(const uint8_t *pkt, int64_t bytes, uint8_t *record, int64_t record_cap, LemonJpegInfo *info) {
     ProgImage im;
     if (!prog_open(pkt, bytes, record_cap, im) || !prog_plan(im)) return LEMON_JPEG_BUFFER;
-    memset(record, 0, (size_t)(LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks));
-    memcpy(record, pkt + kQuantOff, LEMON_JPEG_QUANT_BYTES);
-    int16_t *coef = reinterpret_cast<int16_t *>(record + LEMON_JPEG_QUANT_BYTES);
+    int16_t *coef = lemon_jpeg_par::par_new_record(record, pkt, im.g);
     ParHuff *huff = new ParHuff[3];
     int st = LEMON_JPEG_OK;
     for (int level = 0; level < im.levels && st == LEMON_JPEG_OK; ++level)
@@ -482,9 +349,8 @@ static inline int seq_decode(const uint8_t *pkt, int64_t bytes, uint8_t *record,
                 const int64_t lo = t ? sc.ends[t - 1] : 0, hi = sc.nivl > 1 ? (int64_t)sc.ends[t] : sc.bytes;
                 int rc = LEMON_JPEG_STREAM;
                 if (lo <= hi && hi <= sc.bytes && (t + 1 < sc.nivl || hi == sc.bytes)) {
-                    const int64_t mcu0 = sc.restart ? t * sc.restart : 0;
-                    const int64_t nm = sc.restart && sc.mcus - mcu0 > sc.restart ? sc.restart : sc.mcus - mcu0;
-                    rc = seq_interval(im, sc, huff, sc.data + lo, hi - lo, mcu0 * sc.spm, nm * sc.spm, coef);
+                    const lemon_jpeg_par::McuRange r = lemon_jpeg_par::interval_mcus(sc.restart, sc.mcus, t);
+                    rc = seq_interval(im, sc, huff, sc.data + lo, hi - lo, r.first * sc.spm, r.count * sc.spm, coef);
                 }
                 if (rc != LEMON_JPEG_OK) {                           // the rest of this work item is not decoded
                     if (rc > st) st = rc;
@@ -498,18 +364,7 @@ static inline int seq_decode(const uint8_t *pkt, int64_t bytes, uint8_t *record,
     const uint16_t *quant = reinterpret_cast<const uint16_t *>(record);
     for (int64_t b = 0; b < im.g.blocks; ++b) {
         const uint16_t *qt = quant + 64 * (b < im.g.n0 ? 0 : (b < im.g.n0 + im.g.nc ? 1 : 2));
-        const int16_t *blk = coef + 64 * b;
-        int64_t A = 0;
-        int32_t D = 0;
-        for (int i = 0; i < 64; ++i) {
-            const int32_t v = blk[i], a = (v < 0 ? -v : v) * (int32_t)qt[i];
-            if (a > max_abs) max_abs = a;
-            if (i) A += a; else D = a;
-        }
-        if ((int64_t)D + 2 * A > lemon_jpeg::kEnvelopeQuick) {
-            ++exact;
-            if (!jpeg_block_in_envelope(blk, qt)) return LEMON_JPEG_ENVELOPE;
-        }
+        if (!lemon_jpeg::block_in_envelope(coef + 64 * b, qt, max_abs, exact)) return LEMON_JPEG_ENVELOPE;
     }
     info->max_abs = max_abs;
     info->exact_blocks = exact;

@@ -1,6 +1,8 @@
 // jpeg_prog_par.hpp -- the device form of the Huffman pass of a PROGRESSIVE JPEG (SOF2): the packet a decode worker writes
 // (lemon_jpeg_prog_pack, jpeg_prog.hpp) and the step functions that the kernels (jpeg_prog.hip) and the host loop
-// (lemon_jpeg_prog_entropy_par_host) share.  Plain C++17, no HIP needed.  Bit window and Huffman step are jpeg_par.hpp's.
+// (lemon_jpeg_prog_entropy_par_host) share.  Plain C++17, no HIP needed.  Bit window, Huffman step, the head's geometry, the
+// interval-to-MCU map, the envelope loop and the record initialisation are jpeg_par.hpp's; the table builder is
+// jpeg_entropy.hpp's (jpeg_build_huff).
 //
 // Packet (little endian, the whole a multiple of 16 bytes):
 //   int32  head[32]           kH* below: magic "LJP2", geometry, scans, pool entries, wave items, levels, section offsets (at 0)
@@ -55,11 +57,9 @@ enum { kSComp = 0, kSSs, kSSe, kSAh, kSAl, kSLevel, kSRestart, kSIntervals, kSDa
 static const int32_t kMagic = 0x32504A4C;          // "LJP2"
 static const int32_t kQuantOff = 128, kScanOff = 512;
 
-struct ProgImage {                    // a validated packet head
-    int32_t w, h, nc, hs, vs, scans, pool, items, levels;
-    int32_t luma, spm, mx, my;        // blocks per interleaved MCU (of which luma), the MCU grid
+struct ProgImage : lemon_jpeg_par::PacketGeom {          // a validated packet head
+    int32_t scans, pool, items, levels;
     int64_t bytes, pool_off, data_off, data_bytes;
-    JpegGeom g;
     const uint8_t *pkt;
 };
 
@@ -83,15 +83,10 @@ LEMON_JPEG_HD bool prog_open(const uint8_t *pkt, int64_t bytes, int64_t rec_room
     if (!pkt || bytes < kScanOff + 4 * kScanInts || (((uintptr_t)pkt) & 15) != 0) return false;
     const int32_t *hd = reinterpret_cast<const int32_t *>(pkt);
     if (hd[kHMagic] != kMagic) return false;
-    im.w = hd[kHWidth]; im.h = hd[kHHeight]; im.nc = hd[kHComponents]; im.hs = hd[kHHs]; im.vs = hd[kHVs];
+    if (!lemon_jpeg_par::packet_geometry(hd, rec_room, im)) return false;
     im.scans = hd[kHScans]; im.pool = hd[kHPool]; im.items = hd[kHItems]; im.levels = hd[kHLevels];
-    if (!jpeg_geometry(im.w, im.h, im.nc, im.hs, im.vs, im.g)) return false;
-    if (rec_room < LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks) return false;
     if (im.scans < 1 || im.scans > 64 || im.pool < 0 || im.pool > 192 || im.levels < 1 || im.levels > im.scans || im.items < im.scans)
         return false;
-    im.luma = im.nc == 3 ? im.hs * im.vs : 1;
-    im.spm = im.nc == 3 ? im.luma + 2 : 1;
-    im.mx = im.nc == 3 ? im.g.bwc : im.g.bw0; im.my = im.nc == 3 ? im.g.bhc : im.g.bh0;
     im.bytes = bytes; im.pool_off = hd[kHPoolOff]; im.data_off = hd[kHDataOff]; im.data_bytes = hd[kHDataBytes];
     if (im.pool_off != kScanOff + 4 * kScanInts * (int64_t)im.scans || im.pool_off + 4 * (int64_t)im.pool > bytes) return false;
     if (im.data_bytes < 0 || im.data_off < im.pool_off + 4 * (int64_t)im.pool || im.data_off > bytes || im.data_bytes > bytes - im.data_off)
@@ -110,7 +105,7 @@ LEMON_JPEG_HD bool prog_scan(const ProgImage &im, int s, ProgScan &sc) {
     if (sc.al < 0 || sc.al > 13 || sc.ah < 0 || sc.ah > 14 || (sc.ah != 0 && sc.al != sc.ah - 1)) return false;
     if (sc.level < 0 || sc.level >= im.levels || sc.restart < 0 || sc.restart > 65535) return false;
     if (sc.comp < 0) {
-        sc.bw = im.mx; sc.spm = im.spm; sc.mcus = (int64_t)im.mx * im.my;
+        sc.bw = im.mx; sc.spm = im.spm; sc.mcus = im.mcus;
     } else {
         const int32_t cw = sc.comp == 0 || im.nc == 1 ? im.w : im.g.dwc, ch = sc.comp == 0 || im.nc == 1 ? im.h : im.g.dhc;
         sc.bw = (cw + 7) / 8; sc.spm = 1; sc.mcus = (int64_t)sc.bw * ((ch + 7) / 8);
@@ -144,32 +139,9 @@ LEMON_JPEG_HD bool prog_overlap(const ProgScan &a, const ProgScan &b) {
 // Pool entry idx (0 <= idx < im.pool) -> the table; false when the entry leaves the packet or describes no prefix code.
 LEMON_JPEG_HD bool prog_build_huff(const ProgImage &im, int idx, ParHuff &h) {
     const int64_t off = reinterpret_cast<const uint32_t *>(im.pkt + im.pool_off)[idx];
-    for (int i = 0; i < 512; ++i) h.look[i] = 0;
-    for (int i = 0; i < 256; ++i) h.vals[i] = 0;
-    for (int l = 0; l < 18; ++l) h.maxcode[l] = -1;
-    for (int l = 0; l < 17; ++l) h.valptr[l] = 0;
-    h.maxcode[17] = 0x7fffffff;
-    if (off < im.pool_off || off > im.bytes || 16 > im.bytes - off) return false;
-    const uint8_t *spec = im.pkt + off;
-    int32_t total = 0;
-    for (int l = 0; l < 16; ++l) total += spec[l];
-    if (total > 256 || total > im.bytes - off - 16) return false;
-    for (int i = 0; i < total; ++i) h.vals[i] = spec[16 + i];
-    int32_t code = 0, k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        const int c = spec[l - 1];
-        if (code + c > (1 << l)) return false;
-        h.valptr[l] = k - code;
-        h.maxcode[l] = c ? code + c - 1 : -1;
-        if (l <= 9)
-            for (int i = 0; i < c; ++i) {
-                const int32_t first = (code + i) << (9 - l);
-                for (int32_t j = 0; j < (1 << (9 - l)); ++j) h.look[first + j] = (uint16_t)((l << 8) | spec[16 + k + i]);
-            }
-        code += c; k += c;
-        code <<= 1;
-    }
-    return true;
+    const bool inside = off >= im.pool_off && off <= im.bytes && 16 <= im.bytes - off;
+    const uint8_t *spec = im.pkt + (inside ? off : 0);              // (outside: room -1 holds no table, and `h` is initialised)
+    return lemon_jpeg::jpeg_build_huff(spec, spec + 16, inside ? im.bytes - off - 16 : -1, h);
 }
 
 // record block (planar, jpeg_entropy.hpp) of block q of the scan's own order
@@ -180,11 +152,7 @@ LEMON_JPEG_HD int64_t prog_block_addr(const ProgImage &im, const ProgScan &sc, i
         return (sc.comp == 1 ? im.g.n0 : im.g.n0 + im.g.nc) + row * im.g.bwc + col;
     }
     const int64_t m = q / im.spm;
-    const int slot = (int)(q - m * im.spm);
-    const int64_t yy = m / im.mx, xx = m - yy * im.mx;
-    if (slot >= im.luma) return (slot == im.luma ? im.g.n0 : im.g.n0 + im.g.nc) + yy * im.g.bwc + xx;
-    const int by = slot / im.hs, bx = slot - by * im.hs;
-    return (yy * im.vs + by) * im.g.bw0 + xx * im.hs + bx;
+    return jpeg_mcu_block_addr(im.g, im.mx, im.hs, im.vs, im.luma, m, (int)(q - m * im.spm));
 }
 
 LEMON_JPEG_HD int prog_bit_at(const uint8_t *d, int64_t len, int64_t pos) {
@@ -225,6 +193,10 @@ struct HostWave {
             if (prog_bit_at(d, len, i)) coef[64 * prog_block_addr(im, sc, q0 + i)] |= (int16_t)p1;
     }
 };
+
+// The run of an EOBn symbol: 2^r blocks plus the r bits that follow its l-bit code in w.  Callers: prog_interval (AC first, AC
+// refinement), lemon_jpeg_prog::seq_interval (jpeg_prog.hpp, the same two).
+LEMON_JPEG_HD int32_t prog_eob_run(uint32_t w, int l, int r) { return (1 << r) + (r ? (int32_t)((w << l) >> (32 - r)) : 0); }
 
 // the interval ends inside its last byte
 LEMON_JPEG_HD int prog_interval_end(int64_t total_bits, int64_t bit) {
@@ -298,8 +270,7 @@ LEMON_JPEG_HD int prog_interval(const ProgImage &im, const ProgScan &sc, const P
                     bit += l;
                     if (bit > total) return LEMON_JPEG_STREAM;
                 } else {
-                    eobrun = 1 << r;
-                    if (r) eobrun += (int32_t)((w << l) >> (32 - r));
+                    eobrun = prog_eob_run(w, l, r);
                     bit += l + r;
                     if (bit > total || eobrun > nblk - b) return LEMON_JPEG_STREAM;
                     --eobrun;
@@ -329,8 +300,7 @@ LEMON_JPEG_HD int prog_interval(const ProgImage &im, const ProgScan &sc, const P
                     val = ((w << l) >> 31) ? p1 : -p1;
                     bit += l + 1;
                 } else if (r != 15) {
-                    eobrun = 1 << r;
-                    if (r) eobrun += (int32_t)((w << l) >> (32 - r));
+                    eobrun = prog_eob_run(w, l, r);
                     bit += l + r;
                     if (bit > total || eobrun > nblk - b) return LEMON_JPEG_STREAM;
                     break;
@@ -373,9 +343,8 @@ LEMON_JPEG_HD int prog_item(const ProgImage &im, const ProgScan &sc, const ParHu
     for (int64_t t = t0; t < t0 + LEMON_JPEG_PROG_GROUP && t < sc.nivl; ++t) {
         const int64_t lo = t ? sc.ends[t - 1] : 0, hi = sc.nivl > 1 ? (int64_t)sc.ends[t] : sc.bytes;
         if (lo > hi || hi > sc.bytes || (t + 1 == sc.nivl && hi != sc.bytes)) return LEMON_JPEG_STREAM;
-        const int64_t mcu0 = sc.restart ? t * sc.restart : 0;
-        const int64_t nm = sc.restart && sc.mcus - mcu0 > sc.restart ? sc.restart : sc.mcus - mcu0;
-        const int rc = prog_interval(im, sc, huff, sc.data + lo, hi - lo, mcu0 * sc.spm, nm * sc.spm, coef, wv);
+        const lemon_jpeg_par::McuRange r = lemon_jpeg_par::interval_mcus(sc.restart, sc.mcus, t);
+        const int rc = prog_interval(im, sc, huff, sc.data + lo, hi - lo, r.first * sc.spm, r.count * sc.spm, coef, wv);
         if (rc != LEMON_JPEG_OK) return rc;
     }
     return LEMON_JPEG_OK;
@@ -425,9 +394,7 @@ static inline int lemon_jpeg_prog_entropy_par_host_impl(const uint8_t *packet, i
     *status = LEMON_JPEG_BUFFER;
     ProgImage im;
     if (!record || !prog_open(packet, bytes, record_cap, im) || !prog_plan(im)) return 0;
-    memset(record, 0, (size_t)(LEMON_JPEG_QUANT_BYTES + 128 * im.g.blocks));
-    memcpy(record, packet + kQuantOff, LEMON_JPEG_QUANT_BYTES);
-    int16_t *coef = reinterpret_cast<int16_t *>(record + LEMON_JPEG_QUANT_BYTES);
+    int16_t *coef = lemon_jpeg_par::par_new_record(record, packet, im.g);
     ParHuff *huff = new ParHuff[3];
     HostWave wv;
     int st = LEMON_JPEG_OK;
@@ -443,14 +410,7 @@ static inline int lemon_jpeg_prog_entropy_par_host_impl(const uint8_t *packet, i
             }
         }
     delete[] huff;
-    if (st == LEMON_JPEG_OK) {
-        const uint16_t *quant = reinterpret_cast<const uint16_t *>(record);
-        for (int64_t b = 0; b < im.g.blocks; ++b) {
-            const int c = b < im.g.n0 ? 0 : (b < im.g.n0 + im.g.nc ? 1 : 2);
-            const int rc = lemon_jpeg_par::par_check_block(coef + 64 * b, quant + 64 * c);
-            if (rc > st) st = rc;
-        }
-    }
+    if (st == LEMON_JPEG_OK && !lemon_jpeg_par::par_envelope_blocks(record, im.g, 0, 1)) st = LEMON_JPEG_ENVELOPE;
     *status = st;
     return 0;
 }

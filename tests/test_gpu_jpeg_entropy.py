@@ -87,6 +87,33 @@ def test_device_records_equal_the_host_pass_in_one_mixed_batch_with_poisoned_buf
         assert np.array_equal(rec, ref), (name, subseq, int((rec != ref).sum()))
 
 
+def test_packets_with_a_tampered_huffman_specification_get_the_looped_host_status(hip):
+    # one launch: three codes of length 1 / counts summing to 510 written over a DC or an AC specification, between intact packets
+    from lemon_amd import jpeg_host
+    from tests import jpegverdictfx as fx
+    _, _, bases = fx.load_golden()
+    batch, good_ref = [], {}
+    for name in fx.TAMPER_BASES[:2]:
+        good = jpeg_host.pack(bases[name])[0]
+        good_ref[len(batch)] = jpeg_host.decode_record(bases[name])[0].data
+        batch.append(good)
+        for _, p in fx.tampered_packets(name, bases[name]):
+            good_ref[len(batch) + 1] = good_ref[len(batch) - 1]
+            batch += [good._replace(data=p), good]
+    assert len(batch) == 18
+    status, records, lay, after, before = _launch(batch, jpeg_host.SUBSEQ_MIN)
+    assert np.array_equal(after, before)                              # the packets are only read
+    assert lay.groups >= len(batch) and min(pk.scan_bytes for pk in batch) > jpeg_host.SUBSEQ_MIN      # every scan: several lanes
+    for k, pk in enumerate(batch):
+        rec = np.full(records[k].size, POISON, np.uint8)
+        want = jpeg_host.entropy_par_host(pk.data, rec, jpeg_host.SUBSEQ_MIN)
+        assert status[k] == want == (0 if k in good_ref else 13), (k, int(status[k]), want)
+        if k in good_ref:
+            assert np.array_equal(records[k], good_ref[k]) and np.array_equal(rec, good_ref[k]), k
+        else:
+            assert (records[k] == POISON).all() and (rec == POISON).all(), k      # a refused image's record is not touched
+
+
 def test_decode_jpegs_with_device_entropy_equals_pil(hip, tmp_path):
     from lemon_amd.data import RaggedImages, decode_jpegs
     cases = jpegfx.accepted_cases()

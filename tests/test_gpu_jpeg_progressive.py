@@ -133,6 +133,31 @@ def test_corrupt_scans_get_the_host_codes_status_and_leave_their_neighbours_alon
     assert want[1::2] == [10, 11, 10, 11, 11], want                   # size-2 symbol: code; run past the end, early end, left over: stream
 
 
+def test_packets_with_a_tampered_huffman_specification_get_the_looped_host_status(hip):
+    # one launch: a specification of the pool overwritten (three codes of length 1, counts summing to 510, values that run past
+    # the packet's end) or its pool offset pointing past the packet, between intact packets
+    from lemon_amd import jpeg_host
+    from tests import jpegverdictfx as fx
+    _, _, bases = fx.load_golden()
+    batch, good_ref = [], {}
+    for name in fx.TAMPER_BASES[2:]:
+        good = jpeg_host.prog_pack(bases[name])[0]
+        good_ref[len(batch)] = jpeg_host.decode_record(bases[name], progressive=True)[0].data
+        batch.append(good)
+        for _, p in fx.tampered_packets(name, bases[name]):
+            good_ref[len(batch) + 1] = good_ref[len(batch) - 1]
+            batch += [good._replace(data=p), good]
+    assert len(batch) == 26
+    status, records, lay, after, before = _launch(batch)
+    assert np.array_equal(after, before)                              # the packets are only read
+    for k, pk in enumerate(batch):
+        rec = np.full(records[k].size, POISON, np.uint8)
+        want = jpeg_host.prog_entropy_par_host(pk.data, rec)
+        assert status[k] == want == (0 if k in good_ref else 8), (k, int(status[k]), want)
+        if k in good_ref:
+            assert np.array_equal(records[k], good_ref[k]) and np.array_equal(rec, good_ref[k]), k
+
+
 def _write_mixed(d, n=40):
     """n files of three sizes, every third progressive (with and without restart markers, one grayscale)."""
     rng = np.random.default_rng(7)
