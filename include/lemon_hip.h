@@ -538,6 +538,45 @@ int lemon_grid_f1_ks(const float *d1_dev, const float *D_n_dev, const float *dis
                      double xtol, int maxfun, void *ws_dev, int64_t ws_bytes, double *scores_dev, double *f1_dev,
                      double *thres_dev, void *stream);
 
+/* The local searches in front of the grid (lib/metrics/utils.py:143-158: scipy.optimize.minimize with Powell and Nelder-Mead
+ * from every start point, options={}) as ONE launch: S searches, one workgroup each, no host synchronisation inside a search.
+ * The record is lemon_grid_f1_ks's: d1 [n], six neighbour arrays [n, kmax] (row pitch kmax), y [n] uint8 (is_mislabel).
+ * x0 [S, 6] float64 start points in the order (beta, gamma, tau_1_n, tau_2_n, tau_1_m, tau_2_m); spec [S, 4] int32 =
+ * (method, k with 1 <= k <= kmax: the search sees the [n, k] prefix of the record, force_zero mask, force_one mask; bit i of a
+ * mask = hyper-parameter i, zeros are applied first as metrics.unpack_vector does; the optimiser keeps moving a forced
+ * coordinate, the objective ignores it).  The objective is maximize_metric's: 0.0 when a score is not finite, else -F1 at the
+ * threshold of optimize_f1_efficient (fminbound, xtol 1e-8, maxfun 500), scores with lemon_score's arithmetic.  The optimisers
+ * restate scipy 1.15 in IEEE double (csrc/hparam_search_core.hpp): out[s] = (x, fun, nfev, nit, status) of
+ * scipy.optimize.minimize on that objective, bit for bit; status is scipy's (0 ok, 1 maxfev, 2 maxiter, 3 NaN), or 5 where
+ * scipy's bracket() would raise at its iteration limit.  Nelder-Mead orders tied vertices as np.argsort does on x86-64 with
+ * AVX-512 (an 8-lane network, not a stable sort).
+ * lemon_hparam_search: every pointer is a device pointer; ws: lemon_hparam_search_workspace_bytes(n, S) bytes, 8-byte
+ * aligned, used when the score row of a search (8 n bytes, beside n bytes of labels) does not fit into 48 KB of LDS.  The call
+ * waits for the stream once, to check spec before anything is launched.  Refused with LEMON_E_INVALID, nothing written: a null
+ * pointer, n <= 0, k outside [1, kmax], an unknown method, a mask beyond six bits, a short workspace, S > 65535.
+ * lemon_hparam_search_host / lemon_hparam_objective_host: the same header compiled for the host (threads looped, libm's
+ * exp), host pointers; for the tests, no product path calls them.  The objective returns NaN for arguments out of contract.
+ * lemon_hparam_search_set_test_knobs: test-only.  force_workspace != 0 keeps the score rows out of LDS; the four caps
+ * (Nelder-Mead maxiter / maxfev, Powell maxiter / maxfev; <= 0 = scipy's defaults 1200, 1200, 6000, 6000) apply to both
+ * forms.  Recorded time (tools/hparam_search_time.py): 64 searches at n = 5 000, kmax = 50 in 0.42 s. */
+#define LEMON_SEARCH_NELDER_MEAD 0
+#define LEMON_SEARCH_POWELL 1
+typedef struct LemonSearchResult { double x[6]; double fun; int32_t nfev, nit, status, pad; } LemonSearchResult;
+int64_t lemon_hparam_search_workspace_bytes(int64_t n, int S); /* < 0: LEMON_E_* */
+int lemon_hparam_search(const float *d1, const float *D_n, const float *dists_tr_n, const float *dists_n,
+                        const float *D_m, const float *dists_tr_m, const float *dists_m, const uint8_t *y,
+                        int64_t n, int kmax, int S, const double *x0, const int32_t *spec,
+                        void *ws, int64_t ws_bytes, LemonSearchResult *out, void *stream);
+int lemon_hparam_search_host(const float *d1, const float *D_n, const float *dists_tr_n, const float *dists_n,
+                             const float *D_m, const float *dists_tr_m, const float *dists_m, const uint8_t *y,
+                             int64_t n, int kmax, int S, const double *x0, const int32_t *spec,
+                             void *ws, int64_t ws_bytes, LemonSearchResult *out);
+double lemon_hparam_objective_host(const float *d1, const float *D_n, const float *dists_tr_n, const float *dists_n,
+                                   const float *D_m, const float *dists_tr_m, const float *dists_m, const uint8_t *y,
+                                   int64_t n, int kmax, int k, int force_zero, int force_one, const double *x);
+int lemon_hparam_search_set_test_knobs(int force_workspace, int nm_maxiter, int nm_maxfun, int powell_maxiter,
+                                       int powell_maxfun);
+
 /* ---- k-means on caption embeddings + the deep-kNN label score ------------------------ */
 
 /* FaissKMeans.predict = index.search(x, 1) (lib/datasets/clustering.py:38-41) and the assignment step of faiss.Kmeans.train

@@ -32,11 +32,22 @@ EXPORTS = [
     "lemon_jpeg_prog_entropy_workspace_bytes", "lemon_jpeg_prog_entropy_par_host",
     "lemon_tokenizer_create_bpe", "lemon_tokenizer_create_wordpiece", "lemon_tokenizer_free", "lemon_tokenizer_table_info",
     "lemon_tokenize", "lemon_tokenize_host",
+    "lemon_hparam_search_workspace_bytes", "lemon_hparam_search", "lemon_hparam_search_host", "lemon_hparam_objective_host",
+    "lemon_hparam_search_set_test_knobs",
 ]
 
 
 class LemonHipError(RuntimeError):
     pass
+
+
+SEARCH_NELDER_MEAD, SEARCH_POWELL = 0, 1   # LEMON_SEARCH_*
+SEARCH_METHODS = {"Nelder-Mead": SEARCH_NELDER_MEAD, "Powell": SEARCH_POWELL}
+
+
+class SearchResult(ctypes.Structure):      # LemonSearchResult
+    _fields_ = [("x", ctypes.c_double * 6), ("fun", ctypes.c_double), ("nfev", ctypes.c_int32), ("nit", ctypes.c_int32),
+                ("status", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
 class SearchInfo(ctypes.Structure):
@@ -173,6 +184,13 @@ def load():
     lib.lemon_tokenizer_table_info.argtypes = [vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)]
     lib.lemon_tokenize.argtypes = [vp, vp, c_i64, vp, c_i64, c_int, i32, vp, vp, vp, vp]
     lib.lemon_tokenize_host.argtypes = [vp, vp, c_i64, vp, c_i64, c_int, i32, vp, vp, vp]
+    lib.lemon_hparam_search_workspace_bytes.argtypes = [c_i64, c_int]
+    lib.lemon_hparam_search_workspace_bytes.restype = c_i64
+    lib.lemon_hparam_search.argtypes = [vp] * 8 + [c_i64, c_int, c_int, vp, vp, vp, c_i64, vp, vp]
+    lib.lemon_hparam_search_host.argtypes = [vp] * 8 + [c_i64, c_int, c_int, vp, vp, vp, c_i64, vp]
+    lib.lemon_hparam_objective_host.argtypes = [vp] * 8 + [c_i64, c_int, c_int, c_int, c_int, vp]
+    lib.lemon_hparam_objective_host.restype = ctypes.c_double
+    lib.lemon_hparam_search_set_test_knobs.argtypes = [c_int] * 5
     _lib = lib
     return lib
 

@@ -1,10 +1,12 @@
 // The bounded-Brent threshold search of the hyper-parameter grid, shared by lemon_grid_f1 (gridf1.hip) and lemon_grid_f1_ks
 // (ksweep.hip): one wavefront per score row, a faithful restatement of scipy's _minimize_scalar_bounded in IEEE double (no FMA
-// contraction inside the search), F1 from integer counts.  A non-finite score row yields F1 = 0, thres = NaN.
+// contraction inside the search; hps::fminbound of hparam_search_core.hpp, shared with lemon_hparam_search), F1 from integer counts.  A non-finite score row yields F1 = 0, thres = NaN.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+
+#include "hparam_search_core.hpp"
 
 namespace {
 
@@ -24,8 +26,6 @@ __device__ __forceinline__ double neg_f1(const F1Ctx &c, double t) {
     const long long denom = 2 * tp + (pred - tp) + (c.pos - tp);
     return denom ? -(2.0 * (double)tp / (double)denom) : -0.0;
 }
-
-__device__ __forceinline__ double sgn1(double v) { return v < 0.0 ? -1.0 : 1.0; }   // np.sign(v) + (v == 0)
 
 __global__ __launch_bounds__(256) void k_grid_brent(const double *__restrict__ score, const uint8_t *__restrict__ y,
                                                     int64_t n, int G, double xatol, int maxfun, double sqrt_eps,
@@ -56,65 +56,8 @@ __global__ __launch_bounds__(256) void k_grid_brent(const double *__restrict__ s
     if (bad) { if (lane == 0) { out_f1[g] = 0.0; out_thres[g] = __builtin_nan(""); } return; }
 
     // scipy.optimize._optimize._minimize_scalar_bounded (scipy 1.15), every wave-uniform value in double
-    double a = lo, b = hi;
-    double fulc = a + golden_mean * (b - a);
-    double nfc = fulc, xf = fulc;
-    double rat = 0.0, e = 0.0;
-    double x = xf;
-    double fx = neg_f1(c, x);
-    int num = 1;
-    double fu = INFINITY;
-    double ffulc = fx, fnfc = fx;
-    double xm = 0.5 * (a + b);
-    double tol1 = sqrt_eps * fabs(xf) + xatol / 3.0;
-    double tol2 = 2.0 * tol1;
-    while (fabs(xf - xm) > (tol2 - 0.5 * (b - a))) {
-        int golden = 1;
-        if (fabs(e) > tol1) {                            // parabolic fit
-            golden = 0;
-            double r = (xf - nfc) * (fx - ffulc);
-            double q = (xf - fulc) * (fx - fnfc);
-            double p = (xf - fulc) * q - (xf - nfc) * r;
-            q = 2.0 * (q - r);
-            if (q > 0.0) p = -p;
-            q = fabs(q);
-            r = e;
-            e = rat;
-            if ((fabs(p) < fabs(0.5 * q * r)) && (p > q * (a - xf)) && (p < q * (b - xf))) {
-                rat = (p + 0.0) / q;
-                x = xf + rat;
-                if (((x - a) < tol2) || ((b - x) < tol2)) rat = tol1 * sgn1(xm - xf);
-            } else {
-                golden = 1;
-            }
-        }
-        if (golden) {
-            e = (xf >= xm) ? a - xf : b - xf;
-            rat = golden_mean * e;
-        }
-        const double ar = fabs(rat);
-        x = xf + sgn1(rat) * (ar > tol1 ? ar : tol1);    // np.maximum(abs(rat), tol1); neither is NaN here
-        fu = neg_f1(c, x);
-        num += 1;
-        if (fu <= fx) {
-            if (x >= xf) a = xf; else b = xf;
-            fulc = nfc; ffulc = fnfc;
-            nfc = xf; fnfc = fx;
-            xf = x; fx = fu;
-        } else {
-            if (x < xf) a = x; else b = x;
-            if ((fu <= fnfc) || (nfc == xf)) {
-                fulc = nfc; ffulc = fnfc;
-                nfc = x; fnfc = fu;
-            } else if ((fu <= ffulc) || (fulc == xf) || (fulc == nfc)) {
-                fulc = x; ffulc = fu;
-            }
-        }
-        xm = 0.5 * (a + b);
-        tol1 = sqrt_eps * fabs(xf) + xatol / 3.0;
-        tol2 = 2.0 * tol1;
-        if (num >= maxfun) break;
-    }
+    struct NegF1 { const F1Ctx &c; __device__ double operator()(double t) { return neg_f1(c, t); } } f{c};
+    const double xf = hps::fminbound(f, lo, hi, xatol, maxfun, sqrt_eps, golden_mean);
     const double best = -neg_f1(c, xf);                  // optimize_f1_efficient re-evaluates at the returned x
     if (lane == 0) { out_f1[g] = best; out_thres[g] = xf; }
 }

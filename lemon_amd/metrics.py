@@ -215,10 +215,13 @@ def grid_points(grid, force_zero=(), force_one=()):
 
 def maximize_metric(score_fn, y, grid, x0s, obj_func=optimize_f1_efficient, obj_func_args=None,
                     force_zero=(), force_one=(), scipy_methods=("Powell", "Nelder-Mead"), rec_for_lbfgs=None,
-                    batch_grid=None, lbfgs_device="cpu"):
+                    batch_grid=None, lbfgs_device="cpu", local_search=None):
     """lib/metrics/utils.py:151-196.  score_fn(hparams dict) -> scores (numpy [n]); y = is_mislabel.
     Order of candidates (and therefore tie-breaking on equal objective) follows the reference:
-    scipy local searches from every start, LBFGS-polished starts, then the full grid; strict '>'."""
+    scipy local searches from every start, LBFGS-polished starts, then the full grid; strict '>'.
+    local_search(x0s, scipy_methods, force_zero, force_one) -> [(x, fun), ...] for each x0, for each method: serves the scipy
+    searches from one device launch (ops.local_search bound to the record: the same optimisers on the same objective, bit
+    for bit); the results go through the same strict '>' in the same order.  None: scipy on the host, as the reference."""
     obj_func_args = obj_func_args or {}
     y = np.asarray(y)
 
@@ -230,11 +233,18 @@ def maximize_metric(score_fn, y, grid, x0s, obj_func=optimize_f1_efficient, obj_
         return -obj_func(y, score, **obj_func_args)
 
     best_x, best_val = None, -1
-    for x0 in x0s:
-        for method in scipy_methods:
-            res = minimize(objective, x0, method=method, options={})
-            if -res.fun > best_val:
-                best_val, best_x = -res.fun, res.x
+    if local_search is not None:
+        found = list(local_search(x0s, scipy_methods, force_zero, force_one))
+        assert len(found) == len(x0s) * len(scipy_methods), "local_search: one result per (x0, method) expected"
+        for x, fun in found:
+            if -fun > best_val:
+                best_val, best_x = -fun, x
+    else:
+        for x0 in x0s:
+            for method in scipy_methods:
+                res = minimize(objective, x0, method=method, options={})
+                if -res.fun > best_val:
+                    best_val, best_x = -res.fun, res.x
     if rec_for_lbfgs is not None:
         import torch
         rec_t = {k: torch.as_tensor(np.asarray(v), dtype=torch.float64 if k == "d_1" else torch.float32).to(lbfgs_device)

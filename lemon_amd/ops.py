@@ -786,6 +786,53 @@ def lemon_score(rec, hparams, return_dn=False):
     return (score, dn, dm) if return_dn else score
 
 
+def local_search(rec, y, x0s, methods=("Powell", "Nelder-Mead"), force_zero=(), force_one=(), ks=None, return_info=False):
+    """The scipy local searches of maximize_metric (lib/metrics/utils.py:151-158) on the device-resident record `rec`, all in
+    ONE launch and one copy back (lemon_hparam_search): for each x0 of `x0s`, for each method -- the reference's order -- what
+    scipy.optimize.minimize(objective, x0, method=method, options={}) returns on maximize_metric's objective, bit for bit.
+    -> [(x [6] float64, fun), ...]; with `ks` (values of knn_k, each <= the record's depth: a search sees the [n, k] prefix)
+    one such list per k.  return_info: (x, fun, nfev, nit, status) instead.  force_zero / force_one: names of HP_ORDER."""
+    dev = rec["D_n"].device
+    f32 = lambda key: dev_f32(rec[key], key)
+    d1, Dn, trn, dn, Dm, trm, dm = (f32(key) for key in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m"))
+    n, kmax = Dn.shape
+    k_list = [kmax] if ks is None else [int(k) for k in ks]
+    if any(k < 1 or k > kmax for k in k_list):
+        raise ValueError(f"local_search: every k must lie in 1 .. {kmax} (the record's depth), got {k_list}")
+    unknown = [m for m in methods if m not in _lib.SEARCH_METHODS]
+    if unknown:
+        raise ValueError(f"local_search: unknown method(s) {unknown}; the device path has {sorted(_lib.SEARCH_METHODS)}")
+    fz = sum(1 << HP_ORDER.index(nm) for nm in set(force_zero))
+    fo = sum(1 << HP_ORDER.index(nm) for nm in set(force_one))
+    x0s = np.asarray(x0s, dtype=np.float64).reshape(-1, 6)
+    per_k = len(x0s) * len(methods)
+    S = per_k * len(k_list)
+    if S == 0:
+        return [] if ks is None else [[] for _ in k_list]
+    x0 = np.repeat(np.tile(x0s, (len(k_list), 1)), len(methods), axis=0)              # for each k, each x0, each method
+    spec = np.array([[_lib.SEARCH_METHODS[m], k, fz, fo] for k in k_list for _ in range(len(x0s)) for m in methods], dtype=np.int32)
+    lib = _lib.load()
+    need = lib.lemon_hparam_search_workspace_bytes(n, S)
+    if need < 0:
+        _lib.check(int(need), "lemon_hparam_search_workspace_bytes")
+    yb = torch.as_tensor(np.asarray(y).astype(bool).astype(np.uint8)).to(dev)
+    x0_d, spec_d = torch.from_numpy(x0).to(dev), torch.from_numpy(spec).to(dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(S * ctypes.sizeof(_lib.SearchResult), dtype=torch.uint8, device=dev)
+    _call("lemon_hparam_search", dev, ptr(d1), ptr(Dn), ptr(trn), ptr(dn), ptr(Dm), ptr(trm), ptr(dm), ptr(yb), n, kmax, S,
+          ptr(x0_d), ptr(spec_d), ptr(ws), need, ptr(out))
+    res = (_lib.SearchResult * S).from_buffer_copy(out.cpu().numpy().tobytes())
+    rows = [(np.array(list(r.x), dtype=np.float64), float(r.fun)) + ((int(r.nfev), int(r.nit), int(r.status)) if return_info else ())
+            for r in res]
+    bad = [s for s, r in enumerate(res) if r.status == 5]
+    if bad:
+        raise _lib.LemonHipError(f"lemon_hparam_search: search(es) {bad} ended at the iteration limit of scipy's bracket(), where "
+                                 "scipy.optimize.minimize raises RuntimeError")
+    if ks is None:
+        return rows
+    return [rows[t * per_k:(t + 1) * per_k] for t in range(len(k_list))]
+
+
 def _stack_col(df, col, device):
     return torch.from_numpy(np.stack(df[col].values).astype(np.float32, copy=False)).to(device)
 

@@ -61,6 +61,10 @@ def build_parser():
                    help="where the SoftMargin/LBFGS polish of the hyper-parameter search runs (lib/metrics/utils.py:121-149)")
     p.add_argument("--hparam_grid", default="full", choices=["full", "small"],
                    help="'small' = 3x3x2x2 grid for smoke runs (reference grid is 21x21x4x4)")
+    p.add_argument("--hparam_search", default="host", choices=["host", "device"],
+                   help="where the Powell / Nelder-Mead searches in front of the grid run: 'host' = scipy.optimize.minimize, one "
+                        "score launch and one copy per objective evaluation (the reference's way); 'device' = all searches of a "
+                        "run in one launch (lemon_hparam_search), the same optimisers restated in IEEE double, same results")
     p.add_argument("--knn_k_sweep", default=None, type=str,
                    help="comma-separated knn_k values, e.g. 1,2,5,10,15,20,30,50 (the reference's grid, experiments.py:86): embed, build "
                         "the DB and search ONCE at the largest, then run the tail of a --knn_k run for every value on the prefix "
@@ -215,7 +219,8 @@ def _grid_setup(args):
 
 def _sweep_tail(args, df, out_dir, device, ks):
     """The tail of a run for every k of the sweep, on the prefix of the record searched at max(ks); the grid of all ks comes
-    from ONE ops.grid_f1_ks call made in front of the loop."""
+    from ONE ops.grid_f1_ks call made in front of the loop and, with --hparam_search device, the local searches of all ks from
+    ONE ops.local_search call beside it."""
     import copy
     import json
     from . import metrics as M, ops
@@ -224,12 +229,16 @@ def _sweep_tail(args, df, out_dir, device, ks):
         df["d_1"] = 0.0
     deep = {c: torch.from_numpy(np.stack(df[c].values)) for c in NEIGHBOR_COLUMNS}     # the gathered record, [n, max(ks)]
     setup = _grid_setup(args)
-    grid_f1 = hps = None
+    grid_f1 = hps = searched = searched_with = None
     if setup is not None:
         df_val = df.query('sset == "val"')
         hps = M.grid_points(*setup)
-        grid_f1 = ops.grid_f1_ks(_device_rec(df_val, device), df_val["is_mislabel"].values,
-                                 [[hp[n] for n in M.HP_NAMES] for hp in hps], ks)[0]
+        rec_deep = _device_rec(df_val, device)
+        grid_f1 = ops.grid_f1_ks(rec_deep, df_val["is_mislabel"].values, [[hp[n] for n in M.HP_NAMES] for hp in hps], ks)[0]
+        if getattr(args, "hparam_search", "host") == "device":
+            searched_with = (SEARCH_STARTS, SEARCH_METHODS, list(setup[1]), list(setup[2]))
+            searched = ops.local_search(rec_deep, df_val["is_mislabel"].values, SEARCH_STARTS, SEARCH_METHODS, setup[1], setup[2],
+                                        ks=ks)
     selection = {}
     for t, k in enumerate(ks):
         out_k = out_dir / f"knn_k={k}"
@@ -247,8 +256,14 @@ def _sweep_tail(args, df, out_dir, device, ks):
             assert asked == hps, "the grid of maximize_metric is not the grid lemon_grid_f1_ks was called with"
             return grid_f1[t]
 
+        def served_search(x0s, methods, force_zero, force_one, t=t):
+            asked = ([list(x0) for x0 in x0s], tuple(methods), list(force_zero), list(force_one))
+            assert asked == searched_with, "the searches of maximize_metric are not the ones lemon_hparam_search was called with"
+            return searched[t]
+
         print(f"---- knn_k = {k} ----")
-        sel_res = _tail(args_k, df_k, out_k, device, batch_grid=served if grid_f1 is not None else None)
+        sel_res = _tail(args_k, df_k, out_k, device, batch_grid=served if grid_f1 is not None else None,
+                        local_search=served_search if searched is not None else None)
         entry = None
         if sel_res is not None:
             entry = {"selected_val": sel_res.get("selected_val"), **{name: float(sel_res[name]) for name in M.HP_NAMES},
@@ -266,10 +281,15 @@ def _sweep_tail(args, df, out_dir, device, ks):
         f.write("done")
 
 
-def _tail(args, df, out_dir, device, batch_grid=None):
+SEARCH_STARTS = [[0] * 6, [0.5] * 6, [1] * 6, [10] * 6]       # the start points and methods the reference hands to maximize_metric
+SEARCH_METHODS = ("Powell", "Nelder-Mead")
+
+
+def _tail(args, df, out_dir, device, batch_grid=None, local_search=None):
     """Everything behind the per-sample record: the d1 ablation, the hyper-parameter search, the final score, the metrics and
     the files of a run.  Returns agg_results' entry (None with --real_dataset / --skip_hparam_optim).  batch_grid: serves the
-    grid's F1 values in place of the ops.grid_f1 call (the k sweep)."""
+    grid's F1 values in place of the ops.grid_f1 call (the k sweep); local_search: serves the local searches in place of the
+    ops.local_search call of --hparam_search device (the k sweep)."""
     from . import metrics as M, ops
     device_rec = lambda frame: _device_rec(frame, device)
     sel_res = None
@@ -297,8 +317,11 @@ def _tail(args, df, out_dir, device, batch_grid=None):
                 grid, force_zero, force_one = _grid_setup(args)
                 rec_lbfgs = {c: (df_val[c].values if c == "d_1" else np.stack(df_val[c].values))
                              for c in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")}
+                if local_search is None and getattr(args, "hparam_search", "host") == "device":
+                    local_search = lambda x0s, methods, fz, fo: ops.local_search(rec_val, y_val, x0s, methods, fz, fo)
                 best, best_f1, best_thres = M.maximize_metric(
-                    score_fn, y_val, grid, [[0] * 6, [0.5] * 6, [1] * 6, [10] * 6], M.optimize_f1_efficient, {},
+                    score_fn, y_val, grid, SEARCH_STARTS, M.optimize_f1_efficient, {}, scipy_methods=SEARCH_METHODS,
+                    local_search=local_search,
                     force_zero=force_zero, force_one=force_one, rec_for_lbfgs=rec_lbfgs,
                     lbfgs_device=str(device) if args.lbfgs_device == "cuda" else "cpu",
                     batch_grid=batch_grid or
