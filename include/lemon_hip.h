@@ -577,6 +577,38 @@ double lemon_hparam_objective_host(const float *d1, const float *D_n, const floa
 int lemon_hparam_search_set_test_knobs(int force_workspace, int nm_maxiter, int nm_maxfun, int powell_maxiter,
                                        int powell_maxfun);
 
+/* The LBFGS polish of maximize_metric (lib/metrics/utils.py:160-176: torch_minimize :129-141 on the SoftMargin proxy
+ * :121-127,148-149) as ONE launch: S polishes on one record, one workgroup each.  The record and y as in lemon_hparam_search.
+ * x0 [S, 6] double: the start points; spec int32 [S, 3]: (k, force_zero, force_one) with 1 <= k <= kmax (the polish sees
+ * the [n, k] prefix) and the six-bit force masks of lemon_hparam_search.  outer_steps: optimizer.step calls, 1 .. 20 (the
+ * reference's is 20).  The proxy is loss = mean_i log1p(exp(-t_i s_i)), t = 2 y - 1, s = the score with ONE exp per element,
+ * exp(-(tau_1 D + tau_2 tr)), in float64 on the float32 record, with its gradient in the same pass; exp and log1p are restated
+ * with explicit fma and every sum has a fixed order (csrc/lbfgs_core.hpp), so the result is a function of the record alone and
+ * the device and the host twin agree bit for bit.  It is not bit-compatible with torch's float32-promoted two-exp expression;
+ * the candidate is scored exactly afterwards, as the reference does.  The optimiser restates torch.optim.LBFGS (torch 2.10:
+ * lr 0.1, max_iter 20, max_eval 25, history 100, strong_wolfe) with the state kept over the outer steps.  Nothing is clamped:
+ * an overflow becomes inf or NaN as in torch and flows to the result; out[s].status is 1 where x or loss is not finite, else 0.
+ * lemon_lbfgs_polish: every pointer is a device pointer; the call waits for the stream once, to check spec before anything
+ * is launched.  Refused with LEMON_E_INVALID, nothing written: a null pointer, n <= 0, k outside [1, kmax], a mask beyond six
+ * bits, S > 65535, outer_steps outside [1, 20].
+ * lemon_lbfgs_polish_host / lemon_lbfgs_proxy_host: the same header compiled for the host (threads looped, the same
+ * reduction order), host pointers; for the tests, no product path calls them.  The proxy returns the loss and writes grad[6];
+ * NaN for arguments out of contract.  lemon_lbfgs_math_host: test-only, the restated exp (fn 0) / log1p (fn 1) on count
+ * host doubles. */
+typedef struct LemonPolishResult { double x[6]; double loss; int32_t nfev, nit, status, pad; } LemonPolishResult;
+int lemon_lbfgs_polish(const float *d1, const float *D_n, const float *dists_tr_n, const float *dists_n,
+                       const float *D_m, const float *dists_tr_m, const float *dists_m, const uint8_t *y,
+                       int64_t n, int kmax, int S, const double *x0, const int32_t *spec, int outer_steps,
+                       LemonPolishResult *out, void *stream);
+int lemon_lbfgs_polish_host(const float *d1, const float *D_n, const float *dists_tr_n, const float *dists_n,
+                            const float *D_m, const float *dists_tr_m, const float *dists_m, const uint8_t *y,
+                            int64_t n, int kmax, int S, const double *x0, const int32_t *spec, int outer_steps,
+                            LemonPolishResult *out);
+double lemon_lbfgs_proxy_host(const float *d1, const float *D_n, const float *dists_tr_n, const float *dists_n,
+                              const float *D_m, const float *dists_tr_m, const float *dists_m, const uint8_t *y,
+                              int64_t n, int kmax, int k, int force_zero, int force_one, const double *x, double *grad);
+int lemon_lbfgs_math_host(int fn, const double *x, int64_t count, double *out);
+
 /* ---- k-means on caption embeddings + the deep-kNN label score ------------------------ */
 
 /* FaissKMeans.predict = index.search(x, 1) (lib/datasets/clustering.py:38-41) and the assignment step of faiss.Kmeans.train

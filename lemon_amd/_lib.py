@@ -34,6 +34,7 @@ EXPORTS = [
     "lemon_tokenize", "lemon_tokenize_host",
     "lemon_hparam_search_workspace_bytes", "lemon_hparam_search", "lemon_hparam_search_host", "lemon_hparam_objective_host",
     "lemon_hparam_search_set_test_knobs",
+    "lemon_lbfgs_polish", "lemon_lbfgs_polish_host", "lemon_lbfgs_proxy_host", "lemon_lbfgs_math_host",
 ]
 
 
@@ -48,6 +49,14 @@ SEARCH_METHODS = {"Nelder-Mead": SEARCH_NELDER_MEAD, "Powell": SEARCH_POWELL}
 class SearchResult(ctypes.Structure):      # LemonSearchResult
     _fields_ = [("x", ctypes.c_double * 6), ("fun", ctypes.c_double), ("nfev", ctypes.c_int32), ("nit", ctypes.c_int32),
                 ("status", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class PolishResult(ctypes.Structure):      # LemonPolishResult
+    _fields_ = [("x", ctypes.c_double * 6), ("loss", ctypes.c_double), ("nfev", ctypes.c_int32), ("nit", ctypes.c_int32),
+                ("status", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+POLISH_OUTER_STEPS = 20                    # optimizer.step calls of torch_minimize (lib/metrics/utils.py:129-141)
 
 
 class SearchInfo(ctypes.Structure):
@@ -191,6 +200,11 @@ def load():
     lib.lemon_hparam_objective_host.argtypes = [vp] * 8 + [c_i64, c_int, c_int, c_int, c_int, vp]
     lib.lemon_hparam_objective_host.restype = ctypes.c_double
     lib.lemon_hparam_search_set_test_knobs.argtypes = [c_int] * 5
+    lib.lemon_lbfgs_polish.argtypes = [vp] * 8 + [c_i64, c_int, c_int, vp, vp, c_int, vp, vp]
+    lib.lemon_lbfgs_polish_host.argtypes = [vp] * 8 + [c_i64, c_int, c_int, vp, vp, c_int, vp]
+    lib.lemon_lbfgs_proxy_host.argtypes = [vp] * 8 + [c_i64, c_int, c_int, c_int, c_int, vp, vp]
+    lib.lemon_lbfgs_proxy_host.restype = ctypes.c_double
+    lib.lemon_lbfgs_math_host.argtypes = [c_int, vp, c_i64, vp]
     _lib = lib
     return lib
 

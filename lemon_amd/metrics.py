@@ -215,13 +215,16 @@ def grid_points(grid, force_zero=(), force_one=()):
 
 def maximize_metric(score_fn, y, grid, x0s, obj_func=optimize_f1_efficient, obj_func_args=None,
                     force_zero=(), force_one=(), scipy_methods=("Powell", "Nelder-Mead"), rec_for_lbfgs=None,
-                    batch_grid=None, lbfgs_device="cpu", local_search=None):
+                    batch_grid=None, lbfgs_device="cpu", local_search=None, lbfgs_polish=None):
     """lib/metrics/utils.py:151-196.  score_fn(hparams dict) -> scores (numpy [n]); y = is_mislabel.
     Order of candidates (and therefore tie-breaking on equal objective) follows the reference:
     scipy local searches from every start, LBFGS-polished starts, then the full grid; strict '>'.
     local_search(x0s, scipy_methods, force_zero, force_one) -> [(x, fun), ...] for each x0, for each method: serves the scipy
     searches from one device launch (ops.local_search bound to the record: the same optimisers on the same objective, bit
-    for bit); the results go through the same strict '>' in the same order.  None: scipy on the host, as the reference."""
+    for bit); the results go through the same strict '>' in the same order.  None: scipy on the host, as the reference.
+    lbfgs_polish(x0s, force_zero, force_one) -> [x, ...], one candidate per x0: serves the LBFGS polish from one device launch
+    (ops.lbfgs_polish bound to the record) in place of _torch_lbfgs; every candidate is scored by the same objective at the
+    same place in the order, non-finite ones are skipped.  None: _torch_lbfgs on rec_for_lbfgs, as before."""
     obj_func_args = obj_func_args or {}
     y = np.asarray(y)
 
@@ -245,7 +248,16 @@ def maximize_metric(score_fn, y, grid, x0s, obj_func=optimize_f1_efficient, obj_
                 res = minimize(objective, x0, method=method, options={})
                 if -res.fun > best_val:
                     best_val, best_x = -res.fun, res.x
-    if rec_for_lbfgs is not None:
+    if lbfgs_polish is not None:
+        polished = [np.asarray(c, dtype=np.float64) for c in lbfgs_polish(x0s, force_zero, force_one)]
+        assert len(polished) == len(x0s), "lbfgs_polish: one candidate per x0 expected"
+        for cand in polished:
+            if not np.all(np.isfinite(cand)):        # a diverged polish: skipped, as below
+                continue
+            val = -objective(cand)
+            if val > best_val:
+                best_val, best_x = val, cand
+    elif rec_for_lbfgs is not None:
         import torch
         rec_t = {k: torch.as_tensor(np.asarray(v), dtype=torch.float64 if k == "d_1" else torch.float32).to(lbfgs_device)
                  for k, v in rec_for_lbfgs.items()}

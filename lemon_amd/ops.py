@@ -833,6 +833,43 @@ def local_search(rec, y, x0s, methods=("Powell", "Nelder-Mead"), force_zero=(), 
     return [rows[t * per_k:(t + 1) * per_k] for t in range(len(k_list))]
 
 
+def lbfgs_polish(rec, y, x0s, force_zero=(), force_one=(), ks=None, return_info=False):
+    """The LBFGS polish of maximize_metric (lib/metrics/utils.py:160-176) on the device-resident record `rec`, all start points
+    in ONE launch and one copy back (lemon_lbfgs_polish): for each x0 of `x0s` -- the reference's order -- the x that 20
+    optimizer.step calls of torch.optim.LBFGS leave on the SoftMargin proxy, computed in fixed-order IEEE double (a function of
+    the record alone; not bit-compatible with torch's own float32-promoted run, see include/lemon_hip.h).
+    -> [(x [6] float64, status), ...], status 1 = x or the loss is not finite; with `ks` (values of knn_k, each <= the record's
+    depth: a polish sees the [n, k] prefix) one such list per k.  return_info: (x, status, loss, nfev, nit) instead.
+    force_zero / force_one: names of HP_ORDER."""
+    dev = rec["D_n"].device
+    f32 = lambda key: dev_f32(rec[key], key)
+    d1, Dn, trn, dn, Dm, trm, dm = (f32(key) for key in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m"))
+    n, kmax = Dn.shape
+    k_list = [kmax] if ks is None else [int(k) for k in ks]
+    if any(k < 1 or k > kmax for k in k_list):
+        raise ValueError(f"lbfgs_polish: every k must lie in 1 .. {kmax} (the record's depth), got {k_list}")
+    fz = sum(1 << HP_ORDER.index(nm) for nm in set(force_zero))
+    fo = sum(1 << HP_ORDER.index(nm) for nm in set(force_one))
+    x0s = np.asarray(x0s, dtype=np.float64).reshape(-1, 6)
+    per_k = len(x0s)
+    S = per_k * len(k_list)
+    if S == 0:
+        return [] if ks is None else [[] for _ in k_list]
+    x0 = np.tile(x0s, (len(k_list), 1))                                               # for each k, each x0
+    spec = np.array([[k, fz, fo] for k in k_list for _ in range(per_k)], dtype=np.int32)
+    yb = torch.as_tensor(np.asarray(y).astype(bool).astype(np.uint8)).to(dev)
+    x0_d, spec_d = torch.from_numpy(x0).to(dev), torch.from_numpy(spec).to(dev)
+    out = torch.empty(S * ctypes.sizeof(_lib.PolishResult), dtype=torch.uint8, device=dev)
+    _call("lemon_lbfgs_polish", dev, ptr(d1), ptr(Dn), ptr(trn), ptr(dn), ptr(Dm), ptr(trm), ptr(dm), ptr(yb), n, kmax, S,
+          ptr(x0_d), ptr(spec_d), _lib.POLISH_OUTER_STEPS, ptr(out))
+    res = (_lib.PolishResult * S).from_buffer_copy(out.cpu().numpy().tobytes())
+    rows = [(np.array(list(r.x), dtype=np.float64), int(r.status)) + ((float(r.loss), int(r.nfev), int(r.nit)) if return_info else ())
+            for r in res]
+    if ks is None:
+        return rows
+    return [rows[t * per_k:(t + 1) * per_k] for t in range(len(k_list))]
+
+
 def _stack_col(df, col, device):
     return torch.from_numpy(np.stack(df[col].values).astype(np.float32, copy=False)).to(device)
 

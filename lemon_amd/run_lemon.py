@@ -65,6 +65,11 @@ def build_parser():
                    help="where the Powell / Nelder-Mead searches in front of the grid run: 'host' = scipy.optimize.minimize, one "
                         "score launch and one copy per objective evaluation (the reference's way); 'device' = all searches of a "
                         "run in one launch (lemon_hparam_search), the same optimisers restated in IEEE double, same results")
+    p.add_argument("--lbfgs_polish", default="host", choices=["host", "device"],
+                   help="where the SoftMargin/LBFGS polish of the hyper-parameter search runs: 'host' = torch.optim.LBFGS driven "
+                        "from Python on --lbfgs_device (the reference's way; a few seconds a knn_k, launch-bound); 'device' = every "
+                        "polish of a run in one launch (lemon_lbfgs_polish), the same optimiser restated in fixed-order IEEE double: "
+                        "the candidates are a function of the record alone; they are scored exactly afterwards, as before")
     p.add_argument("--knn_k_sweep", default=None, type=str,
                    help="comma-separated knn_k values, e.g. 1,2,5,10,15,20,30,50 (the reference's grid, experiments.py:86): embed, build "
                         "the DB and search ONCE at the largest, then run the tail of a --knn_k run for every value on the prefix "
@@ -220,7 +225,7 @@ def _grid_setup(args):
 def _sweep_tail(args, df, out_dir, device, ks):
     """The tail of a run for every k of the sweep, on the prefix of the record searched at max(ks); the grid of all ks comes
     from ONE ops.grid_f1_ks call made in front of the loop and, with --hparam_search device, the local searches of all ks from
-    ONE ops.local_search call beside it."""
+    ONE ops.local_search call beside it; with --lbfgs_polish device the polishes of all ks from ONE ops.lbfgs_polish call."""
     import copy
     import json
     from . import metrics as M, ops
@@ -229,7 +234,7 @@ def _sweep_tail(args, df, out_dir, device, ks):
         df["d_1"] = 0.0
     deep = {c: torch.from_numpy(np.stack(df[c].values)) for c in NEIGHBOR_COLUMNS}     # the gathered record, [n, max(ks)]
     setup = _grid_setup(args)
-    grid_f1 = hps = searched = searched_with = None
+    grid_f1 = hps = searched = searched_with = polished = polished_with = None
     if setup is not None:
         df_val = df.query('sset == "val"')
         hps = M.grid_points(*setup)
@@ -239,6 +244,9 @@ def _sweep_tail(args, df, out_dir, device, ks):
             searched_with = (SEARCH_STARTS, SEARCH_METHODS, list(setup[1]), list(setup[2]))
             searched = ops.local_search(rec_deep, df_val["is_mislabel"].values, SEARCH_STARTS, SEARCH_METHODS, setup[1], setup[2],
                                         ks=ks)
+        if getattr(args, "lbfgs_polish", "host") == "device":
+            polished_with = (SEARCH_STARTS, list(setup[1]), list(setup[2]))
+            polished = ops.lbfgs_polish(rec_deep, df_val["is_mislabel"].values, SEARCH_STARTS, setup[1], setup[2], ks=ks)
     selection = {}
     for t, k in enumerate(ks):
         out_k = out_dir / f"knn_k={k}"
@@ -261,9 +269,15 @@ def _sweep_tail(args, df, out_dir, device, ks):
             assert asked == searched_with, "the searches of maximize_metric are not the ones lemon_hparam_search was called with"
             return searched[t]
 
+        def served_polish(x0s, force_zero, force_one, t=t):
+            asked = ([list(x0) for x0 in x0s], list(force_zero), list(force_one))
+            assert asked == polished_with, "the polishes of maximize_metric are not the ones lemon_lbfgs_polish was called with"
+            return [x for x, _ in polished[t]]
+
         print(f"---- knn_k = {k} ----")
         sel_res = _tail(args_k, df_k, out_k, device, batch_grid=served if grid_f1 is not None else None,
-                        local_search=served_search if searched is not None else None)
+                        local_search=served_search if searched is not None else None,
+                        lbfgs_polish=served_polish if polished is not None else None)
         entry = None
         if sel_res is not None:
             entry = {"selected_val": sel_res.get("selected_val"), **{name: float(sel_res[name]) for name in M.HP_NAMES},
@@ -285,11 +299,12 @@ SEARCH_STARTS = [[0] * 6, [0.5] * 6, [1] * 6, [10] * 6]       # the start points
 SEARCH_METHODS = ("Powell", "Nelder-Mead")
 
 
-def _tail(args, df, out_dir, device, batch_grid=None, local_search=None):
+def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_polish=None):
     """Everything behind the per-sample record: the d1 ablation, the hyper-parameter search, the final score, the metrics and
     the files of a run.  Returns agg_results' entry (None with --real_dataset / --skip_hparam_optim).  batch_grid: serves the
     grid's F1 values in place of the ops.grid_f1 call (the k sweep); local_search: serves the local searches in place of the
-    ops.local_search call of --hparam_search device (the k sweep)."""
+    ops.local_search call of --hparam_search device (the k sweep); lbfgs_polish: serves the polished starts in place of the
+    ops.lbfgs_polish call of --lbfgs_polish device (the k sweep)."""
     from . import metrics as M, ops
     device_rec = lambda frame: _device_rec(frame, device)
     sel_res = None
@@ -319,9 +334,11 @@ def _tail(args, df, out_dir, device, batch_grid=None, local_search=None):
                              for c in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")}
                 if local_search is None and getattr(args, "hparam_search", "host") == "device":
                     local_search = lambda x0s, methods, fz, fo: ops.local_search(rec_val, y_val, x0s, methods, fz, fo)
+                if lbfgs_polish is None and getattr(args, "lbfgs_polish", "host") == "device":
+                    lbfgs_polish = lambda x0s, fz, fo: [x for x, _ in ops.lbfgs_polish(rec_val, y_val, x0s, fz, fo)]
                 best, best_f1, best_thres = M.maximize_metric(
                     score_fn, y_val, grid, SEARCH_STARTS, M.optimize_f1_efficient, {}, scipy_methods=SEARCH_METHODS,
-                    local_search=local_search,
+                    local_search=local_search, lbfgs_polish=lbfgs_polish,
                     force_zero=force_zero, force_one=force_one, rec_for_lbfgs=rec_lbfgs,
                     lbfgs_device=str(device) if args.lbfgs_device == "cuda" else "cpu",
                     batch_grid=batch_grid or
