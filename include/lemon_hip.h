@@ -435,7 +435,7 @@ typedef struct {
     int grid, block;     /* launch geometry of the scan kernel               */
     int query_panel;     /* query rows per workgroup (B of the scan model)   */
     int db_splits;       /* how many workgroups share one query panel        */
-    int64_t nq, n;
+    int64_t nq, n;       /* the call's nq (also when duplicate queries were folded: see nq_distinct) and ntotal */
     int d, k;
     int64_t nq_distinct; /* query rows actually searched (== the call's nq unless duplicates were folded) */
 } lemon_search_info_t;

@@ -295,6 +295,7 @@ int lemon_search_internal(lemon_index_t *idx, const float *q_dev, int64_t nq, in
             rc = lemon_search_internal(idx, qrep, U, k, Dr, Ir, stream);
             idx->qdedup = saved;
             if (rc) return rc;
+            idx->last.nq = nq;                        // (the reduced search recorded U: nq is the call's, nq_distinct what it searched)
             idx->last.nq_distinct = U;
             return lemon_expand_results(Dr, Ir, grp, nq, k, D_dev, I_dev, stream);
         }

@@ -7,7 +7,8 @@ introduced the header; HIP calls stubbed out, the CU count an argument, the knob
 row per query chunk.  The same program and plan_chunk() agreed on all 109 396 rows of a much larger product of shapes and knobs
 when the header was written; the committed subset keeps every kernel, the 1 M x 1 M x 768 headline shape for both metrics,
 whole rounds with a ragged rest through QS4 and through QSW, LEMON_CHUNK_MB per kernel family, streaming at d % 4 != 0,
-n < 64, and LEMON_QS4=0 / LEMON_QS2=0."""
+n < 64, and LEMON_QS4=0 / LEMON_QS2=0.  The rows behind the table's last comment line (the shapes of tests/indexfx.py) were added
+later, from the header itself: they pin it down from then on, and tests/test_gpu_index_state.py holds the launches against them."""
 import os
 import shutil
 import subprocess
