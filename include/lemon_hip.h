@@ -500,6 +500,37 @@ int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, const float 
 int lemon_discrepancy(int method, lemon_index_t *idx_txt, const float *E_tr_dev, const float *qv_dev,
                       const float *q_txt_dev, int64_t nq, int k, int is_train, float *out_dev, void *stream);
 
+/* The database's own text neighbours for the dis_* scores, lib/baselines/discrepancy_baseline.py:165-169 (the cache the
+ * reference builds once per run; experiments.py:141-177 runs it once per grid point): the top-kc list of every row of idx_txt
+ * among the rows of idx_txt, self included, into Ic_dev, int64 [ntotal, kc], owned by the caller.  2 <= kc <= LEMON_MAX_K.
+ * Nothing is kept on the index: a cache belongs to the ntotal it was built at, and lemon_discrepancy_ks checks that count.
+ * May grow the index's neighbour workspace on first use (one stream synchronisation and a device allocation), as
+ * lemon_discrepancy does. */
+int lemon_discrepancy_cache(lemon_index_t *idx_txt, int kc, int64_t *Ic_dev, void *stream);
+
+/* lemon_discrepancy for every method and a list of knn_k in one call, lib/baselines/discrepancy_baseline.py:164-242 on the grid
+ * of experiments.py:141-177 (four methods x eight knn_k per dataset and seed).  out_dev is float32 [4][n_ks][nq] in the order
+ * dis_x, dis_y, div_x, div_y; out[m][t][i] has the bits lemon_discrepancy(method m, k = ks[t]) writes for query i, NaN
+ * included.  methods: bit 0 dis_x, bit 1 dis_y, bit 2 div_x, bit 3 div_y (at least one); a method that is not selected leaves
+ * its rows of out_dev untouched.  ks: HOST int32, strictly ascending, 1 <= ks[0], ks[n_ks-1] + 1 <= LEMON_MAX_K.
+ * E_img_tr_dev / E_txt_tr_dev [ntotal,d]: the DB embeddings (either may be NULL when no method reads it: x image, y text);
+ * q_img_dev may be NULL unless dis_x is selected.  Ic_dev [cache_rows, kc]: what lemon_discrepancy_cache wrote, kc >=
+ * ks[n_ks-1] + 1 (a wider cache serves: an exact list is a prefix of every deeper one); NULL is allowed when no dis_* bit is
+ * set.  cache_rows must equal the index's ntotal (a cache built before an add is refused), else LEMON_E_INVALID.
+ * One text search of the queries at ks[n_ks-1] + is_train; each query's pair distances are computed once at that depth and
+ * every k sums its prefix of them in lemon_discrepancy's order.  Row alignment and every other refusal as lemon_discrepancy
+ * (an empty index is refused as well); a refused call writes nothing.  nq < 2^31.  May grow the index's neighbour workspace on
+ * first use (one stream synchronisation and a device allocation), as lemon_discrepancy does.
+ * lemon_discrepancy_ks_host: the summation header compiled for the host (the 64 lanes looped) for ONE method (0 dis, 1 div) and
+ * one modality, on host pointers and on neighbour lists the caller brings instead of an index: E [n,d], qv [nq,d] (dis only),
+ * Im [nq, ks[n_ks-1] + is_train], Ic [n, kc] (dis only); out [n_ks][nq].  Row ids >= n are refused. */
+int lemon_discrepancy_ks(lemon_index_t *idx_txt, const float *E_img_tr_dev, const float *E_txt_tr_dev,
+                         const float *q_img_dev, const float *q_txt_dev, int64_t nq, const int32_t *ks, int n_ks,
+                         int is_train, int methods, const int64_t *Ic_dev, int64_t cache_rows, int kc, float *out_dev,
+                         void *stream);
+int lemon_discrepancy_ks_host(int method, const float *E, int64_t n, int d, const float *qv, const int64_t *Im, int64_t nq,
+                              const int64_t *Ic, int kc, const int32_t *ks, int n_ks, int is_train, float *out);
+
 /* lib/metrics/utils.py:47-82 calc_scores_given_hparams_vectorized (== loop twin :21-45):
  * score = d_1 + beta*mean_j[e^{-tau_1_n D_n} e^{-tau_2_n dists_tr_n} dists_n] + gamma*(same for m).
  * hp = {beta, gamma, tau_1_n, tau_2_n, tau_1_m, tau_2_m} (host doubles, passed by value in the

@@ -23,7 +23,7 @@ EXPORTS = [
     "lemon_linear_dump_tuned", "lemon_linear_set_tuning", "lemon_linear_stamp", "lemon_index_create", "lemon_index_free", "lemon_index_add",
     "lemon_index_ntotal", "lemon_index_dim", "lemon_index_data", "lemon_index_search",
     "lemon_index_set_algo", "lemon_index_set_wide_filter", "lemon_index_last_scan_kernel", "lemon_index_set_query_dedup", "lemon_index_last_search_info", "lemon_index_set_profiling",
-    "lemon_index_profile_read", "lemon_debug_scan_plan", "lemon_neighbors", "lemon_discrepancy", "lemon_score", "lemon_grid_f1",
+    "lemon_index_profile_read", "lemon_debug_scan_plan", "lemon_neighbors", "lemon_discrepancy", "lemon_discrepancy_cache", "lemon_discrepancy_ks", "lemon_discrepancy_ks_host", "lemon_score", "lemon_grid_f1",
     "lemon_grid_f1_ks", "lemon_grid_f1_ks_workspace_bytes",
     "lemon_kmeans_assign", "lemon_kmeans_update", "lemon_kmeans_split", "lemon_kmeans_train", "lemon_kmeans_workspace_bytes",
     "lemon_knn_label_disagreement", "lemon_jpeg_info", "lemon_jpeg_entropy", "lemon_jpeg_reconstruct_host", "lemon_jpeg_decode",
@@ -162,6 +162,9 @@ def load():
     lib.lemon_debug_scan_plan.argtypes = [c_int, c_int, ip, ip, ip, c_int, ip, ip, c_int, ip]
     lib.lemon_neighbors.argtypes = [vp, vp, vp, vp, vp, c_i64, c_int, c_int, vp, c_int, vp, vp] + [vp] * 9 + [vp]
     lib.lemon_discrepancy.argtypes = [c_int, vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp]
+    lib.lemon_discrepancy_cache.argtypes = [vp, c_int, vp, vp]
+    lib.lemon_discrepancy_ks.argtypes = [vp, vp, vp, vp, vp, c_i64, vp, c_int, c_int, c_int, vp, c_i64, c_int, vp, vp]
+    lib.lemon_discrepancy_ks_host.argtypes = [c_int, vp, c_i64, c_int, vp, vp, c_i64, vp, c_int, vp, c_int, c_int, vp]
     lib.lemon_score.argtypes = [vp] * 7 + [c_i64, c_int, ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp]
     lib.lemon_kmeans_assign.argtypes = [vp, c_i64, c_int, vp, c_int, vp, vp, vp]
     lib.lemon_kmeans_update.argtypes = [vp, c_i64, c_int, vp, vp, c_int, vp, vp, vp, vp, c_i64, vp]

@@ -32,6 +32,83 @@ def discrepancy_scores(db, q_img, q_txt, k, method, is_train=False):
     return out
 
 
+DISCREPANCY_METHODS = ("dis_x", "dis_y", "div_x", "div_y")       # the order of lemon_discrepancy_ks's method bits and output rows
+MAX_SWEEP_K = 63                                                 # max + 1 <= LEMON_MAX_K (the cache and the train split search k + 1)
+
+
+def _checked_ks(ks):
+    try:
+        ks = [int(k) for k in ks]
+    except (TypeError, ValueError):
+        raise ValueError(f"ks: {ks!r} is not a list of integers") from None
+    if not ks:
+        raise ValueError("ks: the list is empty")
+    if any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"ks: {ks} is not strictly ascending")
+    if ks[0] < 1 or ks[-1] > MAX_SWEEP_K:
+        raise ValueError(f"ks: every knn_k must lie in 1 .. {MAX_SWEEP_K}, got {ks}")
+    return ks
+
+
+def discrepancy_cache(db, kmax):
+    """The database's own text neighbours for the dis_* scores (discrepancy_baseline.py:165-169), once for every split and
+    every knn_k <= kmax: int64 CUDA [n, kmax + 1].  It belongs to the rows `db` holds now; discrepancy_sweep refuses it after
+    an add."""
+    kmax = int(kmax)
+    if not 1 <= kmax <= MAX_SWEEP_K:
+        raise ValueError(f"kmax must lie in 1 .. {MAX_SWEEP_K}, got {kmax}")
+    assert db.metric == _lib.METRIC_IP, "discrepancy baselines are defined on the cosine (IP) indices"
+    cache = torch.empty((db.index_txt.ntotal, kmax + 1), dtype=torch.int64, device=db.device)
+    with torch.cuda.device(db.device):
+        _lib.check(_lib.load().lemon_discrepancy_cache(db.index_txt._h, kmax + 1, ptr(cache), stream_ptr(db.device)),
+                   "lemon_discrepancy_cache")
+    return cache
+
+
+def discrepancy_sweep(db, q_img, q_txt, ks, methods=DISCREPANCY_METHODS, is_train=False, cache=None):
+    """discrepancy_scores for every method of `methods` and every knn_k of `ks` (strictly ascending, 1 .. 63) from one text
+    search and one pass over each query's neighbour pairs: float32 CUDA [len(methods), len(ks), nq], in the orders given, every
+    element with the bits of discrepancy_scores(db, q_img, q_txt, k, method, is_train).
+    cache: discrepancy_cache(db, kmax) with kmax >= max(ks), shared by the splits of a run; None builds it here when a dis_*
+    method is asked for."""
+    ks = _checked_ks(ks)
+    methods = list(methods)
+    if not methods:
+        raise ValueError("methods: the list is empty")
+    for m in methods:
+        if m not in DISCREPANCY_METHODS:
+            raise ValueError(f"methods: {m!r} is not one of {DISCREPANCY_METHODS}")
+    assert db.metric == _lib.METRIC_IP, "discrepancy baselines are defined on the cosine (IP) indices"
+    q_img, q_txt = dev_f32(q_img, "q_img"), dev_f32(q_txt, "q_txt")
+    nq, n = q_txt.shape[0], db.index_txt.ntotal
+    if db.img.shape[0] != n or db.txt.shape[0] != n or q_img.shape[0] != nq:
+        raise ValueError(f"the text index holds {n} rows, the database embeddings {db.img.shape[0]} / {db.txt.shape[0]}; "
+                         f"{q_img.shape[0]} image and {nq} text queries")
+    bits = 0
+    for m in methods:
+        bits |= 1 << DISCREPANCY_METHODS.index(m)
+    kc = 0
+    if bits & 3:
+        if cache is None:
+            cache = discrepancy_cache(db, ks[-1])
+        if not (torch.is_tensor(cache) and cache.is_cuda and cache.dtype == torch.int64 and cache.dim() == 2 and cache.is_contiguous()):
+            raise ValueError("cache: expected the contiguous int64 CUDA tensor discrepancy_cache returns")
+        if cache.shape[0] != n:
+            raise ValueError(f"cache: built for {cache.shape[0]} database rows, the database holds {n}")
+        if cache.shape[1] < ks[-1] + 1:
+            raise ValueError(f"cache: {cache.shape[1]} columns, max(ks) + 1 = {ks[-1] + 1} are needed")
+        kc = cache.shape[1]
+    else:
+        cache = None
+    out = torch.empty((4, len(ks), nq), dtype=torch.float32, device=db.device)     # rows of methods not asked for stay unwritten
+    ks_c = (ctypes.c_int32 * len(ks))(*ks)
+    with torch.cuda.device(db.device):
+        _lib.check(_lib.load().lemon_discrepancy_ks(db.index_txt._h, ptr(db.img), ptr(db.txt), ptr(q_img), ptr(q_txt), nq, ks_c,
+                                                    len(ks), int(bool(is_train)), bits, ptr(cache), 0 if cache is None else cache.shape[0],
+                                                    kc, ptr(out), stream_ptr(db.device)), "lemon_discrepancy_ks")
+    return out[[DISCREPANCY_METHODS.index(m) for m in methods]]
+
+
 def clip_similarity(first_modality_embeddings, second_modality_embeddings, dist="cosine"):
     """CLIP-similarity baseline score = paired distance of (un-normalised) image and text embeddings."""
     return our_metric(first_modality_embeddings, second_modality_embeddings, dist)

@@ -35,6 +35,11 @@ void lemon_set_error(const char *fmt, ...);
         }                                                                                  \
     } while (0)
 
+// Caller-owned embedding / query rows: with d % 4 == 0 some kernels behind the search read them 16 bytes at a time on the
+// strength of d alone (exact_score and the staged k_bf16_final in knn_bf16.hip), so such rows must start on a 16-byte
+// boundary.  With d % 4 != 0 every kernel walks rows one float at a time and any float pointer will do.
+static inline bool rows_vector_safe(const float *p, int d) { return (d & 3) != 0 || (((uintptr_t)p) & 15) == 0; }
+
 // ---- index object ---------------------------------------------------------------
 // Data layout in HBM (DESIGN.md "Data layout"):
 //   x     [cap, d]        row-major copy of what the caller added (gathers, exact re-rank)
