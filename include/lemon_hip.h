@@ -490,6 +490,47 @@ int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, const float 
                     int64_t *I_n_dev, float *D_m_dev, float *dists_m_dev, float *dists_tr_m_dev,
                     int64_t *I_m_dev, void *stream);
 
+/* ---- metric sweep: the euclidean lists of the reference's grid from the cosine scan (experiments.py crosses dist_type with
+ * everything; DESIGN.md section 4, "Metric sweep") ------------------------------------------------------------------------
+ *
+ * lemon_index_l2_from_ip: the k list IndexFlatL2.search would return for the rows of q_dev over the rows of `idx`, an
+ * IndexFlatIP, derived from that index's own search output D_ip_dev / I_ip_dev [nq, kd] (kd >= k, best first, padding I = -1
+ * at the end) without another scan: D = max(0, fmaf(-2, s, dot(q,q) + dot(x,x))), the numeric contract's own expression on
+ * the list's scores, the stored row norms and one chain per query; the first k by (D ascending, id ascending) go to
+ * D_l2_dev / I_l2_dev [nq, k] (slots beyond the DB: I = -1, D = +FLT_MAX).  cert_dev, uint8 [nq]: 1 where the row is PROVEN
+ * to equal the L2 search bit for bit -- the list holds the whole DB, or D of slot k-1 is strictly below the bound
+ * max(0, fmaf(-2, s_{kd-1}, dot(q,q) + min_x dot(x,x))) that no row outside the list can undercut (fp32 add, fmaf and max
+ * are monotone: csrc/l2_from_ip_core.hpp); 0 where it is not, where dot(q,q), a listed score or any stored norm is not finite,
+ * or where an id is not a row of the index.  A row with cert 0 is still written but must be searched with an IndexFlatL2.
+ * Refused with LEMON_E_INVALID, nothing written: a null pointer, an index that is not IP, k < 1, k > kd, kd > LEMON_MAX_K,
+ * q_dev not 16-byte aligned when d % 4 == 0.  The smallest stored norm is reduced on the device once per index content
+ * (the first call after an add) and kept; dot(q,q) lives in the index's neighbour workspace, which the first larger call
+ * grows (one stream synchronisation and a device allocation) and later calls only reuse.
+ * lemon_l2_from_ip_host: the same header with the lanes looped, on host pointers, for the tests: qq [nq], xx [n] and xx_min
+ * are brought by the caller (xx_min: NaN when any norm is not finite). */
+int lemon_index_l2_from_ip(lemon_index_t *idx, const float *q_dev, int64_t nq, const float *D_ip_dev, const int64_t *I_ip_dev,
+                           int kd, int k, float *D_l2_dev, int64_t *I_l2_dev, uint8_t *cert_dev, void *stream);
+int lemon_l2_from_ip_host(const float *qq, const float *xx, int64_t n, float xx_min, const float *D_ip, const int64_t *I_ip,
+                          int64_t nq, int kd, int k, float *D_l2, int64_t *I_l2, uint8_t *cert);
+
+/* lemon_neighbors for both metrics from one search a side.  idx_img / idx_txt: IndexFlatIP over the normalised DB rows;
+ * dists_tr_ip_dev / dists_tr_l2_dev [ntotal]: run_lemon.py:169 and :173.  Each side is searched once at
+ * kd = min(LEMON_MAX_K, k + drop_self + margin), margin >= 0.  The first set of outputs is what lemon_neighbors writes for an
+ * IP pair (an exact list is a prefix of every deeper one); the second set (*_l2_dev) is what it writes for an L2 pair WHERE
+ * cert_n_dev[i] and cert_m_dev[i] (uint8 [nq], the certificate of lemon_index_l2_from_ip at depth k + drop_self on the image
+ * and the text side) are both 1: record row i of the second set reads the derived lists, and a side whose certificate is 0
+ * may differ from the L2 search, so such rows must be replaced by lemon_neighbors on an IndexFlatL2 pair.  Every other
+ * argument, limit and refusal as lemon_neighbors; I_* may be NULL; de-duplication on the text side only. */
+int lemon_neighbors_metrics(lemon_index_t *idx_img, lemon_index_t *idx_txt, const float *dists_tr_ip_dev,
+                            const float *dists_tr_l2_dev, const float *q_img_dev, const float *q_txt_dev, int64_t nq, int k,
+                            int drop_self, const uint8_t *in_db_dev, int discrete, const int32_t *tr_label_id_dev,
+                            const int32_t *q_label_id_dev, int margin,
+                            float *d1_dev, float *D_n_dev, float *dists_n_dev, float *dists_tr_n_dev, int64_t *I_n_dev,
+                            float *D_m_dev, float *dists_m_dev, float *dists_tr_m_dev, int64_t *I_m_dev,
+                            float *d1_l2_dev, float *D_n_l2_dev, float *dists_n_l2_dev, float *dists_tr_n_l2_dev,
+                            int64_t *I_n_l2_dev, float *D_m_l2_dev, float *dists_m_l2_dev, float *dists_tr_m_l2_dev,
+                            int64_t *I_m_l2_dev, uint8_t *cert_n_dev, uint8_t *cert_m_dev, void *stream);
+
 /* Discrepancy baselines, lib/baselines/discrepancy_baseline.py:164-242 (next-row scope).
  * method 0 = dis_x / dis_y: mean cosine distance between the query's embedding qv_dev [nq,d] and the
  * second-order neighbours (through the DB's own text kNN cache of k+1, self removed by index, :165-169)

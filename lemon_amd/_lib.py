@@ -25,6 +25,7 @@ EXPORTS = [
     "lemon_index_set_algo", "lemon_index_set_wide_filter", "lemon_index_last_scan_kernel", "lemon_index_set_query_dedup", "lemon_index_last_search_info", "lemon_index_set_profiling",
     "lemon_index_profile_read", "lemon_debug_scan_plan", "lemon_neighbors", "lemon_discrepancy", "lemon_discrepancy_cache", "lemon_discrepancy_ks", "lemon_discrepancy_ks_host", "lemon_score", "lemon_grid_f1",
     "lemon_grid_f1_ks", "lemon_grid_f1_ks_workspace_bytes",
+    "lemon_index_l2_from_ip", "lemon_l2_from_ip_host", "lemon_neighbors_metrics",
     "lemon_kmeans_assign", "lemon_kmeans_update", "lemon_kmeans_split", "lemon_kmeans_train", "lemon_kmeans_workspace_bytes",
     "lemon_knn_label_disagreement", "lemon_jpeg_info", "lemon_jpeg_entropy", "lemon_jpeg_reconstruct_host", "lemon_jpeg_decode",
     "lemon_jpeg_pack", "lemon_jpeg_entropy_device", "lemon_jpeg_entropy_workspace_bytes", "lemon_jpeg_entropy_par_host",
@@ -161,6 +162,9 @@ def load():
     ip = ctypes.POINTER(c_int)
     lib.lemon_debug_scan_plan.argtypes = [c_int, c_int, ip, ip, ip, c_int, ip, ip, c_int, ip]
     lib.lemon_neighbors.argtypes = [vp, vp, vp, vp, vp, c_i64, c_int, c_int, vp, c_int, vp, vp] + [vp] * 9 + [vp]
+    lib.lemon_index_l2_from_ip.argtypes = [vp, vp, c_i64, vp, vp, c_int, c_int, vp, vp, vp, vp]
+    lib.lemon_l2_from_ip_host.argtypes = [vp, vp, c_i64, ctypes.c_float, vp, vp, c_i64, c_int, c_int, vp, vp, vp]
+    lib.lemon_neighbors_metrics.argtypes = [vp] * 6 + [c_i64, c_int, c_int, vp, c_int, vp, vp, c_int] + [vp] * 18 + [vp, vp, vp]
     lib.lemon_discrepancy.argtypes = [c_int, vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp]
     lib.lemon_discrepancy_cache.argtypes = [vp, c_int, vp, vp]
     lib.lemon_discrepancy_ks.argtypes = [vp, vp, vp, vp, vp, c_i64, vp, c_int, c_int, c_int, vp, c_i64, c_int, vp, vp]

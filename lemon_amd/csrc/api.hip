@@ -61,7 +61,7 @@ extern "C" int lemon_index_create(int metric, int d, lemon_index_t **out) {
 
 extern "C" int lemon_index_free(lemon_index_t *idx) {
     if (!idx) return LEMON_OK;
-    void *ptrs[] = {idx->x, idx->xp, idx->xnorm, idx->xh, idx->xh_stats, idx->xn2max_dev, idx->ws_qp, idx->ws_qnorm,
+    void *ptrs[] = {idx->x, idx->xp, idx->xnorm, idx->xh, idx->xh_stats, idx->xn2max_dev, idx->xnrange_dev, idx->ws_qp, idx->ws_qnorm,
                     idx->ws_cand, idx->ws_part, idx->ws_state, idx->ws_D, idx->ws_I, idx->ws_dd, idx->ws_ddq,
                     idx->plan_slots[0].dev, idx->plan_slots[1].dev, idx->plan_slots[2].dev, idx->plan_slots[3].dev};
     for (void *p : ptrs)
@@ -313,18 +313,6 @@ extern "C" int lemon_index_search(lemon_index_t *idx, const float *q_dev, int64_
 // ---- K4: neighbour finalisation ----------------------------------------------------------
 // One thread per (query, slot): self-exclusion offset, sign convention, cross-modal distance by
 // the chain contract on gathered rows, dists_tr gather.  run_lemon.py:256-289,303,306.
-struct NbParams {
-    const float *img_tr, *txt_tr, *dists_tr, *q_img, *q_txt;
-    const float *Dn, *Dm;       // [nq, ks] raw search output
-    const int64_t *In, *Im;
-    const uint8_t *in_db;
-    const int32_t *tr_lab, *q_lab;
-    float *D_n, *dists_n, *dists_tr_n, *D_m, *dists_m, *dists_tr_m;
-    int64_t *I_n, *I_m;
-    int64_t nq;
-    int d, k, ks, metric, drop_self, discrete;
-};
-
 // STAGED: wave-cooperative row fetches (d % 4 == 0); otherwise every lane walks its rows from global.
 template <bool L2, bool STAGED>
 __global__ __launch_bounds__(128) void k_neighbors_finalize(NbParams p) {
@@ -373,6 +361,23 @@ __global__ __launch_bounds__(128) void k_neighbors_finalize(NbParams p) {
         p.dists_m[t] = dist_m;
         p.dists_tr_m[t] = p.dists_tr[jm];
     }
+}
+
+int lemon_neighbors_finalize(const NbParams &p, hipStream_t stream) {
+    const int64_t total = p.nq * p.k;
+    const bool staged = (p.d & 3) == 0 &&
+                        ((((uintptr_t)p.img_tr) | ((uintptr_t)p.txt_tr) | ((uintptr_t)p.q_img) | ((uintptr_t)p.q_txt)) & 15) == 0;
+    const dim3 grid((unsigned)((total + 127) / 128)), block(128);
+    const bool l2m = p.metric == LEMON_METRIC_L2;
+    if (staged) {
+        if (l2m) hipLaunchKernelGGL((k_neighbors_finalize<true, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((k_neighbors_finalize<false, true>), grid, block, 0, stream, p);
+    } else {
+        if (l2m) hipLaunchKernelGGL((k_neighbors_finalize<true, false>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((k_neighbors_finalize<false, false>), grid, block, 0, stream, p);
+    }
+    LEMON_HIP_CHECK(hipGetLastError());
+    return LEMON_OK;
 }
 
 extern "C" int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, const float *dists_tr_dev,
@@ -434,22 +439,7 @@ extern "C" int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, c
     p.I_n = I_n_dev; p.I_m = I_m_dev;
     p.nq = nq; p.d = idx_img->d; p.k = k; p.ks = ks; p.metric = idx_img->metric;
     p.drop_self = drop_self; p.discrete = discrete;
-    const int64_t total = nq * k;
-    {
-        const bool staged = (p.d & 3) == 0 &&
-                            ((((uintptr_t)p.img_tr) | ((uintptr_t)p.txt_tr) | ((uintptr_t)p.q_img) | ((uintptr_t)p.q_txt)) & 15) == 0;
-        const dim3 grid((unsigned)((total + 127) / 128)), block(128);
-        const bool l2m = p.metric == LEMON_METRIC_L2;
-        if (staged) {
-            if (l2m) hipLaunchKernelGGL((k_neighbors_finalize<true, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_neighbors_finalize<false, true>), grid, block, 0, stream, p);
-        } else {
-            if (l2m) hipLaunchKernelGGL((k_neighbors_finalize<true, false>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_neighbors_finalize<false, false>), grid, block, 0, stream, p);
-        }
-    }
-    LEMON_HIP_CHECK(hipGetLastError());
-    return LEMON_OK;
+    return lemon_neighbors_finalize(p, stream);
 }
 
 // ---- discrepancy baselines (lib/baselines/discrepancy_baseline.py:164-242) ------------------

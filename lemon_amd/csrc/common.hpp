@@ -60,6 +60,8 @@ struct lemon_index {
     float *xh_stats;      // [2, cap]: measured ||x-xh||^2 and ||xh||^2 per row
     int64_t xh_rows;      // rows of xh that are up to date
     unsigned *xn2max_dev; // device scalars (float bits): max dot(x,x), max ||x-xh||^2, max ||xh||^2
+    unsigned *xnrange_dev; // device scalars (float bits): min and max of xnorm[0 .. n) for the metric sweep (metric_sweep.hip)
+    int64_t xnrange_rows; // 1 + the n xnrange_dev was reduced at (0: never), so every add makes it stale
     // search workspace (grown on demand)
     int64_t ws_q;         // query rows the workspace is sized for
     int64_t ws_qp_row_bytes;  // bytes per staged query row the workspace is sized for
@@ -157,6 +159,19 @@ __host__ __device__ inline u32 lemon_key_index(u64 key) { return 0xffffffffu - (
 int lemon_search_internal(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
                           float *D_dev, int64_t *I_dev, hipStream_t stream);
 int lemon_rowdot_chain(const float *a, const float *b, int64_t n, int d, float *out, hipStream_t s);
+// K4, the neighbour finalisation of lemon_neighbors (api.hip), shared with lemon_neighbors_metrics (metric_sweep.hip)
+struct NbParams {
+    const float *img_tr, *txt_tr, *dists_tr, *q_img, *q_txt;
+    const float *Dn, *Dm;       // [nq, ks] raw search output (ks: the pitch of a row; k + off <= ks columns are read)
+    const int64_t *In, *Im;
+    const uint8_t *in_db;
+    const int32_t *tr_lab, *q_lab;
+    float *D_n, *dists_n, *dists_tr_n, *D_m, *dists_m, *dists_tr_m;
+    int64_t *I_n, *I_m;
+    int64_t nq;
+    int d, k, ks, metric, drop_self, discrete;
+};
+int lemon_neighbors_finalize(const NbParams &p, hipStream_t stream);
 int lemon_dedup_queries(lemon_index_t *idx, const float *q_dev, int64_t nq, hipStream_t stream, int64_t *U_host,
                         const int **rep_dev, const int **group_dev);
 int lemon_gather_query_rows(const float *q_dev, const int *rep_dev, int64_t U, int d, float *out_dev, hipStream_t stream);

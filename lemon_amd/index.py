@@ -133,6 +133,34 @@ class _IndexFlat:
 class IndexFlatIP(_IndexFlat):
     metric = _lib.METRIC_IP
 
+    def derive_l2(self, x, D, I, k):
+        """The `k` list `IndexFlatL2.search(x, k)` returns over the same rows, derived from this index's own search output
+        `D, I = self.search(x, kd)` with kd >= k (kd <= 64) and no further scan: returns (D, I, certified).  `certified` is
+        a bool [nq]: True where the derived row is proven to equal the L2 search bit for bit; a row that is not certified must
+        be searched with an IndexFlatL2 (include/lemon_hip.h, lemon_index_l2_from_ip).  numpy in -> numpy out."""
+        k = int(k)
+        t, was_numpy = self._to_dev(x, "derive_l2(x)")
+        nq = t.shape[0]
+        to = lambda a, dt: (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a).to(
+            device=self.device, dtype=dt).contiguous()
+        Dip, Iip = to(D, torch.float32), to(I, torch.int64)
+        if Dip.dim() != 2 or Dip.shape != Iip.shape or Dip.shape[0] != nq:
+            raise ValueError(f"derive_l2: D and I must both be [{nq}, kd], got {tuple(Dip.shape)} and {tuple(Iip.shape)}")
+        kd = Dip.shape[1]
+        if not 1 <= k <= kd <= _lib.MAX_K:
+            raise ValueError(f"derive_l2: 1 <= k <= kd <= {_lib.MAX_K} required, got k = {k}, kd = {kd}")
+        Dl = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        Il = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        cert = torch.zeros((nq,), dtype=torch.uint8, device=self.device)
+        if nq:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.lemon_index_l2_from_ip(self._h, ptr(t), nq, ptr(Dip), ptr(Iip), kd, k, ptr(Dl), ptr(Il),
+                                                            ptr(cert), stream_ptr(self.device)), "lemon_index_l2_from_ip")
+        cert = cert.bool()
+        if was_numpy:
+            return Dl.cpu().numpy(), Il.cpu().numpy(), cert.cpu().numpy()
+        return Dl, Il, cert
+
 
 class IndexFlatL2(_IndexFlat):
     metric = _lib.METRIC_L2

@@ -331,7 +331,7 @@ class Embedder:
         return e
 
 
-def score_splits(db, splits, k, hparams=None, discrete=False):
+def score_splits(db, splits, k, hparams=None, discrete=False, margin=4):
     """splits: list of dicts {name, img, txt, drop_self, in_db, label_id}.  Returns per split the
     record of device arrays (+ 'score' float64 when hparams is given).
 
@@ -341,7 +341,13 @@ def score_splits(db, splits, k, hparams=None, discrete=False):
     second case is exactly "keep the first k of k+1", so val/test ride along with in_db = 0.
 
     k may be a list of ks: the same single call runs at max(ks) and the return value is {k: records}, the records of each k
-    being the prefix of the deep record (neighbors.prefix_record), scored with its own k when hparams is given."""
+    being the prefix of the deep record (neighbors.prefix_record), scored with its own k when hparams is given.
+
+    A metric-sweep DB, LemonDB(..., dist_type=("cosine", "euclidean")), returns {metric: what a DB of that dist_type returns}
+    from ONE neighbors_metrics call (`margin` extra neighbours certify the euclidean lists, DESIGN.md section 4 "Metric
+    sweep"); the call's counts per split are left in db.last_sweep_counts."""
+    if getattr(db, "metrics", None):
+        return _score_splits_metrics(db, splits, k, hparams, discrete, margin)
     if not isinstance(k, numbers.Integral):
         from .neighbors import prefix_record
         ks = sorted({int(v) for v in k})
@@ -393,13 +399,45 @@ def score_splits(db, splits, k, hparams=None, discrete=False):
     return out
 
 
+class _OneMetric:
+    """The view of a metric-sweep DB that score_splits' single-metric body sees: `neighbors` hands out one metric's record of
+    a neighbors_metrics call made once for both."""
+
+    def __init__(self, db, margin):
+        self.db, self.margin, self.recs, self.counts, self.metric_name = db, margin, None, None, None
+        self.index_img = db.index_img
+
+    def neighbors(self, img, txt, k, **kw):
+        if self.recs is None:
+            self.recs, self.counts = self.db.neighbors_metrics(img, txt, k, margin=self.margin, **kw)
+        return self.recs[self.metric_name]
+
+
+def _score_splits_metrics(db, splits, k, hparams, discrete, margin):
+    view = _OneMetric(db, margin)
+    out = {}
+    for m in db.metrics:
+        view.metric_name = m
+        out[m] = score_splits(view, splits, k, hparams, discrete)
+    counts, lo = {}, 0
+    if view.counts is not None:
+        for s in (s for s in splits if s["img"].shape[0] > 0):
+            n = s["img"].shape[0]
+            cn, cm = view.counts["cert_n"][lo:lo + n], view.counts["cert_m"][lo:lo + n]
+            counts[s["name"]] = {"rows": n, "certified_n": int(cn.sum()), "certified_m": int(cm.sum()), "fallback": int((~(cn & cm)).sum())}
+            lo += n
+    db.last_sweep_counts = counts
+    return out
+
+
 def run_hot_path(embedder, data, k=5, dist_type="cosine", hparams=FIXED_HPARAMS, discrete=False,
                  world_size=1, rank=0, algo=None, timers=None, profile_index=False, gather_log=None):
     """One pass of the hot path over `data` = {split: {"pixels": float [n,3,S,S] or raw uint8 [n,H,W,3], "ids": [n,L], "label_id": [n]}}
     for split in train/val/test, this rank's shard of each.  DB = all ranks' train shards in global
     order.  The train split is embedded ONCE and reused as DB and as queries (the reference embeds it
     twice, run_lemon.py:137-161 and :198-233; same model, same inputs => same embeddings).  k: an int, or a list of ks
-    (score_splits: one neighbour call at max(ks); returns ({k: records}, db))."""
+    (score_splits: one neighbour call at max(ks); returns ({k: records}, db)).  dist_type: a name, or ("cosine", "euclidean")
+    for both from one search (score_splits on a metric-sweep DB; returns ({metric: ...}, db))."""
     dev = embedder.device
     t0 = time.perf_counter()
     emb = {}
@@ -434,7 +472,10 @@ def run_hot_path(embedder, data, k=5, dist_type="cosine", hparams=FIXED_HPARAMS,
     if timers is not None:
         torch.cuda.synchronize(dev)
         timers["knn_score_s"] = time.perf_counter() - t0
-    for per_k in ([recs] if isinstance(k, numbers.Integral) else recs.values()):
+    groups = list(recs.values()) if getattr(db, "metrics", None) else [recs]       # a metric sweep: {metric: ...} outermost
+    if not isinstance(k, numbers.Integral):
+        groups = [per_k for g in groups for per_k in g.values()]
+    for per_k in groups:
         for name in per_k:                  # keep the embeddings the scores were computed from
             per_k[name]["emb_img"], per_k[name]["emb_txt"] = emb[name]
     return recs, db

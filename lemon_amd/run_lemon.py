@@ -9,9 +9,14 @@ per-sample record schema (:291-307).  Differences, all explicit:
     --encoder_batch); `--clip_path random[:arch]` / `--data_root synthetic:N` run without any files;
   * under torchrun (WORLD_SIZE>1) samples are sharded over ranks, DB shards all-gathered over RCCL;
   * extension flag --knn_k_sweep 1,2,5,...: the validation protocol's choice of knn_k in ONE run -- embed, DB build and search
-    once at the largest k, then the tail of a run per k on the prefix of the record (<output_dir>/knn_k=<k>/, k_selection.json).
+    once at the largest k, then the tail of a run per k on the prefix of the record (<output_dir>/knn_k=<k>/, k_selection.json);
+  * extension flag --dist_type_sweep cosine,euclidean: both metrics of the reference's grid in ONE run -- embed once, one pair
+    of IP indices, one search per modality and split; the euclidean lists are derived from the cosine lists and certified row
+    by row, the rest searched again (<output_dir>/dist_type=<m>/, dist_sweep.json).  Composes with --knn_k_sweep.
 """
 import argparse
+import copy
+import json
 import os
 import pickle
 import sys
@@ -74,7 +79,34 @@ def build_parser():
                    help="comma-separated knn_k values, e.g. 1,2,5,10,15,20,30,50 (the reference's grid, experiments.py:86): embed, build "
                         "the DB and search ONCE at the largest, then run the tail of a --knn_k run for every value on the prefix "
                         "of the record -> <output_dir>/knn_k=<k>/ and <output_dir>/k_selection.json; --knn_k is ignored")
+    p.add_argument("--dist_type_sweep", default=None, type=str,
+                   help="comma-separated dist_type values, cosine,euclidean (experiments.py crosses the two with every other axis): "
+                        "embed, build ONE pair of IP indices and search once per modality and split; the euclidean neighbour lists "
+                        "are derived from the cosine lists searched --dist_sweep_margin deeper and certified row by row, rows that "
+                        "cannot be certified are searched again on an L2 pair; then the tail of a --dist_type run per metric -> "
+                        "<output_dir>/dist_type=<m>/ and <output_dir>/dist_sweep.json; --dist_type is ignored")
+    p.add_argument("--dist_sweep_margin", default=4, type=int,
+                   help="extra neighbours the cosine search of --dist_type_sweep keeps to certify the euclidean lists (the search "
+                        "depth stays within LEMON_MAX_K = 64)")
     return p
+
+
+DIST_TYPES = ("cosine", "euclidean")
+
+
+def parse_dist_sweep(text):
+    """'euclidean,cosine,cosine' -> ['euclidean', 'cosine']: de-duplicated, order kept.  Refused (ValueError): an empty list, a
+    name that is not a dist_type."""
+    parts = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not parts:
+        raise ValueError("--dist_type_sweep: the list is empty; expected comma-separated values of dist_type such as cosine,euclidean")
+    out = []
+    for t in parts:
+        if t not in DIST_TYPES:
+            raise ValueError(f"--dist_type_sweep: {t!r} is not a dist_type (cosine|euclidean)")
+        if t not in out:
+            out.append(t)
+    return out
 
 
 MAX_SWEEP_K = 63       # max + 1 <= LEMON_MAX_K: the train split searches k + 1 (include/lemon_hip.h)
@@ -119,6 +151,13 @@ def main(argv=None):
             parse_k_sweep(args.knn_k_sweep)
         except ValueError as e:
             parser.error(str(e))
+    if args.dist_type_sweep is not None:
+        try:
+            parse_dist_sweep(args.dist_type_sweep)
+        except ValueError as e:
+            parser.error(str(e))
+        if args.dist_sweep_margin < 0:
+            parser.error("--dist_sweep_margin: must be >= 0")
     return run_with_tee(_run, args)
 
 
@@ -147,7 +186,10 @@ def _run(args):
         torch.from_numpy(tr_prompt_ids).to(device)
     sel = torch.from_numpy(np.asarray(train_indices_in_compr)).to(device)
     algo = {"auto": None, "f32": _lib.ALGO_F32_MFMA, "bf16": _lib.ALGO_BF16_FILTER}[args.algo]
-    db = LemonDB(full_img[sel], full_txt[sel], args.dist_type, tr_label_id=full_pid[sel], algo=algo)
+    metrics = parse_dist_sweep(args.dist_type_sweep) if getattr(args, "dist_type_sweep", None) is not None else None
+    dist_names = metrics or [args.dist_type]
+    both = len(dist_names) == 2             # one IP pair serves both metrics (LemonDB.neighbors_metrics)
+    db = LemonDB(full_img[sel], full_txt[sel], tuple(dist_names) if both else dist_names[0], tr_label_id=full_pid[sel], algo=algo)
 
     cls_txt = None
     if is_clf:   # class-prompt embeddings, only used by --normalize_d1 (:180-190)
@@ -158,42 +200,70 @@ def _run(args):
     names = ["val", "test"] if (args.debug or args.skip_train) else ["train", "val", "test"]
     sweep = parse_k_sweep(args.knn_k_sweep) if getattr(args, "knn_k_sweep", None) is not None else None
     k = sweep[-1] if sweep else args.knn_k        # a sweep searches once, at its largest k
-    frames = []
+    frames = {m: [] for m in dist_names}
+    sweep_counts = {}
     for sname in names:
         if sname not in emb:
             emb[sname] = embed_split(sets[sname], sname)
         e_img, e_txt, meta = emb[sname]
         nq, lo = e_img.shape[0], meta["lo"]
-        rec = db.neighbors(e_img, e_txt, k, drop_self=(sname == "train"),
-                           in_db=in_db_mask[lo:lo + nq] if sname == "train" else None,
-                           discrete=args.use_discrete_for_text, q_label_id=ids_of(meta),
-                           return_indices=False)
-        if args.normalize_d1:
-            assert is_clf
-            rec["d_1"] = ops.d1_normalized(args.dist_type, e_img, cls_txt,
-                                           torch.from_numpy(np.asarray(meta["noisy"], dtype=np.int32)))
+        kw = dict(drop_self=(sname == "train"), in_db=in_db_mask[lo:lo + nq] if sname == "train" else None,
+                  discrete=args.use_discrete_for_text, q_label_id=ids_of(meta), return_indices=False)
         n_total = len(sets[sname])
-        host = {key: all_gather_rows(v, n_total).cpu().numpy() for key, v in rec.items()}
+        if both:
+            recs, counts = db.neighbors_metrics(e_img, e_txt, k, margin=args.dist_sweep_margin, **kw)
+            flags = torch.stack([counts["cert_n"], counts["cert_m"]], dim=1).to(torch.uint8)
+            flags = all_gather_rows(flags, n_total).cpu().numpy().astype(bool)       # [n_total, 2]: every rank's shard
+            sweep_counts[sname] = {"rows": int(n_total), "certified_n": int(flags[:, 0].sum()), "certified_m": int(flags[:, 1].sum()),
+                                   "fallback": int((~(flags[:, 0] & flags[:, 1])).sum())}
+        else:
+            recs = {dist_names[0]: db.neighbors(e_img, e_txt, k, **kw)}
+            sweep_counts[sname] = {"rows": int(n_total), "certified_n": None, "certified_m": None, "fallback": None}
+        noisy_shard = None
+        if args.normalize_d1:                     # this rank's rows, before the metadata of all ranks replaces them
+            assert is_clf
+            noisy_shard = torch.from_numpy(np.asarray(meta["noisy"], dtype=np.int32))
         meta, flips = ctx.gather_meta(meta)       # metadata to every rank (small python objects)
-        if rank == 0:
-            frames.append(pd.DataFrame({
-                **meta_columns(sname, n_total, meta, flips),
-                "d_1": host["d_1"].astype(np.float64),
-                **{c: list(host[c]) for c in ("dists_n", "D_n", "dists_tr_n", "dists_m", "D_m", "dists_tr_m")},
-            }))
+        for m in dist_names:
+            rec = recs[m]
+            if args.normalize_d1:
+                rec["d_1"] = ops.d1_normalized(m, e_img, cls_txt, noisy_shard)
+            host = {key: all_gather_rows(v, n_total).cpu().numpy() for key, v in rec.items()}
+            if rank == 0:
+                frames[m].append(pd.DataFrame({
+                    **meta_columns(sname, n_total, meta, flips),
+                    "d_1": host["d_1"].astype(np.float64),
+                    **{c: list(host[c]) for c in ("dists_n", "D_n", "dists_tr_n", "dists_m", "D_m", "dists_tr_m")},
+                }))
     torch.cuda.synchronize(device)
     timedelta = (datetime.now() - start_t).total_seconds()
     if rank != 0:
         if world > 1:
             torch.distributed.destroy_process_group()
         return 0
-    df = pd.concat(frames, ignore_index=True)
-    n_samples = len(df)
+    n_samples = sum(len(f) for f in frames[dist_names[0]])
     print(f"Finished {n_samples} samples in {timedelta} seconds; avg of {timedelta / n_samples}s per sample")
-    if sweep:
-        _sweep_tail(args, df, out_dir, device, sweep)
-    else:
-        _tail(args, df, out_dir, device)
+    for m in dist_names:
+        df = pd.concat(frames[m], ignore_index=True)
+        args_m, out_m = args, out_dir
+        if metrics is not None:             # the tail of a --dist_type m run, under its own directory
+            out_m = out_dir / f"dist_type={m}"
+            out_m.mkdir(exist_ok=True, parents=True)
+            args_m = copy.copy(args)
+            args_m.dist_type, args_m.output_dir = m, str(out_m)
+            with open(out_m / "args.json", "w") as f:
+                json.dump(vars(args_m), f, default=str)
+            print(f"==== dist_type = {m} ====")
+        if sweep:
+            _sweep_tail(args_m, df, out_m, device, sweep)
+        else:
+            _tail(args_m, df, out_m, device)
+    if metrics is not None:
+        with open(out_dir / "dist_sweep.json", "w") as f:
+            json.dump({"metrics": list(dist_names), "margin": int(args.dist_sweep_margin) if both else None, "knn_k": int(k),
+                       "splits": sweep_counts}, f, indent=1)
+        with open(os.path.join(out_dir, "done"), "w") as f:
+            f.write("done")
     if world > 1:
         torch.distributed.destroy_process_group()
     return 0
