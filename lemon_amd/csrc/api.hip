@@ -61,11 +61,9 @@ extern "C" int lemon_index_create(int metric, int d, lemon_index_t **out) {
 
 extern "C" int lemon_index_free(lemon_index_t *idx) {
     if (!idx) return LEMON_OK;
-    void *ptrs[] = {idx->x, idx->xp, idx->xnorm, idx->xh, idx->xh_stats, idx->xn2max_dev, idx->xnrange_dev, idx->ws_qp, idx->ws_qnorm,
-                    idx->ws_cand, idx->ws_part, idx->ws_state, idx->ws_D, idx->ws_I, idx->ws_dd, idx->ws_ddq,
-                    idx->plan_slots[0].dev, idx->plan_slots[1].dev, idx->plan_slots[2].dev, idx->plan_slots[3].dev};
-    for (void *p : ptrs)
+    for (void *p : {(void *)idx->x, (void *)idx->xp, (void *)idx->xnorm})
         if (p) (void)hipFree(p);
+    for (int b = 0; b < lemon_index::N_BUFS; ++b) lemon_release(idx, b);
     for (auto &e : *idx->prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     delete idx->prof_events;
     for (auto &slot : idx->plan_slots) delete slot.host;
@@ -174,8 +172,8 @@ extern "C" int lemon_index_add(lemon_index_t *idx, const float *x_dev, int64_t n
         if (idx->x) (void)hipFree(idx->x);
         if (idx->xp) (void)hipFree(idx->xp);
         if (idx->xnorm) (void)hipFree(idx->xnorm);
-        if (idx->xh) { (void)hipFree(idx->xh); idx->xh = nullptr; }
-        if (idx->xh_stats) { (void)hipFree(idx->xh_stats); idx->xh_stats = nullptr; }
+        lemon_release(idx, lemon_index::XH);             // the 16-bit copy is sized by cap: the next filter search rebuilds it
+        lemon_release(idx, lemon_index::XH_STATS);
         idx->xh_rows = 0;
         idx->x = nx; idx->xp = nxp; idx->xnorm = nxn; idx->cap = want;
     }
@@ -258,7 +256,7 @@ static int lemon_auto_choose(lemon_index_t *idx, const float *q_dev, int64_t nq,
 }
 
 int lemon_search_internal(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, float *D_dev,
-                          int64_t *I_dev, hipStream_t stream) {
+                          int64_t *I_dev, hipStream_t stream, bool may_dedup) {
     LEMON_REQUIRE(idx != nullptr, "index handle");
     LEMON_REQUIRE(nq >= 0, "nq >= 0");
     LEMON_REQUIRE(k >= 1 && k <= LEMON_MAX_K_DEEP, "1 <= k <= LEMON_MAX_K_DEEP");
@@ -266,30 +264,22 @@ int lemon_search_internal(lemon_index_t *idx, const float *q_dev, int64_t nq, in
     LEMON_REQUIRE(q_dev && D_dev && I_dev, "null pointer");
     LEMON_REQUIRE(rows_vector_safe(q_dev, idx->d), "q_dev must be 16-byte aligned when d % 4 == 0");
     // identical query rows (class prompts: 50 000 text queries, 100 distinct rows on CIFAR-100) are searched once
-    if (idx->qdedup && nq >= LEMON_DEDUP_MIN_NQ && nq < ((int64_t)1 << 31) && idx->n > 0) {
+    if (idx->qdedup && may_dedup && nq >= LEMON_DEDUP_MIN_NQ && nq < ((int64_t)1 << 31) && idx->n > 0) {
         int64_t U = 0;
         const int *rep = nullptr, *grp = nullptr;
         int rc = lemon_dedup_queries(idx, q_dev, nq, stream, &U, &rep, &grp);
         if (rc) return rc;
         if (U * 2 <= nq) {
             const size_t qb = ((size_t)U * idx->d * 4 + 255) & ~(size_t)255, db = ((size_t)U * k * 4 + 255) & ~(size_t)255;
-            const size_t need = qb + db + (size_t)U * k * 8;
-            if (need > idx->ws_ddq_bytes) {
-                LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-                if (idx->ws_ddq) (void)hipFree(idx->ws_ddq);
-                idx->ws_ddq = nullptr; idx->ws_ddq_bytes = 0;
-                if (hipMalloc((void **)&idx->ws_ddq, need) != hipSuccess) { lemon_set_error("dedup result workspace allocation failed"); return LEMON_E_NOMEM; }
-                idx->ws_ddq_bytes = need;
-            }
-            float *qrep = idx->ws_ddq;
-            float *Dr = (float *)((char *)idx->ws_ddq + qb);
-            int64_t *Ir = (int64_t *)((char *)idx->ws_ddq + qb + db);
+            rc = lemon_reserve(idx, lemon_index::WS_DDQ, qb + db + (size_t)U * k * 8, stream, "dedup result workspace");
+            if (rc) return rc;
+            char *ws = idx->at<char>(lemon_index::WS_DDQ);
+            float *qrep = (float *)ws;
+            float *Dr = (float *)(ws + qb);
+            int64_t *Ir = (int64_t *)(ws + qb + db);
             rc = lemon_gather_query_rows(q_dev, rep, U, idx->d, qrep, stream);
             if (rc) return rc;
-            const int saved = idx->qdedup;
-            idx->qdedup = 0;
-            rc = lemon_search_internal(idx, qrep, U, k, Dr, Ir, stream);
-            idx->qdedup = saved;
+            rc = lemon_search_internal(idx, qrep, U, k, Dr, Ir, stream, false);     // (the representatives are distinct)
             if (rc) return rc;
             idx->last.nq = nq;                        // (the reduced search recorded U: nq is the call's, nq_distinct what it searched)
             idx->last.nq_distinct = U;
@@ -365,8 +355,7 @@ __global__ __launch_bounds__(128) void k_neighbors_finalize(NbParams p) {
 
 int lemon_neighbors_finalize(const NbParams &p, hipStream_t stream) {
     const int64_t total = p.nq * p.k;
-    const bool staged = (p.d & 3) == 0 &&
-                        ((((uintptr_t)p.img_tr) | ((uintptr_t)p.txt_tr) | ((uintptr_t)p.q_img) | ((uintptr_t)p.q_txt)) & 15) == 0;
+    const bool staged = rows_staged(p.d, {p.img_tr, p.txt_tr, p.q_img, p.q_txt});
     const dim3 grid((unsigned)((total + 127) / 128)), block(128);
     const bool l2m = p.metric == LEMON_METRIC_L2;
     if (staged) {
@@ -380,6 +369,42 @@ int lemon_neighbors_finalize(const NbParams &p, hipStream_t stream) {
     return LEMON_OK;
 }
 
+// ---- the two-sided search (common.hpp says what each of the three does) ---------------------
+int lemon_two_sided_check(const TwoSided &c) {
+    LEMON_REQUIRE(c.img && c.txt, "index handles");
+    LEMON_REQUIRE(c.img->d == c.txt->d && c.img->n == c.txt->n && c.img->metric == c.txt->metric,
+                  "image and text index must agree in d, ntotal and metric");
+    LEMON_REQUIRE(c.nq >= 0, "nq >= 0");
+    LEMON_REQUIRE(c.k >= 1 && c.k + (c.drop_self ? 1 : 0) <= LEMON_MAX_K, "1 <= k, k + drop_self <= LEMON_MAX_K");
+    return LEMON_OK;
+}
+
+int lemon_two_sided_search(const TwoSided &c, int kd, int64_t elems, hipStream_t stream) {
+    LEMON_REQUIRE(c.q_img && c.q_txt, "null pointer");
+    LEMON_REQUIRE(!c.discrete || (c.tr_lab && c.q_lab), "label ids required when discrete");
+    LEMON_REQUIRE(rows_vector_safe(c.q_img, c.img->d) && rows_vector_safe(c.q_txt, c.img->d),
+                  "q_img_dev and q_txt_dev must be 16-byte aligned when d % 4 == 0");
+    int rc = lemon_reserve_nb(c.img, elems, stream);
+    if (rc) return rc;
+    float *D = c.img->at<float>(lemon_index::WS_D);
+    int64_t *I = c.img->at<int64_t>(lemon_index::WS_I);
+    // The image-side queries of the LEMoN loop are embeddings of distinct images: looking for duplicates among them costs a
+    // row hash, a radix sort and a host synchronisation per call for nothing, so de-duplication is applied to the TEXT side
+    // only (class datasets: C distinct prompts among nq queries, SURVEY A5).  A caller that does have duplicate image
+    // queries gets them folded by lemon_index_search on the handle itself.
+    rc = lemon_search_internal(c.img, c.q_img, c.nq, kd, D, I, stream, false);                  // run_lemon.py:235
+    if (rc) return rc;
+    return lemon_search_internal(c.txt, c.q_txt, c.nq, kd, D + c.nq * kd, I + c.nq * kd, stream);   // run_lemon.py:236
+}
+
+NbParams lemon_nb_params(const TwoSided &c) {
+    NbParams p = {};
+    p.img_tr = c.img->x; p.txt_tr = c.txt->x; p.q_img = c.q_img; p.q_txt = c.q_txt;
+    p.in_db = c.in_db; p.tr_lab = c.tr_lab; p.q_lab = c.q_lab;
+    p.nq = c.nq; p.d = c.img->d; p.k = c.k; p.drop_self = c.drop_self; p.discrete = c.discrete;
+    return p;
+}
+
 extern "C" int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, const float *dists_tr_dev,
                                const float *q_img_dev, const float *q_txt_dev, int64_t nq, int k,
                                int drop_self, const uint8_t *in_db_dev, int discrete,
@@ -388,57 +413,23 @@ extern "C" int lemon_neighbors(lemon_index_t *idx_img, lemon_index_t *idx_txt, c
                                int64_t *I_n_dev, float *D_m_dev, float *dists_m_dev, float *dists_tr_m_dev,
                                int64_t *I_m_dev, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    LEMON_REQUIRE(idx_img && idx_txt, "index handles");
-    LEMON_REQUIRE(idx_img->d == idx_txt->d && idx_img->n == idx_txt->n && idx_img->metric == idx_txt->metric,
-                  "image and text index must agree in d, ntotal and metric");
-    LEMON_REQUIRE(nq >= 0, "nq >= 0");
-    const int ks = k + (drop_self ? 1 : 0);
-    LEMON_REQUIRE(k >= 1 && ks <= LEMON_MAX_K, "1 <= k, k + drop_self <= LEMON_MAX_K");
-    if (nq == 0) return LEMON_OK;
-    LEMON_REQUIRE(dists_tr_dev && q_img_dev && q_txt_dev && d1_dev && D_n_dev && dists_n_dev &&
-                      dists_tr_n_dev && D_m_dev && dists_m_dev && dists_tr_m_dev, "null pointer");
-    LEMON_REQUIRE(!discrete || (tr_label_id_dev && q_label_id_dev), "label ids required when discrete");
-    LEMON_REQUIRE(rows_vector_safe(q_img_dev, idx_img->d) && rows_vector_safe(q_txt_dev, idx_img->d),
-                  "q_img_dev and q_txt_dev must be 16-byte aligned when d % 4 == 0");
-    // raw search outputs live in the image index's neighbour workspace: [2][nq, ks]
-    const int64_t need = 2 * nq * ks;
-    if (need > idx_img->ws_nb) {
-        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        if (idx_img->ws_D) (void)hipFree(idx_img->ws_D);
-        if (idx_img->ws_I) (void)hipFree(idx_img->ws_I);
-        idx_img->ws_D = nullptr; idx_img->ws_I = nullptr; idx_img->ws_nb = 0;
-        if (hipMalloc(&idx_img->ws_D, (size_t)need * sizeof(float)) != hipSuccess ||
-            hipMalloc(&idx_img->ws_I, (size_t)need * sizeof(int64_t)) != hipSuccess) {
-            lemon_set_error("neighbour workspace allocation failed");
-            return LEMON_E_NOMEM;
-        }
-        idx_img->ws_nb = need;
-    }
-    float *Dn = idx_img->ws_D, *Dm = idx_img->ws_D + nq * ks;
-    int64_t *In = idx_img->ws_I, *Im = idx_img->ws_I + nq * ks;
-    // The image-side queries of the LEMoN loop are embeddings of distinct images: looking for duplicates among them costs a
-    // row hash, a radix sort and a host synchronisation per call for nothing, so de-duplication is applied to the TEXT side
-    // only (class datasets: C distinct prompts among nq queries, SURVEY A5).  A caller that does have duplicate image
-    // queries gets them folded by lemon_index_search on the handle itself.
-    const int img_dedup = idx_img->qdedup;
-    idx_img->qdedup = 0;
-    int rc = lemon_search_internal(idx_img, q_img_dev, nq, ks, Dn, In, stream);   // run_lemon.py:235
-    idx_img->qdedup = img_dedup;
+    const TwoSided c = {idx_img, idx_txt, q_img_dev, q_txt_dev, nq, k, drop_self, discrete, in_db_dev, tr_label_id_dev, q_label_id_dev};
+    int rc = lemon_two_sided_check(c);
     if (rc) return rc;
-    rc = lemon_search_internal(idx_txt, q_txt_dev, nq, ks, Dm, Im, stream);       // run_lemon.py:236
+    if (nq == 0) return LEMON_OK;
+    LEMON_REQUIRE(dists_tr_dev && d1_dev && D_n_dev && dists_n_dev && dists_tr_n_dev && D_m_dev && dists_m_dev && dists_tr_m_dev,
+                  "null pointer");
+    const int ks = k + (drop_self ? 1 : 0);
+    rc = lemon_two_sided_search(c, ks, 2 * nq * ks, stream);     // raw search outputs: [2][nq, ks]
     if (rc) return rc;
     rc = lemon_paired_distance(idx_img->metric, q_img_dev, q_txt_dev, nq, idx_img->d, d1_dev, stream);
     if (rc) return rc;
-    NbParams p;
-    p.img_tr = idx_img->x; p.txt_tr = idx_txt->x; p.dists_tr = dists_tr_dev;
-    p.q_img = q_img_dev; p.q_txt = q_txt_dev;
-    p.Dn = Dn; p.Dm = Dm; p.In = In; p.Im = Im;
-    p.in_db = in_db_dev; p.tr_lab = tr_label_id_dev; p.q_lab = q_label_id_dev;
-    p.D_n = D_n_dev; p.dists_n = dists_n_dev; p.dists_tr_n = dists_tr_n_dev;
-    p.D_m = D_m_dev; p.dists_m = dists_m_dev; p.dists_tr_m = dists_tr_m_dev;
-    p.I_n = I_n_dev; p.I_m = I_m_dev;
-    p.nq = nq; p.d = idx_img->d; p.k = k; p.ks = ks; p.metric = idx_img->metric;
-    p.drop_self = drop_self; p.discrete = discrete;
+    NbParams p = lemon_nb_params(c);
+    p.dists_tr = dists_tr_dev; p.ks = ks; p.metric = idx_img->metric;
+    p.Dn = idx_img->at<float>(lemon_index::WS_D); p.Dm = p.Dn + nq * ks;
+    p.In = idx_img->at<int64_t>(lemon_index::WS_I); p.Im = p.In + nq * ks;
+    p.D_n = D_n_dev; p.dists_n = dists_n_dev; p.dists_tr_n = dists_tr_n_dev; p.I_n = I_n_dev;
+    p.D_m = D_m_dev; p.dists_m = dists_m_dev; p.dists_tr_m = dists_tr_m_dev; p.I_m = I_m_dev;
     return lemon_neighbors_finalize(p, stream);
 }
 
@@ -507,22 +498,11 @@ extern "C" int lemon_discrepancy(int method, lemon_index_t *idx_txt, const float
     const int kc = k + 1, kq = k + (is_train ? 1 : 0);
     const int64_t n = idx_txt->n;
     // scratch: cache [n, kc] (dis only) + Im [nq, kq] (+ the D arrays the searches return)
-    const int64_t need = (method == 0 ? n * kc : 0) + nq * kq;
-    if (need > idx_txt->ws_nb) {
-        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        if (idx_txt->ws_D) (void)hipFree(idx_txt->ws_D);
-        if (idx_txt->ws_I) (void)hipFree(idx_txt->ws_I);
-        idx_txt->ws_D = nullptr; idx_txt->ws_I = nullptr; idx_txt->ws_nb = 0;
-        if (hipMalloc(&idx_txt->ws_D, (size_t)need * sizeof(float)) != hipSuccess ||
-            hipMalloc(&idx_txt->ws_I, (size_t)need * sizeof(int64_t)) != hipSuccess) {
-            lemon_set_error("discrepancy workspace allocation failed");
-            return LEMON_E_NOMEM;
-        }
-        idx_txt->ws_nb = need;
-    }
-    int64_t *Ic = idx_txt->ws_I, *Im = idx_txt->ws_I + (method == 0 ? n * kc : 0);
-    float *Dc = idx_txt->ws_D, *Dm = idx_txt->ws_D + (method == 0 ? n * kc : 0);
-    int rc;
+    const int64_t cache = method == 0 ? n * kc : 0;
+    int rc = lemon_reserve_nb(idx_txt, cache + nq * kq, stream);
+    if (rc) return rc;
+    int64_t *Ic = idx_txt->at<int64_t>(lemon_index::WS_I), *Im = Ic + cache;
+    float *Dc = idx_txt->at<float>(lemon_index::WS_D), *Dm = Dc + cache;
     if (method == 0) {   // cache of the DB's own text neighbours, discrepancy_baseline.py:165-169
         rc = lemon_search_internal(idx_txt, idx_txt->x, n, kc, Dc, Ic, stream);
         if (rc) return rc;
@@ -533,7 +513,7 @@ extern "C" int lemon_discrepancy(int method, lemon_index_t *idx_txt, const float
     p.E = E_tr_dev; p.qv = qv_dev; p.Im = Im; p.Ic = Ic; p.out = out_dev; p.nq = nq;
     p.d = idx_txt->d; p.k = k; p.kq = kq; p.kc = kc; p.method = method;
     {
-        const bool staged = (p.d & 3) == 0 && ((((uintptr_t)p.E) | ((uintptr_t)p.qv)) & 15) == 0;
+        const bool staged = rows_staged(p.d, {p.E, p.qv});
         const dim3 grid((unsigned)((nq + 1) / 2)), block(128);
         if (staged) hipLaunchKernelGGL(k_discrepancy<true>, grid, block, 0, stream, p);
         else hipLaunchKernelGGL(k_discrepancy<false>, grid, block, 0, stream, p);

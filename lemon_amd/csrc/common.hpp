@@ -8,6 +8,8 @@
 #include <float.h>
 #include "../../include/lemon_hip.h"
 #include "attention_plan.hpp"
+#include "index_ws.hpp"
+#include <initializer_list>
 #include <vector>
 #include <utility>
 #include <mutex>
@@ -39,6 +41,13 @@ void lemon_set_error(const char *fmt, ...);
 // strength of d alone (exact_score and the staged k_bf16_final in knn_bf16.hip), so such rows must start on a 16-byte
 // boundary.  With d % 4 != 0 every kernel walks rows one float at a time and any float pointer will do.
 static inline bool rows_vector_safe(const float *p, int d) { return (d & 3) != 0 || (((uintptr_t)p) & 15) == 0; }
+// The STAGED forms of the pair-distance kernels (chain_dist_wave) fetch rows 16 bytes at a time: d % 4 == 0 and every row
+// array the kernel reads (a null one is not read) on a 16-byte boundary; otherwise every lane walks its rows from global.
+static inline bool rows_staged(int d, std::initializer_list<const float *> rows) {
+    uintptr_t bits = 0;
+    for (const float *p : rows) bits |= (uintptr_t)p;
+    return (d & 3) == 0 && (bits & 15) == 0;
+}
 
 // ---- index object ---------------------------------------------------------------
 // Data layout in HBM (DESIGN.md "Data layout"):
@@ -55,53 +64,81 @@ struct lemon_index {
     int algo;
     int64_t n, cap;       // rows stored / rows allocated (cap is a multiple of 128)
     float *x, *xp, *xnorm;
-    // bf16 filter copies (built lazily by the bf16 path)
-    unsigned short *xh;   // [cap, dpad_h] bf16 (RNE) of x
-    float *xh_stats;      // [2, cap]: measured ||x-xh||^2 and ||xh||^2 per row
-    int64_t xh_rows;      // rows of xh that are up to date
-    unsigned *xn2max_dev; // device scalars (float bits): max dot(x,x), max ||x-xh||^2, max ||xh||^2
-    unsigned *xnrange_dev; // device scalars (float bits): min and max of xnorm[0 .. n) for the metric sweep (metric_sweep.hip)
-    int64_t xnrange_rows; // 1 + the n xnrange_dev was reduced at (0: never), so every add makes it stale
-    // search workspace (grown on demand)
-    int64_t ws_q;         // query rows the workspace is sized for
-    int64_t ws_qp_row_bytes;  // bytes per staged query row the workspace is sized for
-    int dpad_h;           // column pitch of xh (0 until the bf16 copy exists)
-    float *ws_qp;         // [ws_q, dpad] permuted queries
-    float *ws_qnorm;      // [ws_q]
-    u64 *ws_cand;         // [ws_cand_rows, CAND_CAP]  (one 128-row region per scan workgroup)
-    int64_t ws_cand_rows;
-    float *ws_state;      // [grid*128][2] per-query scan state carried across database chunks
-    int64_t ws_state_elems;
-    u64 *ws_part;         // [splits_cap, ws_q, LEMON_MAX_K]
-    int64_t ws_part_elems;
+    // every device buffer that is grown on demand, under the rule of index_ws.hpp (DESIGN.md "Index buffers"):
+    //   XH, XH_STATS, XN2MAX  one group, built lazily by the filter scan (knn_bf16.hip): [cap, dpad_h] 16-bit (RNE) copy of x;
+    //             [2, cap] measured ||x-xh||^2 and ||xh||^2 per row; float bits of max dot(x,x), max ||x-xh||^2, max ||xh||^2
+    //   XNRANGE   float bits: min and max of xnorm[0 .. n) for the metric sweep (metric_sweep.hip)
+    //   WS_QP, WS_QNORM  one group: [ws_q] staged query rows of ws_qp_row_bytes each; [3, ws_q] norms + two spare columns
+    //   WS_CAND   [rows, CAND_CAP] candidates (one 128-row region per scan workgroup)
+    //   WS_PART   [splits, ws_q, LEMON_MAX_K] lists to merge
+    //   WS_STATE  per-lane scan state carried across database chunks + the list counts of k_bf16_final
+    //   WS_D, WS_I  one group of equal element counts: the neighbour workspace of the two-sided search and the discrepancy baselines
+    //   WS_DD, WS_DDQ  query de-duplication (dedup.hip): its arrays; the gathered representative queries + their results
+    //   PLAN0 ..  the device side of plan_slots[0 .. 3]
+    enum Buf { XH, XH_STATS, XN2MAX, XNRANGE, WS_QP, WS_QNORM, WS_CAND, WS_PART, WS_STATE, WS_D, WS_I, WS_DD, WS_DDQ, PLAN0,
+               N_BUFS = PLAN0 + 4 };
+    LemonBuf buf[N_BUFS];
+    template <typename T> T *at(int which) const { return reinterpret_cast<T *>(buf[which].p); }
+    int64_t xh_rows;      // rows of XH that are up to date
+    int dpad_h;           // column pitch of XH (0 until the 16-bit copy exists)
+    int64_t xnrange_rows; // 1 + the n XNRANGE was reduced at (0: never), so every add makes it stale
+    int64_t ws_q;         // query rows WS_QP / WS_QNORM are sized for (the stride of WS_QNORM's three columns)
+    int64_t ws_qp_row_bytes;  // bytes per staged query row WS_QP is sized for
     // fp32 scan: segment plans on the device (knn_f32.hip), a few recent (panels, tiles) shapes -- a pipeline alternates
     // between its train / val / test query counts.  `host` keeps the upload's source alive (stream-ordered copy).
     struct PlanSlot {
         int panels, tiles, grid, splits, pieces_off, segs_off;
-        int *dev; int64_t ints; unsigned long long stamp; std::vector<int> *host;
+        unsigned long long stamp; std::vector<int> *host;
     } plan_slots[4];
     unsigned long long plan_clock;
-    // neighbours workspace
-    int64_t ws_nb;        // elements
-    float *ws_D;          // [ws_nb]
-    int64_t *ws_I;        // [ws_nb]
     lemon_search_info_t last;
     const char *last_kernel;  // family name of the last search's dominant scan kernel (static string; null before any search)
     int wide_filter;      // 1: widths 769..1280 take the register-resident pitches 1024 / 1280 (k_scan_f16_qsw, knn_bf16.hip)
     // LEMON_ALGO_AUTO decision cache (valid while auto_n == n)
     int auto_algo;
     int64_t auto_n;
-    // query de-duplication (dedup.hip): mode (0 off, 1 auto) and its workspace
+    // query de-duplication (dedup.hip): 0 off, 1 auto.  Written by lemon_index_create and lemon_index_set_query_dedup only:
+    // a call that must not fold says so in its arguments (lemon_search_internal)
     int qdedup;
-    void *ws_dd;
-    size_t ws_dd_bytes;
-    float *ws_ddq;        // gathered representative queries + their results
-    size_t ws_ddq_bytes;
     // optional scan-kernel timing (lemon_index_set_profiling)
     int profiling;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> *prof_events;
     double prof_flops, prof_bytes;
 };
+
+// the rule of index_ws.hpp on the device: growth synchronises `s`, the stream of the call that grows
+struct LemonHipDev {
+    hipStream_t s;
+    bool sync() { return hipStreamSynchronize(s) == hipSuccess; }
+    bool alloc(void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; }
+    void free(void *p) { (void)hipFree(p); }
+};
+// every member of an all-or-nothing group of (which, bytes) at its size or more; `what` names the workspace in lemon_last_error
+inline int lemon_reserve_group(lemon_index *idx, std::initializer_list<std::pair<int, size_t>> want, hipStream_t stream, const char *what) {
+    LemonBuf *bufs[lemon_ws::MAX_GROUP];
+    size_t bytes[lemon_ws::MAX_GROUP], total = 0;
+    int n = 0;
+    for (const auto &w : want) { bufs[n] = &idx->buf[w.first]; bytes[n++] = w.second; total += w.second; }
+    LemonHipDev dev{stream};
+    const lemon_ws::Result r = lemon_ws::reserve_group(dev, bufs, bytes, n);
+    if (r == lemon_ws::OK) return LEMON_OK;
+    const bool nomem = r == lemon_ws::NO_MEMORY;
+    lemon_set_error("%s: %s (%zu bytes)", what, nomem ? "allocation failed" : "stream synchronisation failed", total);
+    return nomem ? LEMON_E_NOMEM : LEMON_E_HIP;
+}
+inline int lemon_reserve(lemon_index *idx, int which, size_t bytes, hipStream_t stream, const char *what) {
+    return lemon_reserve_group(idx, {{which, bytes}}, stream, what);
+}
+// free and empty; the caller has synchronised whatever may still read the buffer
+inline void lemon_release(lemon_index *idx, int which) {
+    LemonHipDev dev{nullptr};
+    lemon_ws::release(dev, idx->buf[which]);
+}
+// WS_D / WS_I at `elems` elements each
+inline int lemon_reserve_nb(lemon_index *idx, int64_t elems, hipStream_t stream) {
+    return lemon_reserve_group(idx, {{lemon_index::WS_D, (size_t)elems * sizeof(float)}, {lemon_index::WS_I, (size_t)elems * sizeof(int64_t)}},
+                               stream, "neighbour workspace");
+}
 
 // bracket a kernel launch with events when profiling is on
 struct LemonProfScope {
@@ -156,8 +193,9 @@ __host__ __device__ inline u32 lemon_key_index(u64 key) { return 0xffffffffu - (
 #define LEMON_DEDUP_MIN_NQ 1024 // query de-duplication is attempted from this many queries on
 
 // internal entry points shared between translation units
+// may_dedup: this call may fold identical query rows, if the handle's setting says so too (idx->qdedup && may_dedup)
 int lemon_search_internal(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
-                          float *D_dev, int64_t *I_dev, hipStream_t stream);
+                          float *D_dev, int64_t *I_dev, hipStream_t stream, bool may_dedup = true);
 int lemon_rowdot_chain(const float *a, const float *b, int64_t n, int d, float *out, hipStream_t s);
 // K4, the neighbour finalisation of lemon_neighbors (api.hip), shared with lemon_neighbors_metrics (metric_sweep.hip)
 struct NbParams {
@@ -172,6 +210,21 @@ struct NbParams {
     int d, k, ks, metric, drop_self, discrete;
 };
 int lemon_neighbors_finalize(const NbParams &p, hipStream_t stream);
+// The two-sided search behind lemon_neighbors and lemon_neighbors_metrics (api.hip).  TwoSided: the arguments both are given.
+// _check: the handles and counts (the entry's own checks follow it).  _search: checks the query rows and labels, reserves the
+// image handle's neighbour workspace at `elems` elements and searches both sides at kd into its front, [2][nq, kd], image side
+// first: the image side never de-duplicated, the text side as its handle says (nq == 0: checks only).  lemon_nb_params: the
+// fields of NbParams that do not depend on the metric or on where the lists and the outputs are.
+struct TwoSided {
+    lemon_index_t *img, *txt;
+    const float *q_img, *q_txt;
+    int64_t nq;
+    int k, drop_self, discrete;
+    const uint8_t *in_db; const int32_t *tr_lab, *q_lab;
+};
+int lemon_two_sided_check(const TwoSided &c);
+int lemon_two_sided_search(const TwoSided &c, int kd, int64_t elems, hipStream_t stream);
+NbParams lemon_nb_params(const TwoSided &c);
 int lemon_dedup_queries(lemon_index_t *idx, const float *q_dev, int64_t nq, hipStream_t stream, int64_t *U_host,
                         const int **rep_dev, const int **group_dev);
 int lemon_gather_query_rows(const float *q_dev, const int *rep_dev, int64_t U, int d, float *out_dev, hipStream_t stream);

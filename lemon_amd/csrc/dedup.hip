@@ -95,15 +95,8 @@ int lemon_dedup_queries(lemon_index_t *idx, const float *q_dev, int64_t nq, hipS
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, t2, (const int *)nullptr, (int *)nullptr, (int)nq, stream);
     const size_t tmp = align256(t1 > t2 ? t1 : t2);
     const size_t n8 = align256((size_t)nq * 8), n4 = align256((size_t)nq * 4);
-    const size_t need = 2 * n8 + 6 * n4 + tmp + 256;
-    if (need > idx->ws_dd_bytes) {
-        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        if (idx->ws_dd) (void)hipFree(idx->ws_dd);
-        idx->ws_dd = nullptr; idx->ws_dd_bytes = 0;
-        if (hipMalloc(&idx->ws_dd, need) != hipSuccess) { lemon_set_error("dedup workspace allocation failed (%zu bytes)", need); return LEMON_E_NOMEM; }
-        idx->ws_dd_bytes = need;
-    }
-    char *p = (char *)idx->ws_dd;
+    if (int rc = lemon_reserve(idx, lemon_index::WS_DD, 2 * n8 + 6 * n4 + tmp + 256, stream, "dedup workspace")) return rc;
+    char *p = idx->at<char>(lemon_index::WS_DD);
     u64 *h = (u64 *)p; p += n8;
     u64 *hs = (u64 *)p; p += n8;
     u32 *iota = (u32 *)p; p += n4;

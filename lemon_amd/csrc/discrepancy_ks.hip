@@ -64,22 +64,6 @@ __global__ __launch_bounds__(64) void k_discrepancy_ks(DiscKsParams p) {
     }
 }
 
-// the index's neighbour workspace, as lemon_discrepancy grows it
-static int disc_workspace(lemon_index_t *idx, int64_t need, hipStream_t stream) {
-    if (need <= idx->ws_nb) return LEMON_OK;
-    LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-    if (idx->ws_D) (void)hipFree(idx->ws_D);
-    if (idx->ws_I) (void)hipFree(idx->ws_I);
-    idx->ws_D = nullptr; idx->ws_I = nullptr; idx->ws_nb = 0;
-    if (hipMalloc(&idx->ws_D, (size_t)need * sizeof(float)) != hipSuccess ||
-        hipMalloc(&idx->ws_I, (size_t)need * sizeof(int64_t)) != hipSuccess) {
-        lemon_set_error("discrepancy workspace allocation failed");
-        return LEMON_E_NOMEM;
-    }
-    idx->ws_nb = need;
-    return LEMON_OK;
-}
-
 extern "C" int lemon_discrepancy_cache(lemon_index_t *idx_txt, int kc, int64_t *Ic_dev, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     LEMON_REQUIRE(idx_txt && idx_txt->metric == LEMON_METRIC_IP, "text index must be an IndexFlatIP");
@@ -87,8 +71,8 @@ extern "C" int lemon_discrepancy_cache(lemon_index_t *idx_txt, int kc, int64_t *
     const int64_t n = idx_txt->n;
     if (n == 0) return LEMON_OK;
     LEMON_REQUIRE(Ic_dev, "null pointer");
-    if (int rc = disc_workspace(idx_txt, n * kc, stream)) return rc;     // the distances the search returns beside the lists
-    return lemon_search_internal(idx_txt, idx_txt->x, n, kc, idx_txt->ws_D, Ic_dev, stream);   // discrepancy_baseline.py:166
+    if (int rc = lemon_reserve_nb(idx_txt, n * kc, stream)) return rc;   // the distances the search returns beside the lists
+    return lemon_search_internal(idx_txt, idx_txt->x, n, kc, idx_txt->at<float>(lemon_index::WS_D), Ic_dev, stream);   // discrepancy_baseline.py:166
 }
 
 static int check_ks(const int32_t *ks, int n_ks) {
@@ -122,9 +106,9 @@ extern "C" int lemon_discrepancy_ks(lemon_index_t *idx_txt, const float *E_img_t
     LEMON_REQUIRE(rows_vector_safe(E_img_tr_dev, d) && rows_vector_safe(E_txt_tr_dev, d) && rows_vector_safe(q_img_dev, d) &&
                       rows_vector_safe(q_txt_dev, d),
                   "E_img_tr_dev, E_txt_tr_dev, q_img_dev and q_txt_dev must be 16-byte aligned when d % 4 == 0");
-    if (int rc = disc_workspace(idx_txt, nq * kqmax, stream)) return rc;
-    int64_t *Im = idx_txt->ws_I;
-    if (int rc = lemon_search_internal(idx_txt, q_txt_dev, nq, kqmax, idx_txt->ws_D, Im, stream)) return rc;   // :209
+    if (int rc = lemon_reserve_nb(idx_txt, nq * kqmax, stream)) return rc;
+    int64_t *Im = idx_txt->at<int64_t>(lemon_index::WS_I);
+    if (int rc = lemon_search_internal(idx_txt, q_txt_dev, nq, kqmax, idx_txt->at<float>(lemon_index::WS_D), Im, stream)) return rc;   // :209
     DiscKsParams p;
     p.E[0] = E_img_tr_dev; p.E[1] = E_txt_tr_dev; p.q[0] = q_img_dev; p.q[1] = q_txt_dev;
     p.Im = Im; p.Ic = Ic_dev; p.out = out_dev; p.nq = nq;
@@ -137,8 +121,7 @@ extern "C" int lemon_discrepancy_ks(lemon_index_t *idx_txt, const float *E_img_t
     for (int t = 0; t < DSC_MAX_KS; ++t) p.ks[t] = t < n_ks ? ks[t] : 0;
     const int wmax = dis ? (kmax + 1 > kqmax ? kmax + 1 : kqmax) : kqmax;
     const size_t lds = (size_t)kqmax * wmax * sizeof(float);
-    const bool staged = (d & 3) == 0 && ((((uintptr_t)E_img_tr_dev) | ((uintptr_t)E_txt_tr_dev) | ((uintptr_t)q_img_dev) |
-                                          ((uintptr_t)q_txt_dev)) & 15) == 0;
+    const bool staged = rows_staged(d, {E_img_tr_dev, E_txt_tr_dev, q_img_dev, q_txt_dev});
     const dim3 grid((unsigned)nq, (unsigned)nmat), block(64);
     if (staged) hipLaunchKernelGGL(k_discrepancy_ks<true>, grid, block, lds, stream, p);
     else hipLaunchKernelGGL(k_discrepancy_ks<false>, grid, block, lds, stream, p);

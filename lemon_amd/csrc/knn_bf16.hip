@@ -2231,35 +2231,34 @@ static int convert_rows(const float *src, int64_t n, int d, lp16 *dst, int dpad_
 
 static int ensure_bf16_copy(lemon_index_t *idx, hipStream_t stream) {
     const int dpad_h = bf16_pitch(idx);
-    if (idx->xh && idx->dpad_h != dpad_h) {      // the wide-filter switch was toggled: the copy exists at the other pitch
+    if (idx->buf[lemon_index::XH].p && idx->dpad_h != dpad_h) {   // the wide-filter switch was toggled: the copy exists at the other pitch
         LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        (void)hipFree(idx->xh); idx->xh = nullptr;
-        if (idx->xh_stats) { (void)hipFree(idx->xh_stats); idx->xh_stats = nullptr; }
+        lemon_release(idx, lemon_index::XH);
+        lemon_release(idx, lemon_index::XH_STATS);
         idx->xh_rows = 0;
     }
     idx->dpad_h = dpad_h;
-    if (!idx->xh) {
-        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        if (hipMalloc(&idx->xh, (size_t)idx->cap * dpad_h * sizeof(unsigned short) + 16) != hipSuccess ||
-            hipMalloc(&idx->xh_stats, (size_t)idx->cap * 2 * sizeof(float)) != hipSuccess ||
-            (!idx->xn2max_dev && hipMalloc(&idx->xn2max_dev, 16) != hipSuccess)) {
-            lemon_set_error("bf16 copy allocation failed");
-            return LEMON_E_NOMEM;
-        }
-        LEMON_HIP_CHECK(hipMemsetAsync(idx->xh, 0, (size_t)idx->cap * dpad_h * sizeof(unsigned short), stream));
+    if (!idx->buf[lemon_index::XH].p) {
+        // all three or none: a call that fails here leaves XH empty, so the next one comes back to this block
+        int rc = lemon_reserve_group(idx, {{lemon_index::XH, (size_t)idx->cap * dpad_h * sizeof(unsigned short) + 16},
+                                           {lemon_index::XH_STATS, (size_t)idx->cap * 2 * sizeof(float)},
+                                           {lemon_index::XN2MAX, 16}}, stream, "16-bit copy");
+        if (rc) return rc;
+        LEMON_HIP_CHECK(hipMemsetAsync(idx->buf[lemon_index::XH].p, 0, (size_t)idx->cap * dpad_h * sizeof(unsigned short), stream));
         idx->xh_rows = 0;
     }
     if (idx->xh_rows < idx->n) {
         const int64_t n_new = idx->n - idx->xh_rows;
-        float *res2 = idx->xh_stats, *hn2 = idx->xh_stats + idx->cap;
+        float *res2 = idx->at<float>(lemon_index::XH_STATS), *hn2 = res2 + idx->cap;
+        unsigned *xn2max = idx->at<unsigned>(lemon_index::XN2MAX);
         int rc = convert_rows(idx->x + idx->xh_rows * idx->d, n_new, idx->d,
-                              reinterpret_cast<lp16 *>(idx->xh) + idx->xh_rows * dpad_h, dpad_h,
+                              idx->at<lp16>(lemon_index::XH) + idx->xh_rows * dpad_h, dpad_h,
                               res2 + idx->xh_rows, hn2 + idx->xh_rows, stream);
         if (rc) return rc;
-        LEMON_HIP_CHECK(hipMemsetAsync(idx->xn2max_dev, 0, 16, stream));
-        hipLaunchKernelGGL(k_max_nonneg, dim3(256), dim3(256), 0, stream, idx->xnorm, idx->n, idx->xn2max_dev);
-        hipLaunchKernelGGL(k_max_nonneg, dim3(256), dim3(256), 0, stream, res2, idx->n, idx->xn2max_dev + 1);
-        hipLaunchKernelGGL(k_max_nonneg, dim3(256), dim3(256), 0, stream, hn2, idx->n, idx->xn2max_dev + 2);
+        LEMON_HIP_CHECK(hipMemsetAsync(xn2max, 0, 16, stream));
+        hipLaunchKernelGGL(k_max_nonneg, dim3(256), dim3(256), 0, stream, idx->xnorm, idx->n, xn2max);
+        hipLaunchKernelGGL(k_max_nonneg, dim3(256), dim3(256), 0, stream, res2, idx->n, xn2max + 1);
+        hipLaunchKernelGGL(k_max_nonneg, dim3(256), dim3(256), 0, stream, hn2, idx->n, xn2max + 2);
         LEMON_HIP_CHECK(hipGetLastError());
         idx->xh_rows = idx->n;
     }
@@ -2344,20 +2343,6 @@ static void launch_final(const FinalParams &fp, bool l2, hipStream_t stream) {
     hipLaunchKernelGGL(fn, dim3((unsigned)((fp.n_lists + 3) / 4)), dim3(256), 0, stream, fp);
 }
 
-// per-lane state carried between chunk launches + the list counts handed to k_bf16_final
-static int ensure_scan_state(lemon_index_t *idx, int64_t elems, hipStream_t stream) {
-    if (elems <= idx->ws_state_elems) return LEMON_OK;
-    LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-    if (idx->ws_state) (void)hipFree(idx->ws_state);
-    idx->ws_state = nullptr; idx->ws_state_elems = 0;
-    if (hipMalloc(&idx->ws_state, (size_t)elems * sizeof(float)) != hipSuccess) {
-        lemon_set_error("scan state allocation failed");
-        return LEMON_E_NOMEM;
-    }
-    idx->ws_state_elems = elems;
-    return LEMON_OK;
-}
-
 int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, float *D_dev,
                       int64_t *I_dev, hipStream_t stream) {
     const int d = idx->d;
@@ -2377,13 +2362,17 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
         const bool stationary = pl.kernel != plan::SCAN_BF16;   // lane lists, chunked launches, k_bf16_final
         rc = lemon_ensure_search_ws(idx, nq_pad, pl.splits, (int64_t)grid * (pl.panel / BQ), dpad_h * 2, CAPH, stream);
         if (rc) return rc;
-        rc = ensure_scan_state(idx, pl.state_elems + pl.cnt_elems, stream);
+        // per-lane state carried between chunk launches + the list counts handed to k_bf16_final
+        rc = lemon_reserve(idx, lemon_index::WS_STATE, (size_t)(pl.state_elems + pl.cnt_elems) * sizeof(float), stream, "scan state");
         if (rc) return rc;
         // bf16 query panel (pad rows zero), chain norms, measured rounding residuals
-        lp16 *qh = reinterpret_cast<lp16 *>(idx->ws_qp);
-        float *qn = idx->ws_qnorm, *qres2 = idx->ws_qnorm + idx->ws_q, *qhn2 = idx->ws_qnorm + 2 * idx->ws_q;
+        lp16 *qh = idx->at<lp16>(lemon_index::WS_QP);
+        float *qn = idx->at<float>(lemon_index::WS_QNORM), *qres2 = qn + idx->ws_q, *qhn2 = qn + 2 * idx->ws_q;
+        float *state = idx->at<float>(lemon_index::WS_STATE);
+        u64 *part = idx->at<u64>(lemon_index::WS_PART);
+        const unsigned *xstat = idx->at<unsigned>(lemon_index::XN2MAX);
         LEMON_HIP_CHECK(hipMemsetAsync(qh, 0, (size_t)nq_pad * dpad_h * sizeof(unsigned short), stream));
-        LEMON_HIP_CHECK(hipMemsetAsync(idx->ws_qnorm, 0, (size_t)idx->ws_q * 3 * sizeof(float), stream));
+        LEMON_HIP_CHECK(hipMemsetAsync(qn, 0, (size_t)idx->ws_q * 3 * sizeof(float), stream));
         rc = convert_rows(q_dev + c0 * d, cn, d, qh, dpad_h, qres2, qhn2, stream);
         if (rc) return rc;
         rc = lemon_rowdot_chain(q_dev + c0 * d, q_dev + c0 * d, cn, d, qn, stream);
@@ -2391,21 +2380,21 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
 
         ScanParamsH p;
         p.b.qp = nullptr; p.b.xp = nullptr; p.b.qnorm = qn; p.b.xnorm = idx->xnorm;
-        p.b.cand = idx->ws_cand; p.b.part = idx->ws_part;
+        p.b.cand = idx->at<u64>(lemon_index::WS_CAND); p.b.part = part;
         p.b.D = D_dev + c0 * k; p.b.I = I_dev + c0 * k;
         p.b.nq = cn; p.b.n = idx->n; p.b.dpad = dpad_h; p.b.kk = k; p.b.metric = idx->metric;
         p.b.n_tiles = pl.n_tiles; p.b.tiles_per_split = pl.tiles_per_split; p.b.splits = pl.splits; p.b.nq_pad = nq_pad;
-        p.qh = qh; p.xh = reinterpret_cast<const lp16 *>(idx->xh);
-        p.q = q_dev + c0 * d; p.x = idx->x; p.qres2 = qres2; p.qhn2 = qhn2; p.xstat = idx->xn2max_dev;
+        p.qh = qh; p.xh = idx->at<lp16>(lemon_index::XH);
+        p.q = q_dev + c0 * d; p.x = idx->x; p.qres2 = qres2; p.qhn2 = qhn2; p.xstat = xstat;
         p.d = d; p.dpad_h = dpad_h;
         rc = lemon_parse_ablate("k_scan_bf16_qs", 1 | 4, &p.ablate);   // bit 1 (value 2) does not exist: see ScanParamsH
         if (rc) return rc;
         p.b.stale = scan_refresh();
-        p.state = idx->ws_state;
-        p.cnt = reinterpret_cast<int *>(idx->ws_state + pl.state_elems);
+        p.state = state;
+        p.cnt = reinterpret_cast<int *>(state + pl.state_elems);
         FinalParams fp;
         fp.b = p.b; fp.q = p.q; fp.x = p.x; fp.cnt = p.cnt; fp.d = d; fp.rows_per_wg = pl.panel; fp.segs = pl.segs;
-        fp.n_lists = (int64_t)grid * pl.panel; fp.qres2 = qres2; fp.xstat = idx->xn2max_dev; fp.prefilter = final_prefilter_on();
+        fp.n_lists = (int64_t)grid * pl.panel; fp.qres2 = qres2; fp.xstat = xstat; fp.prefilter = final_prefilter_on();
         for (int t0 = 0; t0 < pl.n_tiles; t0 += pl.chunk_tiles) {
             const int t1 = (t0 + pl.chunk_tiles < pl.n_tiles) ? t0 + pl.chunk_tiles : pl.n_tiles;
             p.chunk_t0 = t0; p.chunk_t1 = t1; p.first_chunk = (t0 == 0); p.last_chunk = (t1 == pl.n_tiles);
@@ -2420,7 +2409,7 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
         }
         LEMON_HIP_CHECK(hipGetLastError());
         if (pl.splits > 1) {
-            rc = lemon_launch_merge(idx->ws_part, pl.splits, nullptr, nq_pad, cn, k, idx->metric, p.b.D, p.b.I, stream);
+            rc = lemon_launch_merge(part, pl.splits, nullptr, nq_pad, cn, k, idx->metric, p.b.D, p.b.I, stream);
             if (rc) return rc;
         }
         idx->last.algo = LEMON_ALGO_BF16_FILTER;

@@ -589,10 +589,12 @@ extern "C" int lemon_debug_scan_plan(int panels, int n_tiles, int *grid, int *sp
 // the plan of (panels, n_tiles) on the device: [grid + 1] segment offsets | [panels] pieces | pad to 4 ints | segments.
 // Four recent shapes are kept (least recently used slot replaced); the upload is ordered on the stream, so a launch
 // queued earlier that still reads the slot's old content finishes first, and the source vector lives in the slot.
-static int lemon_get_plan(lemon_index_t *idx, int panels, int n_tiles, hipStream_t stream, const lemon_index::PlanSlot **out) {
+static int lemon_get_plan(lemon_index_t *idx, int panels, int n_tiles, hipStream_t stream, const lemon_index::PlanSlot **out,
+                          const int **out_dev) {
     lemon_index::PlanSlot *hit = nullptr, *lru = &idx->plan_slots[0];
+    const auto dev_of = [idx](const lemon_index::PlanSlot *sl) { return lemon_index::PLAN0 + (int)(sl - idx->plan_slots); };
     for (auto &sl : idx->plan_slots) {
-        if (sl.dev && sl.panels == panels && sl.tiles == n_tiles) hit = &sl;
+        if (idx->buf[dev_of(&sl)].p && sl.panels == panels && sl.tiles == n_tiles) hit = &sl;
         if (sl.stamp < lru->stamp) lru = &sl;
     }
     if (!hit) {
@@ -607,23 +609,15 @@ static int lemon_get_plan(lemon_index_t *idx, int panels, int n_tiles, hipStream
         while (buf.size() % 4) buf.push_back(0);
         const int so = (int)buf.size();
         buf.insert(buf.end(), plan.segs.begin(), plan.segs.end());
-        if ((int64_t)buf.size() > lru->ints) {
-            LEMON_HIP_CHECK(hipStreamSynchronize(stream));             // an earlier launch may still read the old buffer
-            if (lru->dev) (void)hipFree(lru->dev);
-            lru->dev = nullptr; lru->ints = 0;
-            if (hipMalloc((void **)&lru->dev, buf.size() * sizeof(int)) != hipSuccess) {
-                lemon_set_error("scan plan allocation failed");
-                return LEMON_E_NOMEM;
-            }
-            lru->ints = (int64_t)buf.size();
-        }
-        LEMON_HIP_CHECK(hipMemcpyAsync(lru->dev, buf.data(), buf.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+        if (int rc = lemon_reserve(idx, dev_of(lru), buf.size() * sizeof(int), stream, "scan plan")) return rc;
+        LEMON_HIP_CHECK(hipMemcpyAsync(idx->buf[dev_of(lru)].p, buf.data(), buf.size() * sizeof(int), hipMemcpyHostToDevice, stream));
         lru->panels = panels; lru->tiles = n_tiles; lru->grid = plan.grid; lru->splits = plan.splits;
         lru->pieces_off = po; lru->segs_off = so;
         hit = lru;
     }
     hit->stamp = ++idx->plan_clock;
     *out = hit;
+    *out_dev = idx->at<int>(dev_of(hit));
     return LEMON_OK;
 }
 
@@ -634,40 +628,16 @@ int lemon_ensure_search_ws(lemon_index_t *idx, int64_t nq_pad, int splits, int64
     const int64_t cand_rows = n_wg * BQ * (cand_cap / CAP);         // in units of CAP-entry rows
     int64_t row_bytes = (int64_t)idx->dpad * 4 > qp_row_bytes ? (int64_t)idx->dpad * 4 : qp_row_bytes;
     if (row_bytes < idx->ws_qp_row_bytes) row_bytes = idx->ws_qp_row_bytes;
-    if (nq_pad > idx->ws_q || row_bytes > idx->ws_qp_row_bytes) {
-        const int64_t rows = nq_pad > idx->ws_q ? nq_pad : idx->ws_q;
-        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        if (idx->ws_qp) (void)hipFree(idx->ws_qp);
-        if (idx->ws_qnorm) (void)hipFree(idx->ws_qnorm);
-        idx->ws_qp = nullptr; idx->ws_qnorm = nullptr; idx->ws_q = 0; idx->ws_qp_row_bytes = 0;
-        if (hipMalloc(&idx->ws_qp, (size_t)rows * row_bytes) != hipSuccess ||
-            hipMalloc(&idx->ws_qnorm, (size_t)rows * 3 * sizeof(float)) != hipSuccess) {   // norms + bf16 residual stats
-            lemon_set_error("search workspace allocation failed (nq_pad=%lld)", (long long)nq_pad);
-            return LEMON_E_NOMEM;
-        }
-        idx->ws_q = rows; idx->ws_qp_row_bytes = row_bytes;
-    }
-    if (cand_rows > idx->ws_cand_rows) {
-        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        if (idx->ws_cand) (void)hipFree(idx->ws_cand);
-        idx->ws_cand = nullptr; idx->ws_cand_rows = 0;
-        if (hipMalloc(&idx->ws_cand, (size_t)cand_rows * CAP * sizeof(u64)) != hipSuccess) {
-            lemon_set_error("candidate workspace allocation failed (%lld rows)", (long long)cand_rows);
-            return LEMON_E_NOMEM;
-        }
-        idx->ws_cand_rows = cand_rows;
-    }
-    if (part_elems > idx->ws_part_elems) {
-        LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-        if (idx->ws_part) (void)hipFree(idx->ws_part);
-        idx->ws_part = nullptr; idx->ws_part_elems = 0;
-        if (hipMalloc(&idx->ws_part, (size_t)part_elems * sizeof(u64)) != hipSuccess) {
-            lemon_set_error("merge workspace allocation failed");
-            return LEMON_E_NOMEM;
-        }
-        idx->ws_part_elems = part_elems;
-    }
-    return LEMON_OK;
+    const int64_t rows = nq_pad > idx->ws_q ? nq_pad : idx->ws_q;
+    int rc = lemon_reserve_group(idx, {{lemon_index::WS_QP, (size_t)rows * row_bytes},
+                                       {lemon_index::WS_QNORM, (size_t)rows * 3 * sizeof(float)}},   // norms + bf16 residual stats
+                                 stream, "search workspace");
+    idx->ws_q = rc ? 0 : rows;                           // (after a failed growth the next call sizes for itself alone)
+    idx->ws_qp_row_bytes = rc ? 0 : row_bytes;
+    if (rc) return rc;
+    rc = lemon_reserve(idx, lemon_index::WS_CAND, (size_t)cand_rows * CAP * sizeof(u64), stream, "candidate workspace");
+    if (rc) return rc;
+    return lemon_reserve(idx, lemon_index::WS_PART, (size_t)part_elems * sizeof(u64), stream, "merge workspace");
 }
 
 // queries are processed in chunks so that the workspace stays bounded (1 GiB of candidates)
@@ -741,8 +711,9 @@ static int lemon_search_f32_pass(lemon_index_t *idx, const float *q_dev, int64_t
         static const bool legacy = getenv("LEMON_SPLITS") != nullptr;   // tuning knob: (panel, split) rectangles, no plan
         const bool planned = !legacy && (int64_t)panels * n_tiles >= 2;
         const lemon_index::PlanSlot *plan = nullptr;
+        const int *plan_dev = nullptr;
         if (planned) {
-            const int prc = lemon_get_plan(idx, panels, n_tiles, stream, &plan);
+            const int prc = lemon_get_plan(idx, panels, n_tiles, stream, &plan, &plan_dev);
             if (prc) return prc;
             grid = (unsigned)plan->grid; splits = plan->splits; pieces_off = plan->pieces_off; segs_off = plan->segs_off;
         } else {
@@ -752,29 +723,31 @@ static int lemon_search_f32_pass(lemon_index_t *idx, const float *q_dev, int64_t
 
         int rc = lemon_ensure_search_ws(idx, nq_pad, splits, grid, dpad * 4, PAIR_CAP, stream);
         if (rc) return rc;
+        float *ws_qp = idx->at<float>(lemon_index::WS_QP), *ws_qnorm = idx->at<float>(lemon_index::WS_QNORM);
+        u64 *ws_part = idx->at<u64>(lemon_index::WS_PART);
         // permuted, zero-padded query panel (+ chain norms for L2)
-        LEMON_HIP_CHECK(hipMemsetAsync(idx->ws_qp, 0, (size_t)nq_pad * dpad * sizeof(float), stream));
-        rc = lemon_permute_rows(q_dev + c0 * d, cn, d, idx->ws_qp, dpad, stream);
+        LEMON_HIP_CHECK(hipMemsetAsync(ws_qp, 0, (size_t)nq_pad * dpad * sizeof(float), stream));
+        rc = lemon_permute_rows(q_dev + c0 * d, cn, d, ws_qp, dpad, stream);
         if (rc) return rc;
         if (idx->metric == LEMON_METRIC_L2) {
-            LEMON_HIP_CHECK(hipMemsetAsync(idx->ws_qnorm, 0, (size_t)nq_pad * sizeof(float), stream));
-            rc = lemon_rowdot_chain(q_dev + c0 * d, q_dev + c0 * d, cn, d, idx->ws_qnorm, stream);
+            LEMON_HIP_CHECK(hipMemsetAsync(ws_qnorm, 0, (size_t)nq_pad * sizeof(float), stream));
+            rc = lemon_rowdot_chain(q_dev + c0 * d, q_dev + c0 * d, cn, d, ws_qnorm, stream);
             if (rc) return rc;
         }
         ScanParams p;
-        p.qp = idx->ws_qp; p.xp = idx->xp; p.qnorm = idx->ws_qnorm; p.xnorm = idx->xnorm;
-        p.cand = idx->ws_cand; p.part = idx->ws_part;
+        p.qp = ws_qp; p.xp = idx->xp; p.qnorm = ws_qnorm; p.xnorm = idx->xnorm;
+        p.cand = idx->at<u64>(lemon_index::WS_CAND); p.part = ws_part;
         p.D = D_dev + c0 * k; p.I = I_dev + c0 * k;
         p.nq = cn; p.n = idx->n; p.dpad = dpad; p.kk = k; p.metric = idx->metric;
         p.n_tiles = n_tiles; p.tiles_per_split = tiles_per_split; p.splits = splits; p.nq_pad = nq_pad;
-        p.plan = planned ? plan->dev : nullptr; p.plan_segs = segs_off; p.phase_dbg = nullptr;
+        p.plan = plan_dev; p.plan_segs = segs_off; p.phase_dbg = nullptr;
         p.ub = ub_dev ? ub_dev + c0 : nullptr;
         // shared admission bounds: one order-encoded float per query, in the tail of the norm workspace ([ws_q, 3] floats:
         // norms, then two spare columns), zeroed per launch; only when a panel really is scanned by several workgroups
         static const bool share = [] { const char *e = getenv("LEMON_SHARE_BOUNDS"); return !(e && e[0] == '0'); }();
         p.th_pub = nullptr;
         if (share && splits > 1) {
-            p.th_pub = reinterpret_cast<unsigned *>(idx->ws_qnorm + 2 * idx->ws_q);
+            p.th_pub = reinterpret_cast<unsigned *>(ws_qnorm + 2 * idx->ws_q);
             LEMON_HIP_CHECK(hipMemsetAsync(p.th_pub, 0, (size_t)nq_pad * sizeof(unsigned), stream));
         }
         // diagnostic instantiation only (LEMON_PHASE_PROF): 1 no operand loads, 2 no barriers, 4 filter off after 5 tiles,
@@ -827,7 +800,7 @@ static int lemon_search_f32_pass(lemon_index_t *idx, const float *q_dev, int64_t
         }
         LEMON_HIP_CHECK(hipGetLastError());
         if (splits > 1) {
-            rc = lemon_launch_merge(idx->ws_part, splits, planned ? plan->dev + pieces_off : nullptr, nq_pad, cn, k, idx->metric, p.D,
+            rc = lemon_launch_merge(ws_part, splits, planned ? plan_dev + pieces_off : nullptr, nq_pad, cn, k, idx->metric, p.D,
                                     p.I, stream);
             if (rc) return rc;
         }

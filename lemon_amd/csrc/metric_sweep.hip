@@ -89,18 +89,15 @@ __global__ __launch_bounds__(64 * L2IP_WAVES) void k_l2_from_ip(L2ipParams p) {
 // the stored norms' range, reduced once per index content (every add changes n)
 int norm_range(lemon_index_t *idx, hipStream_t stream) {
     if (idx->xnrange_rows == idx->n + 1) return LEMON_OK;
-    if (!idx->xnrange_dev && hipMalloc(&idx->xnrange_dev, 8) != hipSuccess) {
-        idx->xnrange_dev = nullptr;
-        lemon_set_error("norm range allocation failed");
-        return LEMON_E_NOMEM;
-    }
+    int rc = lemon_reserve(idx, lemon_index::XNRANGE, 8, stream, "norm range");
+    if (rc) return rc;
+    unsigned *range = idx->at<unsigned>(lemon_index::XNRANGE);
     // FLT_MAX, +0: what an empty index keeps
-    LEMON_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)idx->xnrange_dev, 0x7f7fffff, 1, stream));
-    LEMON_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(idx->xnrange_dev + 1), 0, 1, stream));
+    LEMON_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)range, 0x7f7fffff, 1, stream));
+    LEMON_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(range + 1), 0, 1, stream));
     if (idx->n > 0) {
         const int64_t blocks = (idx->n + 255) / 256;
-        hipLaunchKernelGGL(k_norm_range, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), 0, stream, idx->xnorm, idx->n,
-                           idx->xnrange_dev);
+        hipLaunchKernelGGL(k_norm_range, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), 0, stream, idx->xnorm, idx->n, range);
         LEMON_HIP_CHECK(hipGetLastError());
     }
     idx->xnrange_rows = idx->n + 1;
@@ -113,31 +110,12 @@ int derive(lemon_index_t *idx, const float *qq, int64_t nq, const float *D_ip, c
     int rc = norm_range(idx, stream);
     if (rc) return rc;
     L2ipParams p;
-    p.s = D_ip; p.ids = I_ip; p.qq = qq; p.xx = idx->xnorm; p.xrange = idx->xnrange_dev;
+    p.s = D_ip; p.ids = I_ip; p.qq = qq; p.xx = idx->xnorm; p.xrange = idx->at<unsigned>(lemon_index::XNRANGE);
     p.n = idx->n; p.nq = nq; p.kd = kd; p.k = k; p.D = D_l2; p.I = I_l2; p.cert = cert;
     const int64_t blocks = (nq + L2IP_WAVES - 1) / L2IP_WAVES;
     LEMON_REQUIRE(blocks <= 0x7fffffff, "nq < 2^33");
     hipLaunchKernelGGL(k_l2_from_ip, dim3((unsigned)blocks), dim3(64 * L2IP_WAVES), 0, stream, p);
     LEMON_HIP_CHECK(hipGetLastError());
-    return LEMON_OK;
-}
-
-// the neighbour workspace of an index (ws_D / ws_I, shared with lemon_neighbors and lemon_discrepancy) at `need` elements:
-// the first larger call synchronises and allocates, later calls only enqueue
-int grow_nb(lemon_index_t *idx, int64_t need, hipStream_t stream) {
-    if (need <= idx->ws_nb) return LEMON_OK;
-    LEMON_HIP_CHECK(hipStreamSynchronize(stream));
-    if (idx->ws_D) (void)hipFree(idx->ws_D);
-    if (idx->ws_I) (void)hipFree(idx->ws_I);
-    idx->ws_D = nullptr; idx->ws_I = nullptr; idx->ws_nb = 0;
-    if (hipMalloc(&idx->ws_D, (size_t)need * sizeof(float)) != hipSuccess ||
-        hipMalloc(&idx->ws_I, (size_t)need * sizeof(int64_t)) != hipSuccess) {
-        if (idx->ws_D) (void)hipFree(idx->ws_D);
-        idx->ws_D = nullptr;
-        lemon_set_error("metric sweep workspace allocation failed");
-        return LEMON_E_NOMEM;
-    }
-    idx->ws_nb = need;
     return LEMON_OK;
 }
 
@@ -154,9 +132,9 @@ extern "C" int lemon_index_l2_from_ip(lemon_index_t *idx, const float *q_dev, in
     LEMON_REQUIRE(q_dev && D_ip_dev && I_ip_dev && D_l2_dev && I_l2_dev && cert_dev, "null pointer");
     LEMON_REQUIRE(rows_vector_safe(q_dev, idx->d), "q_dev must be 16-byte aligned when d % 4 == 0");
     if (nq == 0) return LEMON_OK;
-    int rc = grow_nb(idx, nq, stream);                   // qq [nq] lives at the front of the neighbour workspace
+    int rc = lemon_reserve_nb(idx, nq, stream);          // qq [nq] lives at the front of the neighbour workspace
     if (rc) return rc;
-    float *qq = idx->ws_D;
+    float *qq = idx->at<float>(lemon_index::WS_D);
     rc = lemon_rowdot_chain(q_dev, q_dev, nq, idx->d, qq, stream);
     if (rc) return rc;
     return derive(idx, qq, nq, D_ip_dev, I_ip_dev, kd, k, D_l2_dev, I_l2_dev, cert_dev, stream);
@@ -186,32 +164,20 @@ extern "C" int lemon_neighbors_metrics(lemon_index_t *idx_img, lemon_index_t *id
     float *const l2_f32[7] = {d1_l2_dev, D_n_l2_dev, dists_n_l2_dev, dists_tr_n_l2_dev, D_m_l2_dev, dists_m_l2_dev, dists_tr_m_l2_dev};
     int64_t *const ip_i64[2] = {I_n_dev, I_m_dev}, *const l2_i64[2] = {I_n_l2_dev, I_m_l2_dev};
     hipStream_t stream = (hipStream_t)stream_;
-    LEMON_REQUIRE(idx_img && idx_txt, "index handles");
-    LEMON_REQUIRE(idx_img->metric == LEMON_METRIC_IP && idx_txt->metric == LEMON_METRIC_IP, "both indices must be IndexFlatIP");
-    LEMON_REQUIRE(idx_img->d == idx_txt->d && idx_img->n == idx_txt->n, "image and text index must agree in d and ntotal");
-    LEMON_REQUIRE(nq >= 0 && margin >= 0, "nq >= 0, margin >= 0");
-    const int ks = k + (drop_self ? 1 : 0);
-    LEMON_REQUIRE(k >= 1 && ks <= LEMON_MAX_K, "1 <= k, k + drop_self <= LEMON_MAX_K");
-    LEMON_REQUIRE(cert_n_dev && cert_m_dev, "null pointer");
+    const TwoSided c = {idx_img, idx_txt, q_img_dev, q_txt_dev, nq, k, drop_self, discrete, in_db_dev, tr_label_id_dev, q_label_id_dev};
+    LEMON_REQUIRE(!idx_img || !idx_txt || (idx_img->metric == LEMON_METRIC_IP && idx_txt->metric == LEMON_METRIC_IP),
+                  "both indices must be IndexFlatIP");
+    int rc = lemon_two_sided_check(c);
+    if (rc) return rc;
+    LEMON_REQUIRE(margin >= 0, "margin >= 0");
+    LEMON_REQUIRE(cert_n_dev && cert_m_dev && dists_tr_ip_dev && dists_tr_l2_dev, "null pointer");
     for (int t = 0; t < 7; ++t) LEMON_REQUIRE(ip_f32[t] && l2_f32[t], "null pointer");
-    LEMON_REQUIRE(dists_tr_ip_dev && dists_tr_l2_dev && q_img_dev && q_txt_dev, "null pointer");
-    LEMON_REQUIRE(!discrete || (tr_label_id_dev && q_label_id_dev), "label ids required when discrete");
-    LEMON_REQUIRE(rows_vector_safe(q_img_dev, idx_img->d) && rows_vector_safe(q_txt_dev, idx_img->d),
-                  "q_img_dev and q_txt_dev must be 16-byte aligned when d % 4 == 0");
-    if (nq == 0) return LEMON_OK;
-    const int kd = ks + margin < LEMON_MAX_K ? ks + margin : LEMON_MAX_K;
-    // the image index's neighbour workspace: IP lists [2][nq, kd] | L2 lists [2][nq, ks] | qq [2][nq] (ws_D only)
-    int rc = grow_nb(idx_img, 2 * nq * (kd + ks) + 2 * nq, stream);
-    if (rc) return rc;
-    float *Dn = idx_img->ws_D, *Dm = Dn + nq * kd, *Ln = Dm + nq * kd, *Lm = Ln + nq * ks, *qqv = Lm + nq * ks, *qqt = qqv + nq;
-    int64_t *In = idx_img->ws_I, *Im = In + nq * kd, *Jn = Im + nq * kd, *Jm = Jn + nq * ks;
-    const int img_dedup = idx_img->qdedup;               // de-duplication on the text side only, as in lemon_neighbors
-    idx_img->qdedup = 0;
-    rc = lemon_search_internal(idx_img, q_img_dev, nq, kd, Dn, In, stream);
-    idx_img->qdedup = img_dedup;
-    if (rc) return rc;
-    rc = lemon_search_internal(idx_txt, q_txt_dev, nq, kd, Dm, Im, stream);
-    if (rc) return rc;
+    const int ks = k + (drop_self ? 1 : 0), kd = ks + margin < LEMON_MAX_K ? ks + margin : LEMON_MAX_K;
+    // the image index's neighbour workspace: IP lists [2][nq, kd] | L2 lists [2][nq, ks] | qq [2][nq] (WS_D only)
+    rc = lemon_two_sided_search(c, kd, 2 * nq * (kd + ks) + 2 * nq, stream);
+    if (rc || nq == 0) return rc;
+    float *Dn = idx_img->at<float>(lemon_index::WS_D), *Dm = Dn + nq * kd, *Ln = Dm + nq * kd, *Lm = Ln + nq * ks, *qqv = Lm + nq * ks, *qqt = qqv + nq;
+    int64_t *In = idx_img->at<int64_t>(lemon_index::WS_I), *Im = In + nq * kd, *Jn = Im + nq * kd, *Jm = Jn + nq * ks;
     const int d = idx_img->d;
     if ((rc = lemon_rowdot_chain(q_img_dev, q_img_dev, nq, d, qqv, stream))) return rc;
     if ((rc = lemon_rowdot_chain(q_txt_dev, q_txt_dev, nq, d, qqt, stream))) return rc;
@@ -220,17 +186,13 @@ extern "C" int lemon_neighbors_metrics(lemon_index_t *idx_img, lemon_index_t *id
     for (int m = 0; m < 2; ++m) {                        // 0: cosine from the IP lists' prefix, 1: euclidean from the derived lists
         float *const *f = m ? l2_f32 : ip_f32;
         int64_t *const *ix = m ? l2_i64 : ip_i64;
-        const int metric = m ? LEMON_METRIC_L2 : LEMON_METRIC_IP;
-        if ((rc = lemon_paired_distance(metric, q_img_dev, q_txt_dev, nq, d, f[0], stream))) return rc;
-        NbParams p;
-        p.img_tr = idx_img->x; p.txt_tr = idx_txt->x; p.dists_tr = m ? dists_tr_l2_dev : dists_tr_ip_dev;
-        p.q_img = q_img_dev; p.q_txt = q_txt_dev;
+        NbParams p = lemon_nb_params(c);
+        p.metric = m ? LEMON_METRIC_L2 : LEMON_METRIC_IP;
+        if ((rc = lemon_paired_distance(p.metric, q_img_dev, q_txt_dev, nq, d, f[0], stream))) return rc;
+        p.dists_tr = m ? dists_tr_l2_dev : dists_tr_ip_dev; p.ks = m ? ks : kd;
         p.Dn = m ? Ln : Dn; p.Dm = m ? Lm : Dm; p.In = m ? Jn : In; p.Im = m ? Jm : Im;
-        p.in_db = in_db_dev; p.tr_lab = tr_label_id_dev; p.q_lab = q_label_id_dev;
         p.D_n = f[1]; p.dists_n = f[2]; p.dists_tr_n = f[3]; p.D_m = f[4]; p.dists_m = f[5]; p.dists_tr_m = f[6];
         p.I_n = ix[0]; p.I_m = ix[1];
-        p.nq = nq; p.d = d; p.k = k; p.ks = m ? ks : kd; p.metric = metric;
-        p.drop_self = drop_self; p.discrete = discrete;
         if ((rc = lemon_neighbors_finalize(p, stream))) return rc;
     }
     return LEMON_OK;

@@ -383,3 +383,50 @@ def test_every_entry_point_on_a_side_stream(hip, oracle, metric):
         fx.assert_outranked(got[name + "_dirty"], got[name + "_D"], metric, n)
         fx.assert_equals_oracle(oracle, metric, X, q, k, got[name + "_D"], got[name + "_I"])
     assert bool((got["nb_dirty"][:, -1] < got["nb_D_n"][:, 0]).all())
+
+
+# ---- 10. the two-sided search and the image handle's de-duplication setting ------------------------------------------------------
+def _distinct(ix):
+    return ix.last_search_info()["nq_distinct"]
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_two_sided_search_leaves_the_image_handles_dedup_setting_alone(hip, oracle, metric):
+    """LemonDB.neighbors and neighbors_metrics never fold the image side, and say so in the call: at nq = 1024 (the smallest
+    count at which folding is attempted) with 4 distinct image and 8 distinct text queries the image handle searches all nq
+    rows and the text handle 8, whatever the image handle's own setting is -- and that setting is the same after the call"""
+    rng = np.random.default_rng(97)
+    d, n, nq, k = 32, 512, 1024, 5
+    data = dict(img=fx.make_db(rng, n, d, metric), txt=fx.make_db(rng, n, d, metric), lab=rng.integers(0, 10, n).astype(np.int32))
+    s = dict(q_img=fx.repeated(rng, fx.make_queries(rng, 4, d, metric), nq), q_txt=fx.repeated(rng, fx.make_queries(rng, 8, d, metric), nq),
+             q_lab=rng.integers(0, 10, nq).astype(np.int32), in_db=np.zeros(nq, np.uint8))
+    assert (fx.n_distinct(s["q_img"]), fx.n_distinct(s["q_txt"])) == (4, 8)
+    q_img, q_txt = cu(s["q_img"]), cu(s["q_txt"])
+    want = new_index(hip, metric, d, F32, data["img"], dedup=False).search(q_img, k)
+
+    def direct_search(db, folded):
+        """the image queries on the image handle itself: folded or not as the handle's own setting says"""
+        D, I = db.index_img.search(q_img, k)
+        assert _distinct(db.index_img) == (4 if folded else nq)
+        assert bits_equal(D, want[0]) and bits_equal(I, want[1])
+
+    reused = hip.LemonDB(cu(data["img"]), cu(data["txt"]), metric, tr_label_id=data["lab"], algo=F32)
+    for setting in (True, False):
+        reused.index_img.set_query_dedup(setting)
+        _checked_record(hip, oracle, reused, data, s, k, False, False, metric, F32)
+        assert (_distinct(reused.index_img), _distinct(reused.index_txt)) == (nq, 8)
+        direct_search(reused, setting)
+    if fx.is_l2(metric):
+        return
+    sweep = hip.LemonDB(cu(data["img"]), cu(data["txt"]), ("cosine", "euclidean"), tr_label_id=data["lab"], algo=F32)
+    fresh = hip.LemonDB(cu(data["img"]), cu(data["txt"]), ("cosine", "euclidean"), tr_label_id=data["lab"], algo=F32)
+    recs_want, _ = fresh.neighbors_metrics(q_img, q_txt, k)
+    for setting in (True, False):
+        sweep.index_img.set_query_dedup(setting)
+        _dirty_db(sweep, data, s, metric)
+        recs, _ = sweep.neighbors_metrics(q_img, q_txt, k)
+        assert (_distinct(sweep.index_img), _distinct(sweep.index_txt)) == (nq, 8)
+        for name in ("cosine", "euclidean"):
+            for key in REC_KEYS:
+                assert bits_equal(recs[name][key], recs_want[name][key]), (name, key)
+        direct_search(sweep, setting)
