@@ -5,7 +5,8 @@ Kernel level: float64 reference at the project's bar for this input distribution
 equality with the shipped fp32-arithmetic kernels at head_dim 64 (mode 2), the split output forms, poisoned buffers through the
 C ABI, batch independence, the switch.  GEMM level: the hand-written GEMM at the shapes of a 1280-wide tower (n-tile counts 5,
 15 and 20) with the recipe and bars of tests/test_gpu_gemm_forms.py.  Tower level: ViT-H/14-shaped towers against HF CLIPModel
-on the CPU with the SDPA fallback made to raise."""
+on the CPU with the SDPA fallback made to raise.  (Every tile and key-block edge at five head dims, stress input for the online
+softmax, the per-element bound and NaN neighbours: tests/test_gpu_attention_stream_edges.py.)"""
 import ctypes
 
 import pytest

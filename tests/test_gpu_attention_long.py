@@ -4,7 +4,9 @@ sequences beyond 288 tokens -- the 577 tokens of ViT-L/14@336, 1025 at 448 px, t
 
 Kernel level: float64 reference at the project's bar, bit equality with the one-workgroup kernels when forced onto 64 < L <= 288
 (lemon_attention_set_stream_min), the split output forms, poisoned buffers through the C ABI, batch independence, the limits.
-Tower level: a 336-px ViT-L/14 and a 512-token text tower against HF CLIP with the SDPA fallback made to raise."""
+Tower level: a 336-px ViT-L/14 and a 512-token text tower against HF CLIP with the SDPA fallback made to raise.
+(Every block edge from 289 to 577 tokens, stress input for the online softmax, the per-element bound and NaN neighbours:
+tests/test_gpu_attention_stream_edges.py.)"""
 import ctypes
 
 import numpy as np

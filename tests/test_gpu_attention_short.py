@@ -10,10 +10,14 @@ tile count TJ = ceil(L / 32) = 1 .. 9, on the last row of a tile, one short of i
   e. NaN / Inf neighbours in memory (the next batch element, the bytes around the operand) cannot reach a result
   f. limits
 
-Worst |got - ref| / bound of (a), C = 2, per kernel and arithmetic (1.0 = the bound): NOT MEASURED yet -- test (a) prints
-them, one "attention_short ratio | kernel | ..." line per case and family (pytest -s).  On the CPU a plain fp32 evaluation reaches
-0.32 and the emulation of the split arithmetic 0.44 (tests/test_attention_bound_host.py).  Wall time of this file on an MI355X:
-not measured yet."""
+Worst |got - ref| / bound of (a), C = 2, per kernel and arithmetic (1.0 = the bound), one MI355X run (a record, not a threshold;
+test (a) prints them, one "attention_short ratio | kernel | ..." line per case and family, pytest -s):
+  k_attention_hd64_short<1|2>  fp32 / split-fp16     0.167 / 0.160  (L 63 causal, offset)
+  k_attention_hd64<false>      fp32                  0.395  (L 224 causal, offset)
+  k_attention_hd64_f16 (staged) and k_attention_hd64<true> (first general fp16)   0.480  (L 255 causal, tail_v)
+On the CPU a plain fp32 evaluation reaches 0.32 and the emulation of the split arithmetic 0.44
+(tests/test_attention_bound_host.py).  Wall time of this file on an MI355X: 4.3 s for its 409 cases.  The streaming kernels
+beyond 288 tokens and the head dims beyond 64: tests/test_gpu_attention_stream_edges.py."""
 import ctypes
 
 import pytest
