@@ -143,6 +143,10 @@ class KMeans:
             raise ValueError(f"{n} points cannot seed {self.n_clusters} clusters")
         if d % 4 or not 4 <= d <= MAX_DIM:
             raise ValueError(f"the embedding width must be a multiple of 4 in [4, {MAX_DIM}], got {d}")
+        # a NaN row is at "distance 0" from every centroid (the key clamps with dd > 0 ? dd : 0), joins cluster 0 and turns
+        # its mean into NaN, which then attracts every point: refuse here, as raise_if_nonfinite does on the dataset path
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError("KMeans.fit: the input holds non-finite values (NaN or Inf)")
         rows = subsample_rows(n, self.n_clusters, self.max_points_per_centroid, self.seed)
         if rows is not None:
             x = x[torch.from_numpy(rows).to(x.device)].contiguous()
