@@ -452,7 +452,8 @@ int lemon_index_profile_read(lemon_index_t *idx, int64_t *launches, double *kern
                              double *algo_flops, double *algo_bytes);
 
 /* Host-only view of how the exact scan (LEMON_ALGO_F32_MFMA) decomposes `panels` query panels (128 queries each) x
- * `n_tiles` database tiles (128 rows each) over its workgroups: for tests and tools, no device is touched.
+ * `n_tiles` database tiles (128 rows each) over its workgroups: for tests and tools, no device is touched (the plan is that
+ * of a device of 256 CUs, under the LEMON_XCDS / LEMON_SEG_COST of the environment at the time of the call).
  *   seg_begin [*grid + 1]  first segment of every workgroup (cap_wgs + 1 ints of room)
  *   pieces    [panels]     pieces the panel is scanned in (what the merge combines)
  *   segs      [4 * *n_segs] (panel, first tile, tiles, piece number inside the panel) per segment (cap_segs segments of room)

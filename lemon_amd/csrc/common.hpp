@@ -84,10 +84,11 @@ struct lemon_index {
     int64_t xnrange_rows; // 1 + the n XNRANGE was reduced at (0: never), so every add makes it stale
     int64_t ws_q;         // query rows WS_QP / WS_QNORM are sized for (the stride of WS_QNORM's three columns)
     int64_t ws_qp_row_bytes;  // bytes per staged query row WS_QP is sized for
-    // fp32 scan: segment plans on the device (knn_f32.hip), a few recent (panels, tiles) shapes -- a pipeline alternates
-    // between its train / val / test query counts.  `host` keeps the upload's source alive (stream-ordered copy).
+    // fp32 scan: segment plans on the device (knn_f32.hip), a few recent ones -- a pipeline alternates between its train /
+    // val / test query counts -- under all the segment planner reads: the (panels, tiles) shape, the resident slots and
+    // the two knobs.  `host` keeps the upload's source alive (stream-ordered copy).
     struct PlanSlot {
-        int panels, tiles, grid, splits, pieces_off, segs_off;
+        int panels, tiles, slots, xcds, seg_cost, grid, splits, pieces_off, segs_off;
         unsigned long long stamp; std::vector<int> *host;
     } plan_slots[4];
     unsigned long long plan_clock;

@@ -2289,15 +2289,6 @@ static int final_prefilter_on() {
     return on;
 }
 
-static int device_cus() {
-    static const int cus = [] {
-        int dev = 0, c = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-        return c > 0 ? c : 256;
-    }();
-    return cus;
-}
-
 // the instantiation that serves (kernel, kt = pitch / 64, metric), nullptr where there is none
 typedef void (*scan_kernel_t)(ScanParamsH);
 static scan_kernel_t scan_kernel(plan::Kernel kernel, int kt, bool l2) {
@@ -2356,7 +2347,7 @@ int lemon_search_bf16(lemon_index_t *idx, const float *q_dev, int64_t nq, int k,
     plan::Plan pl;
     pl.kernel = plan::SCAN_BF16; pl.cn = 0;
     for (int64_t c0 = 0; c0 < nq; c0 += pl.cn) {
-        pl = plan::plan_chunk(nq - c0, c0 == 0, pl.kernel, idx->n, d, dpad_h, l2, idx->wide_filter != 0, device_cus(), knobs);
+        pl = plan::plan_chunk(nq - c0, c0 == 0, pl.kernel, idx->n, d, dpad_h, l2, idx->wide_filter != 0, lemon_device_cus(), knobs);
         const int64_t cn = pl.cn, nq_pad = (int64_t)pl.panels * pl.panel;
         const unsigned grid = (unsigned)(pl.panels * pl.splits);
         const bool stationary = pl.kernel != plan::SCAN_BF16;   // lane lists, chunked launches, k_bf16_final

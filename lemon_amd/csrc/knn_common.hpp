@@ -59,11 +59,14 @@ struct ScanParams {
     int dpad, kk, metric;
     int n_tiles, tiles_per_split, splits;
     int64_t nq_pad;
-    unsigned long long *phase_dbg;   // diagnostic instantiation only: 4 cycle sums
-    int ablate;           // diagnostic instantiation only: 1 = no operand loads, 2 = no barriers (results invalid)
+    // reserved8 / reserved4: where the pointer and the bits of a retired diagnostic form sat, never read.  They keep the layout
+    // (kernarg offsets and size): without them hipcc merges the argument loads of every scan kernel differently and
+    // assigns other SGPRs, a code-generation change that only a timing on the GPU could clear
+    unsigned long long reserved8;
+    int reserved4;
     int stale;            // new entries per query that trigger a re-selection (fp32 scan)
     int fair;             // fp32 scan: the co-resident workgroups of a CU take turns at the higher issue priority
-    const int *plan;      // planned decomposition (knn_f32.hip, lemon_plan_segments): [grid + 1] first segment of every
+    const int *plan;      // planned decomposition (scan_plan.hpp, lemon_plan_segments_host): [grid + 1] first segment of every
                           // workgroup, ..., then at int offset plan_segs the segments (panel, first tile, tiles, piece);
                           // nullptr: one (panel, split) rectangle per workgroup.  splits = max pieces per panel
     int plan_segs;
@@ -300,7 +303,7 @@ int lemon_permute_rows(const float *src, int64_t n, int d, float *dst, int dpad,
 int lemon_launch_merge(const u64 *part, int splits, const int *pieces, int64_t nq_pad, int64_t nq, int kk, int metric, float *D,
                        int64_t *I, hipStream_t stream);
 int lemon_fill_empty(float *D, int64_t *I, int64_t total, int metric, hipStream_t stream);
-void lemon_plan_splits(int panels, int n_tiles, int *splits, int *tiles_per_split);
+int lemon_device_cus();   // CUs of the device that was current at the first search of the process (256 where that cannot be asked)
 int lemon_ensure_search_ws(lemon_index_t *idx, int64_t nq_pad, int splits, int64_t n_wg, int qp_row_bytes, int cand_cap,
                            hipStream_t stream);
 // LEMON_ABLATE (diagnostics): the value must be a combination of the bits `allowed` names for this kernel, anything else

@@ -1,7 +1,7 @@
 // knn_f32.hip -- exact brute-force top-k scan on the fp32 matrix cores of gfx950.
 //
 // Stands in for faiss IndexFlat{IP,L2}.search as called at run_lemon.py:235-236.
-// A workgroup works through SEGMENTS (lemon_plan_segments): a panel of BQ=128 queries against a contiguous range of
+// A workgroup works through SEGMENTS (scan_plan.hpp): a panel of BQ=128 queries against a contiguous range of
 // database tiles (BX=128 rows) streamed through LDS; S = Q.X^T is accumulated by v_mfma_f32_32x32x2_f32 in
 // ascending k, which is bit-for-bit the float32 fmaf chain of the numeric contract, so the
 // scores (and therefore the selected sets, given the index tie rule) are identical to the CPU
@@ -17,11 +17,12 @@
 // workgroups that walk the same tiles in step.
 #include "knn_common.hpp"
 #include "scan_plan.hpp"
-#include "knn_bf16_plan.hpp"
 #include <algorithm>
 #include <vector>
 
 using namespace lemon_knn;
+namespace splan = lemon_f32_plan;
+static_assert(splan::BQ == BQ && splan::BX == BX, "scan_plan.hpp mirrors the scan geometry");
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -101,13 +102,8 @@ __device__ __forceinline__ void f32_filter_tile(f32x16 a, float th, unsigned jb,
 // One workgroup = 128 queries x a range of 128-row database tiles.  Wave w owns queries 32w..32w+31
 // (B operand, one query per lane pair) against all 128 rows of the tile (A operand, 4 row tiles):
 // acc_i[e] = <x_(32i + (e&3) + 8(e>>2) + 4h), q_(32w + lane&31)> accumulated in ascending k.
-template <bool L2, bool PROF, bool UB = false>
+template <bool L2, bool UB>
 __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
-    // diagnostic instantiation: per-phase cycle sums of wave 0 (loop incl. barriers, filter, maintenance, final)
-    unsigned long long ts = 0, ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0;
-#define PH_STAMP(acc) do { if (PROF) { unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - ts; ts = now_; } } while (0)
-    unsigned long long clk0 = 0, rt0 = 0;
-    if (PROF) { ts = __builtin_amdgcn_s_memtime(); clk0 = ts; rt0 = __builtin_amdgcn_s_memrealtime(); }
     __shared__ __attribute__((aligned(16))) float s_tile[2][2][BQ * BK];  // [buf][Q|X][row*32+..] 64 KiB
     __shared__ __attribute__((aligned(16))) u64 s_keys[NT / 64][256];    // rank-merge scratch, one per wave
     const int tid = threadIdx.x;
@@ -116,8 +112,8 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
     const int l31 = lane & 31, h = lane >> 5;
 
     // work of this workgroup: a run of SEGMENTS = (panel, first tile, tiles, piece number inside the panel).  With a plan
-    // (lemon_plan_segments: equal unit counts per workgroup, XCD-aware, see there) they come from a table; without one
-    // (LEMON_SPLITS) the workgroup is one (panel, split) rectangle.
+    // (lemon_plan_segments_host, scan_plan.hpp: equal unit counts per workgroup, XCD-aware, see there) they come from a
+    // table; without one (LEMON_SPLITS) the workgroup is one (panel, split) rectangle.
     int seg = 0, seg_end = 1;
     if (p.plan) { seg = p.plan[blockIdx.x]; seg_end = p.plan[blockIdx.x + 1]; }
     // Fair shares of the matrix pipe.  The two wavefronts of a SIMD (one from each co-resident workgroup) both have MFMAs
@@ -256,15 +252,11 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
         F32_FRAG(fb, BUF, 1); F32_WAIT(fa, 5);                                                         \
         if (FIRST) F32_MFMA_F(fa, true); else F32_MFMA_F(fa, false);                                   \
         F32_FRAG(fa, BUF, 2); F32_WAIT(fb, 5); F32_MFMA_F(fb, false);                                  \
-        if (!abl_ld) {                                                                                 \
-            F32_COMMIT(SET, (BUF) ^ 1);                                                                \
-            F32_ISSUE(SET);                                                                            \
-            F32_FRAG(fb, BUF, 3); F32_WAIT(fa, 13);                                                    \
-        } else {                                                                                       \
-            F32_FRAG(fb, BUF, 3); F32_WAIT(fa, 5);                                                     \
-        }                                                                                              \
+        F32_COMMIT(SET, (BUF) ^ 1);                                                                    \
+        F32_ISSUE(SET);                                                                                \
+        F32_FRAG(fb, BUF, 3); F32_WAIT(fa, 13);                                                        \
         F32_MFMA_F(fa, false);                                                                         \
-        if (!abl_bar) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(acc0), "+v"(acc1), "+v"(acc2), "+v"(acc3) : : "memory"); \
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(acc0), "+v"(acc1), "+v"(acc2), "+v"(acc3) : : "memory"); \
         F32_FRAG(fa, (BUF) ^ 1, 0); F32_WAIT(fb, 5); F32_MFMA_F(fb, false);                            \
     } while (0)
 
@@ -283,7 +275,6 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
     for (int e = 0; e < 16; ++e) zero16[e] = 0.0f;
     acc0 = zero16; acc1 = zero16; acc2 = zero16; acc3 = zero16;
 
-    const bool abl_ld = PROF && (p.ablate & 1), abl_bar = PROF && (p.ablate & 2);
     F32_ISSUE(a);                                // stage 0
     F32_ISSUE(b);                                // stage 1
     F32_COMMIT(a, 0);
@@ -301,10 +292,8 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
             // ---- epilogue: filter into the lane-private half-lists, then zero the accumulators ----
             // (raised issue priority: the other three waves of the workgroup wait at the barrier for this
             // one, while the co-resident workgroup's waves keep the MFMA pipe busy either way)
-            PH_STAMP(ph0);
             __builtin_amdgcn_s_setprio(3);
             const unsigned jb = (unsigned)(t_begin + jl) * BX + 4 * h;
-            const int ccnt_in = ccnt;
             if (p.th_pub) {
                 asm volatile("s_waitcnt vmcnt(16)" : "+v"(pub));
                 if (pub > 1u) th = fmaxf(th, lemon_ord2f(pub - 1u));   // strictly below the published bound
@@ -319,43 +308,13 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
                     if (j + 96 >= (unsigned)p.n) acc3[e] = -INFINITY;
                 }
             }
-            if (PROF && (p.ablate & 16)) {           // diagnostic: bit 4 = time the bare accumulator read-out (64-value max)
-                float mx = acc0[0];
-#pragma unroll
-                for (int e = 0; e < 16; ++e) mx = fmaxf(fmaxf(mx, acc0[e]), fmaxf(fmaxf(acc1[e], acc2[e]), acc3[e]));
-                if (mx == 123.456f) ph3 += 1;       // keep it alive
-                PH_STAMP(ph3);                       // reported in the 'final' column
-            }
-            if (PROF && (p.ablate & (32 | 128)) && jl > 4) {
-                // diagnostic: what does the co-resident MFMA stream cost an epilogue per instruction CLASS?  The filter is
-                // replaced by instructions of one kind: bit 5 = 512 VALU (4 independent chains; measured 12.7 cycles each
-                // instead of 4), bit 7 = 256 ballot + scalar-branch pairs (never taken)
-                float x0 = acc0[0], x1 = acc1[0], x2 = acc2[0], x3 = acc3[0];
-                                if (p.ablate & 32) {
-#pragma unroll 1
-                    for (int r = 0; r < 8; ++r)
-                        asm volatile(".rept 16\n\tv_add_f32 %0, %0, %4\n\tv_add_f32 %1, %1, %4\n\tv_add_f32 %2, %2, %4\n\tv_add_f32 %3, %3, %4\n\t.endr"
-                                     : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "v"(th));
-                } else {
-#pragma unroll 1
-                    for (int r = 0; r < 256; ++r) {
-                        if (__ballot(x0 > 3.0e38f)) x1 += 1.0f;     // v_cmp -> SGPR -> scalar branch, never taken
-                        asm volatile("" : "+v"(x0));
-                    }
-                }
-                if (x0 + x1 + x2 + x3 == 1.2345f) ph3 += 1;    // keep alive
-            } else
-            if (!(PROF && (p.ablate & 4) && jl > 4)) {     // diagnostic: bit 2 = skip the filter after 5 tiles
             f32_filter_tile<L2, UB>(acc0, th, jb, my_qn, p.xnorm, (unsigned)p.n, ccnt, panel_bytes, my_off, my_ub);
             f32_filter_tile<L2, UB>(acc1, th, jb + 32, my_qn, p.xnorm, (unsigned)p.n, ccnt, panel_bytes, my_off, my_ub);
             f32_filter_tile<L2, UB>(acc2, th, jb + 64, my_qn, p.xnorm, (unsigned)p.n, ccnt, panel_bytes, my_off, my_ub);
             f32_filter_tile<L2, UB>(acc3, th, jb + 96, my_qn, p.xnorm, (unsigned)p.n, ccnt, panel_bytes, my_off, my_ub);
-            }
-            if (PROF && (p.ablate & 8) && jl > 4) ccnt = ccnt_in;   // diagnostic: bit 3 = appends land but are forgotten
             ++jl;                                    // (the accumulators are not zeroed: the next tile's first MFMAs take C = 0)
 
             // ---- maintenance: select the exact top-kk of queries whose lists grew enough ----
-            PH_STAMP(ph1);
             const int pair = ccnt + __shfl_xor(ccnt, 32);
             const bool warm = th == -INFINITY && pair >= p.kk;   // no bound at all yet, own or imported
             const bool stale = pair >= p.kk && pair - clast >= p.stale;
@@ -385,7 +344,6 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
             // NEWEST load at its use, and the wait for it, vmcnt(0), drained the operand prefetch once per tile)
             F32_PUB_FETCH();
             F32_BASE_PRIO();
-            PH_STAMP(ph2);
         }
     }
     F32_WAIT(fa, 0);
@@ -398,7 +356,6 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
 #undef F32_ISSUE
 
     // ---- final: sort every query's best kk, write the result rows ------------------------------
-    PH_STAMP(ph0);
     F32_LANDED(a, 0); F32_LANDED(b, 0);                 // the loads issued past the end of the segment, and the appends
     asm volatile("" : "+v"(pub));
 #undef F32_LANDED
@@ -415,27 +372,8 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
                                      : pair_final_topk<true>(list, n0, n1, p.kk, lane, s_keys[wave], &pos);
         write_out_row(p, split, q, pos, key);
     }
-    PH_STAMP(ph3);
     __syncthreads();                                    // LDS tiles and lists are reused by the next segment
     }
-    if (PROF && tid == 0) {
-        atomicAdd(&p.phase_dbg[0], ph0); atomicAdd(&p.phase_dbg[1], ph1);
-        atomicAdd(&p.phase_dbg[2], ph2); atomicAdd(&p.phase_dbg[3], ph3);
-        const unsigned long long rt = __builtin_amdgcn_s_memrealtime() - rt0;   // this workgroup's life, 100 MHz ticks
-        if (blockIdx.x == 0) {
-            p.phase_dbg[4] = __builtin_amdgcn_s_memtime() - clk0;
-            p.phase_dbg[5] = rt;
-        }
-        // spread of the workgroups' lives, overall and by the parity of the wave slot wave 0 sits in (HW_ID[3:0]): the two
-        // workgroups of a CU share the matrix pipe, and an arbiter that prefers one of them shows up here
-        const unsigned slot = slot_parity;
-        atomicMax(&p.phase_dbg[6], rt);
-        atomicMin(&p.phase_dbg[7], rt);
-        atomicAdd(&p.phase_dbg[8 + 2 * slot], rt);
-        atomicAdd(&p.phase_dbg[9 + 2 * slot], 1ull);
-        if (blockIdx.x < 4096) p.phase_dbg[16 + blockIdx.x] = rt;
-    }
-#undef PH_STAMP
 #undef F32_BASE_PRIO
 }
 
@@ -537,47 +475,35 @@ int lemon_fill_empty(float *D, int64_t *I, int64_t total, int metric, hipStream_
     return LEMON_OK;
 }
 
-// (the rule itself is plain C++ in knn_bf16_plan.hpp, where the 16-bit scan's plan uses it too)
-void lemon_plan_splits(int panels, int n_tiles, int *splits_out, int *tiles_per_split_out) {
-    static const int forced = [] { const char *e = getenv("LEMON_SPLITS"); return e ? atoi(e) : 0; }();   // tuning knob
-    lemon_bf16_plan::plan_splits(panels, n_tiles, forced, splits_out, tiles_per_split_out);
-}
-
-// Planned ("stream-K", XCD-aware) decomposition of the fp32 scan.
-//
-// Balance.  One workgroup alone on a CU reaches well under the MFMA rate of two co-resident ones, so a grid that is not
-// a multiple of 2 x CUs pays a whole extra round (391 panels ran as slowly as 512).  Instead the panels x tiles unit
-// space is cut into equal shares, one per resident slot; a share that touches several panels yields one partial list per
-// panel touched and k_merge combines the pieces of a panel.
-//
-// Locality.  A workgroup re-streams its query panel (128 x d x 4 B) and streams a database tile of the same size per
-// unit; the 64 workgroups of an XCD move 32 MB per unit time through a 4 MB L2, so NOTHING hits unless workgroups read
-// the same tile at the same time.  With plain contiguous shares (round 1) the shares start at arbitrary tiles: at the
-// headline shape PMC FETCH_SIZE was 2.0 x the scan-model bytes and the launch ran at 0.80 of the MFMA peak, against
-// 0.89 at 262 144^2 where every share happens to be four whole panels walked from tile 0 in step.  So the shares are
-// built per XCD (workgroup b runs on XCD b % 8: round-robin dispatch; panel p belongs to XCD p % 8) and ALIGNED: with
-// u units per workgroup and T tiles per panel, T >= u: as many workgroups as the XCD has panels take tiles [0, u) of
-// one panel each -- they walk the same tiles in step -- and the other workgroups share the tails [u, T); T < u: every
-// workgroup first takes floor(u / T) whole panels (again from tile 0, in step), the rest is shared out.  A segment is
-// (panel, first tile, tiles, piece number in the panel); workgroup b owns segments plan[b] .. plan[b+1].
-// (the planner itself is plain C++ in scan_plan.hpp: it is also built with gcc under ASan / UBSan and fuzzed on the CPU)
-static void lemon_plan_segments(int panels, int n_tiles, LemonPlan &plan) {
-    static const int slots = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 2 * (cus > 0 ? cus : 256);
+int lemon_device_cus() {
+    static const int cus = [] {
+        int dev = 0, c = splan::CUS;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+        return c > 0 ? c : splan::CUS;
     }();
-    static const int xcds = [] { const char *e = getenv("LEMON_XCDS"); return e && atoi(e) > 0 ? atoi(e) : 8; }();   // 1 = not XCD-aware
-    static const int seg_cost = [] { const char *e = getenv("LEMON_SEG_COST"); return e ? atoi(e) : 3; }();   // tile times per segment
-    lemon_plan_segments_host(panels, n_tiles, slots, xcds, seg_cost, plan);
+    return cus;
 }
 
+// the knobs of scan_plan.hpp from the environment, read once per call (tests and tools set them between searches)
+static splan::Knobs read_scan_knobs() {
+    splan::Knobs kn;
+    if (const char *e = getenv("LEMON_SPLITS")) { kn.splits_set = true; kn.splits = atoi(e); }
+    if (const char *e = getenv("LEMON_XCDS")) if (atoi(e) > 0) kn.xcds = atoi(e);
+    if (const char *e = getenv("LEMON_SEG_COST")) kn.seg_cost = atoi(e);
+    if (const char *e = getenv("LEMON_SHARE_BOUNDS")) kn.share_bounds = e[0] != '0';
+    if (const char *e = getenv("LEMON_STALE")) if (atoi(e) > 0) kn.stale = atoi(e);
+    if (const char *e = getenv("LEMON_FAIR")) kn.fair = atoi(e);
+    return kn;
+}
+
+// (host only: the segment plan of a device of splan::CUS CUs under the environment's knobs)
 extern "C" int lemon_debug_scan_plan(int panels, int n_tiles, int *grid, int *splits, int *seg_begin, int cap_wgs, int *pieces,
                                      int *segs, int cap_segs, int *n_segs) {
     LEMON_REQUIRE(panels > 0 && n_tiles > 0, "panels, n_tiles > 0");
     LEMON_REQUIRE(grid && splits && seg_begin && pieces && segs && n_segs, "output pointers");
+    const splan::Knobs kn = read_scan_knobs();
     LemonPlan plan;
-    lemon_plan_segments(panels, n_tiles, plan);
+    lemon_plan_segments_host(panels, n_tiles, 2 * splan::CUS, kn.xcds, kn.seg_cost, plan);
     LEMON_REQUIRE(plan.grid <= cap_wgs && (int)(plan.segs.size() / 4) <= cap_segs, "plan fits the output buffers");
     *grid = plan.grid; *splits = plan.splits; *n_segs = (int)(plan.segs.size() / 4);
     std::copy(plan.seg_begin.begin(), plan.seg_begin.end(), seg_begin);
@@ -586,20 +512,23 @@ extern "C" int lemon_debug_scan_plan(int panels, int n_tiles, int *grid, int *sp
     return LEMON_OK;
 }
 
-// the plan of (panels, n_tiles) on the device: [grid + 1] segment offsets | [panels] pieces | pad to 4 ints | segments.
-// Four recent shapes are kept (least recently used slot replaced); the upload is ordered on the stream, so a launch
-// queued earlier that still reads the slot's old content finishes first, and the source vector lives in the slot.
-static int lemon_get_plan(lemon_index_t *idx, int panels, int n_tiles, hipStream_t stream, const lemon_index::PlanSlot **out,
+// the segment plan of a planned chunk on the device: [grid + 1] segment offsets | [panels] pieces | pad to 4 ints | segments.
+// Four recent plans are kept, under everything plan_segments reads (least recently used slot replaced); the upload is ordered
+// on the stream, so a launch queued earlier that still reads the slot's old content finishes first, and the source vector
+// lives in the slot.
+static int lemon_get_plan(lemon_index_t *idx, const splan::Chunk &c, hipStream_t stream, const lemon_index::PlanSlot **out,
                           const int **out_dev) {
     lemon_index::PlanSlot *hit = nullptr, *lru = &idx->plan_slots[0];
     const auto dev_of = [idx](const lemon_index::PlanSlot *sl) { return lemon_index::PLAN0 + (int)(sl - idx->plan_slots); };
     for (auto &sl : idx->plan_slots) {
-        if (idx->buf[dev_of(&sl)].p && sl.panels == panels && sl.tiles == n_tiles) hit = &sl;
+        if (idx->buf[dev_of(&sl)].p && sl.panels == c.panels && sl.tiles == c.n_tiles && sl.slots == c.slots && sl.xcds == c.xcds &&
+            sl.seg_cost == c.seg_cost)
+            hit = &sl;
         if (sl.stamp < lru->stamp) lru = &sl;
     }
     if (!hit) {
         LemonPlan plan;
-        lemon_plan_segments(panels, n_tiles, plan);
+        splan::plan_segments(c, plan);
         if (!lru->host) lru->host = new std::vector<int>();
         else LEMON_HIP_CHECK(hipStreamSynchronize(stream));            // the previous upload from this vector has completed
         std::vector<int> &buf = *lru->host;
@@ -611,8 +540,8 @@ static int lemon_get_plan(lemon_index_t *idx, int panels, int n_tiles, hipStream
         buf.insert(buf.end(), plan.segs.begin(), plan.segs.end());
         if (int rc = lemon_reserve(idx, dev_of(lru), buf.size() * sizeof(int), stream, "scan plan")) return rc;
         LEMON_HIP_CHECK(hipMemcpyAsync(idx->buf[dev_of(lru)].p, buf.data(), buf.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-        lru->panels = panels; lru->tiles = n_tiles; lru->grid = plan.grid; lru->splits = plan.splits;
-        lru->pieces_off = po; lru->segs_off = so;
+        lru->panels = c.panels; lru->tiles = c.n_tiles; lru->slots = c.slots; lru->xcds = c.xcds; lru->seg_cost = c.seg_cost;
+        lru->grid = plan.grid; lru->splits = plan.splits; lru->pieces_off = po; lru->segs_off = so;
         hit = lru;
     }
     hit->stamp = ++idx->plan_clock;
@@ -640,9 +569,6 @@ int lemon_ensure_search_ws(lemon_index_t *idx, int64_t nq_pad, int splits, int64
     return lemon_reserve(idx, lemon_index::WS_PART, (size_t)part_elems * sizeof(u64), stream, "merge workspace");
 }
 
-// queries are processed in chunks so that the workspace stays bounded (1 GiB of candidates)
-static const int64_t QCHUNK = 1 << 19;
-
 namespace {
 // k > LEMON_MAX_K: one pass's [nq, kp] block goes to columns [col0, col0+kp) of the [nq, k] result, and the key of its
 // last entry becomes the query's exclusive upper bound for the next pass (0 = the database is exhausted)
@@ -664,12 +590,85 @@ __global__ void k_fill_u64(u64 *p, int64_t n, u64 v) {
 }
 }  // namespace
 
+static void launch_scan_f32(bool l2, bool ub, unsigned grid, hipStream_t stream, const ScanParams &p) {
+    void (*const fn)(ScanParams) = ub ? (l2 ? k_scan_f32<true, true> : k_scan_f32<false, true>)
+                                      : (l2 ? k_scan_f32<true, false> : k_scan_f32<false, false>);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), 0, stream, p);
+}
+
+// one pass of at most LEMON_MAX_K results per query; ub_dev: the queries' exclusive upper key bounds, or nullptr
 static int lemon_search_f32_pass(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
-                                 const u64 *ub_dev, hipStream_t stream);
+                                 const u64 *ub_dev, const splan::Knobs &knobs, hipStream_t stream) {
+    const int d = idx->d, dpad = idx->dpad;
+    const bool l2 = idx->metric == LEMON_METRIC_L2;
+    if (idx->n == 0) return lemon_fill_empty(D_dev, I_dev, nq * k, idx->metric, stream);
+    int no_bits;        // the fp32 scan has no diagnostic form: a stray LEMON_ABLATE is refused, not ignored
+    int rc = lemon_parse_ablate("k_scan_f32", 0, &no_bits);
+    if (rc) return rc;
+    splan::Chunk c{};
+    for (int64_t c0 = 0; c0 < nq; c0 += c.cn) {
+        c = splan::plan_chunk(nq - c0, idx->n, d, lemon_device_cus(), knobs);
+        const lemon_index::PlanSlot *slot = nullptr;
+        const int *plan_dev = nullptr;
+        if (c.planned) {
+            rc = lemon_get_plan(idx, c, stream, &slot, &plan_dev);
+            if (rc) return rc;
+            splan::set_geometry(c, slot->grid, slot->splits);
+        }
+        rc = lemon_ensure_search_ws(idx, c.nq_pad, c.splits, c.grid, dpad * 4, PAIR_CAP, stream);
+        if (rc) return rc;
+        float *ws_qp = idx->at<float>(lemon_index::WS_QP), *ws_qnorm = idx->at<float>(lemon_index::WS_QNORM);
+        // permuted, zero-padded query panel (+ chain norms for L2)
+        LEMON_HIP_CHECK(hipMemsetAsync(ws_qp, 0, (size_t)c.nq_pad * dpad * sizeof(float), stream));
+        rc = lemon_permute_rows(q_dev + c0 * d, c.cn, d, ws_qp, dpad, stream);
+        if (rc) return rc;
+        if (l2) {
+            LEMON_HIP_CHECK(hipMemsetAsync(ws_qnorm, 0, (size_t)c.nq_pad * sizeof(float), stream));
+            rc = lemon_rowdot_chain(q_dev + c0 * d, q_dev + c0 * d, c.cn, d, ws_qnorm, stream);
+            if (rc) return rc;
+        }
+        ScanParams p;
+        p.qp = ws_qp; p.xp = idx->xp; p.qnorm = ws_qnorm; p.xnorm = idx->xnorm;
+        p.cand = idx->at<u64>(lemon_index::WS_CAND); p.part = idx->at<u64>(lemon_index::WS_PART);
+        p.D = D_dev + c0 * k; p.I = I_dev + c0 * k;
+        p.nq = c.cn; p.n = idx->n; p.dpad = dpad; p.kk = k; p.metric = idx->metric;
+        p.n_tiles = c.n_tiles; p.tiles_per_split = c.tiles_per_split; p.splits = c.splits; p.nq_pad = c.nq_pad;
+        p.reserved8 = 0; p.reserved4 = 0;
+        p.stale = c.stale; p.fair = c.fair;
+        p.plan = plan_dev; p.plan_segs = slot ? slot->segs_off : 0;
+        p.ub = ub_dev ? ub_dev + c0 : nullptr;
+        // shared admission bounds: one order-encoded float per query, in the tail of the norm workspace ([ws_q, 3] floats:
+        // norms, then two spare columns), zeroed per launch; only when a panel really is scanned by several workgroups
+        p.th_pub = nullptr;
+        if (c.share) {
+            p.th_pub = reinterpret_cast<unsigned *>(ws_qnorm + 2 * idx->ws_q);
+            LEMON_HIP_CHECK(hipMemsetAsync(p.th_pub, 0, (size_t)c.nq_pad * sizeof(unsigned), stream));
+        }
+        {
+            const double flops = 2.0 * (double)c.cn * (double)idx->n * (double)d;
+            const double bytes = 4.0 * d * ((double)c.cn + (double)c.panels * (double)idx->n) + 12.0 * k * (double)c.cn;
+            LemonProfScope prof(idx, stream, flops, bytes);
+            launch_scan_f32(l2, ub_dev != nullptr, (unsigned)c.grid, stream, p);
+        }
+        LEMON_HIP_CHECK(hipGetLastError());
+        if (c.splits > 1) {
+            rc = lemon_launch_merge(p.part, c.splits, slot ? plan_dev + slot->pieces_off : nullptr, c.nq_pad, c.cn, k, idx->metric,
+                                    p.D, p.I, stream);
+            if (rc) return rc;
+        }
+        idx->last.algo = LEMON_ALGO_F32_MFMA;
+        idx->last_kernel = "scan_f32";
+        idx->last.grid = c.grid; idx->last.block = NT;
+        idx->last.query_panel = BQ; idx->last.db_splits = c.splits;
+    }
+    idx->last.nq = nq; idx->last.n = idx->n; idx->last.d = d; idx->last.k = k;
+    return LEMON_OK;
+}
 
 int lemon_search_f32(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, float *D_dev,
                      int64_t *I_dev, hipStream_t stream) {
-    if (k <= LEMON_MAX_K) return lemon_search_f32_pass(idx, q_dev, nq, k, D_dev, I_dev, nullptr, stream);
+    const splan::Knobs knobs = read_scan_knobs();
+    if (k <= LEMON_MAX_K) return lemon_search_f32_pass(idx, q_dev, nq, k, D_dev, I_dev, nullptr, knobs, stream);
     // faiss has no k limit: deeper lists are produced LEMON_MAX_K at a time, each pass admitting only rows whose key is
     // below the last key of the previous pass (same order, same tie rule: the concatenation IS the sorted top-k)
     const int kp_max = LEMON_MAX_K;
@@ -686,7 +685,7 @@ int lemon_search_f32(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, 
     int rc = LEMON_OK;
     for (int col0 = 0; col0 < k && rc == LEMON_OK; col0 += kp_max) {
         const int kp = k - col0 < kp_max ? k - col0 : kp_max;
-        rc = lemon_search_f32_pass(idx, q_dev, nq, kp, Dp, Ip, col0 ? ub : nullptr, stream);
+        rc = lemon_search_f32_pass(idx, q_dev, nq, kp, Dp, Ip, col0 ? ub : nullptr, knobs, stream);
         if (rc) break;
         hipLaunchKernelGGL(k_place_pass, dim3((unsigned)((nq * kp + 255) / 256)), dim3(256), 0, stream, Dp, Ip, nq, kp, k, col0,
                            idx->metric, D_dev, I_dev, ub);
@@ -695,120 +694,4 @@ int lemon_search_f32(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, 
     (void)hipFree(Dp); (void)hipFree(Ip); (void)hipFree(ub);
     idx->last.k = k;
     return rc;
-}
-
-static int lemon_search_f32_pass(lemon_index_t *idx, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
-                                 const u64 *ub_dev, hipStream_t stream) {
-    const int d = idx->d, dpad = idx->dpad;
-    if (idx->n == 0) return lemon_fill_empty(D_dev, I_dev, nq * k, idx->metric, stream);
-    const int n_tiles = (int)((idx->n + BX - 1) / BX);
-    for (int64_t c0 = 0; c0 < nq; c0 += QCHUNK) {
-        const int64_t cn = (nq - c0) < QCHUNK ? (nq - c0) : QCHUNK;
-        const int64_t nq_pad = round_up(cn, BQ);
-        const int panels = (int)(nq_pad / BQ);
-        int splits, tiles_per_split = n_tiles, pieces_off = 0, segs_off = 0;
-        unsigned grid;
-        static const bool legacy = getenv("LEMON_SPLITS") != nullptr;   // tuning knob: (panel, split) rectangles, no plan
-        const bool planned = !legacy && (int64_t)panels * n_tiles >= 2;
-        const lemon_index::PlanSlot *plan = nullptr;
-        const int *plan_dev = nullptr;
-        if (planned) {
-            const int prc = lemon_get_plan(idx, panels, n_tiles, stream, &plan, &plan_dev);
-            if (prc) return prc;
-            grid = (unsigned)plan->grid; splits = plan->splits; pieces_off = plan->pieces_off; segs_off = plan->segs_off;
-        } else {
-            lemon_plan_splits(panels, n_tiles, &splits, &tiles_per_split);
-            grid = (unsigned)(panels * splits);
-        }
-
-        int rc = lemon_ensure_search_ws(idx, nq_pad, splits, grid, dpad * 4, PAIR_CAP, stream);
-        if (rc) return rc;
-        float *ws_qp = idx->at<float>(lemon_index::WS_QP), *ws_qnorm = idx->at<float>(lemon_index::WS_QNORM);
-        u64 *ws_part = idx->at<u64>(lemon_index::WS_PART);
-        // permuted, zero-padded query panel (+ chain norms for L2)
-        LEMON_HIP_CHECK(hipMemsetAsync(ws_qp, 0, (size_t)nq_pad * dpad * sizeof(float), stream));
-        rc = lemon_permute_rows(q_dev + c0 * d, cn, d, ws_qp, dpad, stream);
-        if (rc) return rc;
-        if (idx->metric == LEMON_METRIC_L2) {
-            LEMON_HIP_CHECK(hipMemsetAsync(ws_qnorm, 0, (size_t)nq_pad * sizeof(float), stream));
-            rc = lemon_rowdot_chain(q_dev + c0 * d, q_dev + c0 * d, cn, d, ws_qnorm, stream);
-            if (rc) return rc;
-        }
-        ScanParams p;
-        p.qp = ws_qp; p.xp = idx->xp; p.qnorm = ws_qnorm; p.xnorm = idx->xnorm;
-        p.cand = idx->at<u64>(lemon_index::WS_CAND); p.part = ws_part;
-        p.D = D_dev + c0 * k; p.I = I_dev + c0 * k;
-        p.nq = cn; p.n = idx->n; p.dpad = dpad; p.kk = k; p.metric = idx->metric;
-        p.n_tiles = n_tiles; p.tiles_per_split = tiles_per_split; p.splits = splits; p.nq_pad = nq_pad;
-        p.plan = plan_dev; p.plan_segs = segs_off; p.phase_dbg = nullptr;
-        p.ub = ub_dev ? ub_dev + c0 : nullptr;
-        // shared admission bounds: one order-encoded float per query, in the tail of the norm workspace ([ws_q, 3] floats:
-        // norms, then two spare columns), zeroed per launch; only when a panel really is scanned by several workgroups
-        static const bool share = [] { const char *e = getenv("LEMON_SHARE_BOUNDS"); return !(e && e[0] == '0'); }();
-        p.th_pub = nullptr;
-        if (share && splits > 1) {
-            p.th_pub = reinterpret_cast<unsigned *>(ws_qnorm + 2 * idx->ws_q);
-            LEMON_HIP_CHECK(hipMemsetAsync(p.th_pub, 0, (size_t)nq_pad * sizeof(unsigned), stream));
-        }
-        // diagnostic instantiation only (LEMON_PHASE_PROF): 1 no operand loads, 2 no barriers, 4 filter off after 5 tiles,
-        // 8 appends forgotten, 16 bare read-out, 32 / 128 instruction-class probes.  None of them skips maintenance.
-        rc = lemon_parse_ablate("k_scan_f32", 1 | 2 | 4 | 8 | 16 | 32 | 128, &p.ablate);
-        if (rc) return rc;
-        static const int stale = [] { const char *e = getenv("LEMON_STALE"); return e && atoi(e) > 0 ? atoi(e) : 96; }();
-        p.stale = stale;
-        // fair-share turns (see k_scan_f32): about eight turns per launch, between 82 us and 5.2 ms each -- longer turns
-        // measured better (16.9 / 16.7 / 16.4 / 16.3 ms at the headline shape for no turns / 5 us / 82 us / 2.6 ms), a
-        // turn longer than the launch is no turn at all.  LEMON_FAIR = log2(turn in 10 ns ticks) overrides, 0 = off.
-        static const int fair_env = [] { const char *e = getenv("LEMON_FAIR"); return e ? atoi(e) : -1; }();
-        if (fair_env >= 0) p.fair = fair_env;
-        else {
-            const double ticks = 2.0 * (double)cn * (double)idx->n * (double)d / 1.25e14 * 1e8 / 8.0;   // launch / 8, in ticks
-            int bit = 13;
-            while (bit < 19 && (double)(2u << bit) <= ticks) ++bit;
-            p.fair = bit;
-        }
-        {
-            const double flops = 2.0 * (double)cn * (double)idx->n * (double)d;
-            const double bytes = 4.0 * d * ((double)cn + (double)panels * (double)idx->n) + 12.0 * k * (double)cn;
-            LemonProfScope prof(idx, stream, flops, bytes);
-            if (!ub_dev && idx->metric == LEMON_METRIC_IP && getenv("LEMON_PHASE_PROF")) {   // diagnostic build: phase cycle sums
-                static unsigned long long *dbg = nullptr;
-                if (!dbg) { (void)hipMalloc(&dbg, 128 + 8 * 4096); (void)hipMemset(dbg, 0, 128 + 8 * 4096); }
-                (void)hipMemset(dbg + 7, 0xff, 8);
-                p.phase_dbg = dbg;
-                hipLaunchKernelGGL((k_scan_f32<false, true>), dim3(grid), dim3(NT), 0, stream, p);
-                (void)hipStreamSynchronize(stream);
-                unsigned long long h[16]; (void)hipMemcpy(h, dbg, 128, hipMemcpyDeviceToHost);
-                const double tot = (double)(h[0] + h[1] + h[2] + h[3]);
-                fprintf(stderr, "[phase f32] grid=%u loop=%.1f%% filter=%.1f%% maintain=%.1f%% final=%.1f%% cyc/WG=%.3g\n",
-                        grid, 100.0 * h[0] / tot, 100.0 * h[1] / tot, 100.0 * h[2] / tot, 100.0 * h[3] / tot, tot / grid);
-                fprintf(stderr, "[clock f32] workgroup 0: %llu shader cycles in %llu ticks of the 100 MHz counter = %.0f MHz\n",
-                        h[4], h[5], h[5] ? 100.0 * (double)h[4] / (double)h[5] : 0.0);
-                fprintf(stderr, "[lives f32] workgroup life min %.2f ms  max %.2f ms;  wave-slot parity 0: %llu workgroups, mean %.2f ms;  parity 1: %llu, mean %.2f ms\n",
-                        h[7] / 1e5, h[6] / 1e5, h[9], h[9] ? h[8] / 1e5 / h[9] : 0.0, h[11], h[11] ? h[10] / 1e5 / h[11] : 0.0);
-                if (const char *dump = getenv("LEMON_LIVES_DUMP")) {      // per-workgroup lives (100 MHz ticks), one per line
-                    std::vector<unsigned long long> lv(grid < 4096 ? grid : 4096);
-                    (void)hipMemcpy(lv.data(), dbg + 16, lv.size() * 8, hipMemcpyDeviceToHost);
-                    if (FILE *f = fopen(dump, "w")) { for (auto v : lv) fprintf(f, "%llu\n", v); fclose(f); }
-                }
-                (void)hipMemset(dbg, 0, 128 + 8 * 4096);
-            } else if (ub_dev) {
-                if (idx->metric == LEMON_METRIC_L2) hipLaunchKernelGGL((k_scan_f32<true, false, true>), dim3(grid), dim3(NT), 0, stream, p);
-                else hipLaunchKernelGGL((k_scan_f32<false, false, true>), dim3(grid), dim3(NT), 0, stream, p);
-            } else if (idx->metric == LEMON_METRIC_L2) hipLaunchKernelGGL((k_scan_f32<true, false>), dim3(grid), dim3(NT), 0, stream, p);
-            else hipLaunchKernelGGL((k_scan_f32<false, false>), dim3(grid), dim3(NT), 0, stream, p);
-        }
-        LEMON_HIP_CHECK(hipGetLastError());
-        if (splits > 1) {
-            rc = lemon_launch_merge(ws_part, splits, planned ? plan_dev + pieces_off : nullptr, nq_pad, cn, k, idx->metric, p.D,
-                                    p.I, stream);
-            if (rc) return rc;
-        }
-        idx->last.algo = LEMON_ALGO_F32_MFMA;
-        idx->last_kernel = "scan_f32";
-        idx->last.grid = (int)grid; idx->last.block = NT;
-        idx->last.query_panel = BQ; idx->last.db_splits = splits;
-    }
-    idx->last.nq = nq; idx->last.n = idx->n; idx->last.d = d; idx->last.k = k;
-    return LEMON_OK;
 }

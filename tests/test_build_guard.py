@@ -60,8 +60,8 @@ _GEMM_ASM = ["k_gemm_f16x3tILi0E", "k_gemm_f16x3tILi1E", "k_gemm_f16x3tILi2E",
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src,must_be_clean", [
-    # (mangled-name fragments of the PRODUCTION instantiations; k_scan_f32: PROF = false, the 16-bit scans have no other form)
-    ("knn_f32.hip", ["k_scan_f32ILb0ELb0ELb0E", "k_scan_f32ILb1ELb0ELb0E"]),
+    # (mangled-name fragments of the PRODUCTION instantiations; the scans have no other form)
+    ("knn_f32.hip", ["k_scan_f32ILb0ELb0E", "k_scan_f32ILb1ELb0E", "k_scan_f32ILb0ELb1E", "k_scan_f32ILb1ELb1E"]),
     ("knn_bf16.hip", ["k_scan_bf16_qsILi12ELb0E", "k_scan_bf16_qsILi8ELb0E", "k_scan_bf16_qsILi4ELb0E",
                       "k_scan_bf16_qs2ILi12ELi16ELb0E", "k_scan_bf16_qs2ILi12ELi20ELb1E",
                       "k_scan_bf16_qs2ILi8ELi0ELb0E", "k_bf16_finalILb0ELb1E", "k_bf16_finalILb1ELb1E",
@@ -201,7 +201,7 @@ def _check_asm_discipline(name, lines):
     ("knn_bf16.hip", ["k_scan_bf16_qs2ILi12ELi16ELb0E", "k_scan_bf16_qs2ILi12ELi20ELb1E", "k_scan_bf16_qs2ILi8ELi0ELb0E",
                       "k_scan_f16_qs4ILi12ELi16ELb0E", "k_scan_f16_qs4ILi8ELi0ELb0E", "k_scan_f16_qs4ILi8ELi0ELb1E",
                       "k_scan_f16_qswILi16E", "k_scan_f16_qswILi20E"]),
-    ("knn_f32.hip", ["k_scan_f32ILb0ELb0ELb0E", "k_scan_f32ILb1ELb0ELb0E"]),
+    ("knn_f32.hip", ["k_scan_f32ILb0ELb0E", "k_scan_f32ILb1ELb0E", "k_scan_f32ILb0ELb1E", "k_scan_f32ILb1ELb1E"]),
 ])
 def test_hand_issued_asm_is_left_alone_by_the_compiler(src, kernels):
     asm = _kernel_asm(src)

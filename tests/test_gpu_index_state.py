@@ -110,6 +110,53 @@ def test_bf16_scan_sequence_on_one_handle(hip, oracle, monkeypatch, metric, whic
         assert key_of(reused.last_search_info(), "nq", "n", "k") == (nq, len(X), k)
 
 
+# ---- 2b. fp32 scan: its knobs are read per call, and a plan slot belongs to the knobs it was made under ------------------------
+F32_KNOBS = ("LEMON_SPLITS", "LEMON_XCDS", "LEMON_SEG_COST", "LEMON_SHARE_BOUNDS", "LEMON_STALE", "LEMON_FAIR")
+
+
+def _plain_knob_plain(hip, oracle, monkeypatch, metric, n, nq, name, value):
+    """search(Q, 10) at d = 64 on one handle three times -- no knob set, LEMON_<name> = value, no knob set -- each held against
+    the oracle bit for bit (every query: nq <= ORACLE_SAMPLE); -> [(grid, db_splits)] of the three searches, and of the plans
+    lemon_debug_scan_plan gives under the same three settings"""
+    rng = np.random.default_rng(29)
+    d, k = 64, 10
+    X, Q = fx.make_db(rng, n, d, metric), fx.make_queries(rng, nq, d, metric)
+    assert nq <= fx.ORACLE_SAMPLE
+    ix = new_index(hip, metric, d, F32, X)
+    for knob in F32_KNOBS:
+        monkeypatch.delenv(knob, raising=False)
+    panels, tiles = -(-nq // fx.ROWS), -(-n // fx.ROWS)
+    seen, plans = [], []
+    for setting in (None, value, None):
+        if setting is not None:
+            monkeypatch.setenv(name, setting)
+        plan = fx.scan_plan(panels, tiles)
+        plans.append((plan["grid"], plan["splits"]))
+        D, I = ix.search(cu(Q), k)
+        monkeypatch.delenv(name, raising=False)
+        assert ix.last_scan_kernel() == "scan_f32"
+        fx.assert_equals_oracle(oracle, metric, X, Q, k, D, I)
+        seen.append(key_of(ix.last_search_info(), "grid", "db_splits"))
+    return seen, plans
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_fp32_scan_reads_lemon_splits_per_call(hip, oracle, monkeypatch, metric):
+    """3 panels x 24 tiles: planned, then 3 panels x 2 forced splits, then planned again -- whatever the process ran before"""
+    seen, plans = _plain_knob_plain(hip, oracle, monkeypatch, metric, 3000, 300, "LEMON_SPLITS", "2")
+    assert seen[1] == (6, 2)
+    assert seen[0] == seen[2] == plans[0] == plans[2] != seen[1]
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_fp32_plan_slot_is_not_reused_under_another_segment_cost(hip, oracle, monkeypatch, metric):
+    """2 panels x 16 tiles in 4 workgroups (on any device of at least 2 CUs): 3 pieces per panel by default, 2 at cost 0;
+    a slot keyed on (panels, tiles) alone would serve the first plan to all three calls"""
+    seen, plans = _plain_knob_plain(hip, oracle, monkeypatch, metric, 2048, 256, "LEMON_SEG_COST", "0")
+    assert plans[0] == plans[2] and plans[0][1] != plans[1][1]
+    assert seen == plans
+
+
 # ---- 3. switching algorithms on one handle ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("metric", METRICS)
 def test_switching_algorithms_on_one_handle(hip, oracle, metric):

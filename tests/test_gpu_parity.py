@@ -394,7 +394,7 @@ def test_full_size_1m_self_join_bf16_rows_equal_f32_scan(hip):
     assert torch.equal(I[sub], Ir) and torch.equal(D[sub], Dr)
 
 
-@pytest.mark.parametrize("algo,bad", [(BF16, "2"), (BF16, "16"), (BF16, "junk"), (1, "64"), (1, "-1")])
+@pytest.mark.parametrize("algo,bad", [(BF16, "2"), (BF16, "16"), (BF16, "junk"), (1, "64"), (1, "-1"), (1, "4")])
 def test_unknown_ablate_bits_are_refused_before_any_launch(hip, monkeypatch, algo, bad):
     # round 2's recorded GPU fault: a working-tree diagnostic skipped list maintenance on LEMON_ABLATE=2 and the
     # lane-private half-lists (256 entries) ran 1 MiB past the candidate workspace.  Diagnostic knobs are now

@@ -68,6 +68,21 @@ def test_chunked_fp32_call_has_a_large_and_a_small_chunk():
     assert big["splits"] == 1 and rest["splits"] > 1                      # the second chunk merges pieces, the first does not
 
 
+def test_the_scan_plan_reads_its_knobs_per_call(monkeypatch):
+    """the shapes of the two per-call knob tests: 3 x 24 units in 9 workgroups; 2 x 16 units in 3 pieces per panel, 2 at segment
+    cost 0 and 3 again without it, in one process"""
+    for knob in ("LEMON_XCDS", "LEMON_SEG_COST"):
+        monkeypatch.delenv(knob, raising=False)
+    assert fx.scan_plan(3, 24)["grid"] == 9
+    splits = []
+    for cost in (None, "0", None):
+        if cost is not None:
+            monkeypatch.setenv("LEMON_SEG_COST", cost)
+        splits.append(fx.scan_plan(2, 16)["splits"])
+        monkeypatch.delenv("LEMON_SEG_COST", raising=False)
+    assert splits == [3, 2, 3]
+
+
 def test_switch_sequence_alternates_and_moves_nq_both_ways():
     algos = [a for a, _, _ in fx.SWITCH_SEQUENCE]
     assert all(a != b for a, b in zip(algos, algos[1:])) and algos.count(fx.F32) >= 2 and algos.count(fx.BF16) >= 2

@@ -11,7 +11,6 @@ for shape in ${SHAPES:-"50000 40000 512" "131072 131072 512"}; do
   for f in ${VALUES:-0 13 18}; do
     echo "== $shape $KNOB=$f"
     env $KNOB=$f timeout -k 10 300 python3 tools/scan_time.py $shape 51 f32 2>&1 | tail -1
-    [ -n "$LIVES" ] && env $KNOB=$f LEMON_PHASE_PROF=1 timeout -k 10 300 python3 tools/scan_time.py $shape 51 f32 2>&1 | grep -E "lives|phase" | tail -2
   done
 done
 done
