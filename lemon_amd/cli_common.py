@@ -117,9 +117,12 @@ def prepare(args):
     train_set, val_set, test_set = data_mod.get_dataset(args.dataset, args.data_seed, percent_flips=args.noise_level,
                                                         flip_type=args.noise_type, data_root=args.data_root,
                                                         image_size=model.cfg.image_size)
-    if getattr(args, "subset_val_set", -1) > 0:
+    # --subset_val_set_sweep: the whole validation set is embedded and searched once, the subsets are drawn from its
+    # record (run_lemon.subset_val_frame); the cache entries are those of a plain run
+    subset_val_set = -1 if getattr(args, "subset_val_set_sweep", None) is not None else getattr(args, "subset_val_set", -1)
+    if subset_val_set > 0:
         rng = np.random.default_rng(args.data_seed)
-        val_set = val_set.subset(rng.choice(np.arange(len(val_set)), min(args.subset_val_set, len(val_set)), replace=False))
+        val_set = val_set.subset(rng.choice(np.arange(len(val_set)), min(subset_val_set, len(val_set)), replace=False))
 
     # identical prompts are embedded once and gathered (class datasets: C prompts for N samples): the same function
     # of the input, independent of how samples fall into micro-batches; --no_text_dedup encodes every sample's prompt
@@ -174,7 +177,7 @@ def prepare(args):
                            noise_level=args.noise_level, data_seed=args.data_seed, clip_model=args.clip_model,
                            clip_path=os.path.abspath(args.clip_path) if os.path.exists(str(args.clip_path)) else args.clip_path,
                            data_root=args.data_root, prompt=args.custom_cifar_prompt,
-                           subset_val_set=getattr(args, "subset_val_set", -1))
+                           subset_val_set=subset_val_set)
 
     def embed_split(dset, sname):
         """this rank's contiguous shard of a split -> (emb_img, emb_txt, meta) on the device"""

@@ -786,12 +786,42 @@ def lemon_score(rec, hparams, return_dn=False):
     return (score, dn, dm) if return_dn else score
 
 
-def local_search(rec, y, x0s, methods=("Powell", "Nelder-Mead"), force_zero=(), force_one=(), ks=None, return_info=False):
+def _force_masks(force_zero, force_one):
+    return (sum(1 << HP_ORDER.index(nm) for nm in set(force_zero)), sum(1 << HP_ORDER.index(nm) for nm in set(force_one)))
+
+
+def _cell_masks(what, force_zero, force_one, cells):
+    """[(force_zero mask, force_one mask), ...]: of `cells`, a non-empty list of (force_zero, force_one) name pairs, or of the
+    one pair force_zero / force_one where cells is None."""
+    if cells is None:
+        return [_force_masks(force_zero, force_one)]
+    if force_zero or force_one:
+        raise ValueError(f"{what}: give the force masks either as force_zero= / force_one= or as cells=, not both")
+    cells = list(cells)
+    if not cells:
+        raise ValueError(f"{what}: cells is empty; expected a list of (force_zero, force_one) pairs")
+    return [_force_masks(fz, fo) for fz, fo in cells]
+
+
+def _by_cell(rows, n_cells, n_ks, per_k, ks, cells):
+    """rows in spec's order (cell, k, the per_k results of one k) -> what the caller asked for: per cell where `cells` was
+    given, per k where `ks` was given."""
+    per = [rows[c * n_ks * per_k:(c + 1) * n_ks * per_k] for c in range(n_cells)]
+    if ks is not None:
+        per = [[r[t * per_k:(t + 1) * per_k] for t in range(n_ks)] for r in per]
+    return per[0] if cells is None else per
+
+
+def local_search(rec, y, x0s, methods=("Powell", "Nelder-Mead"), force_zero=(), force_one=(), ks=None, return_info=False,
+                 cells=None):
     """The scipy local searches of maximize_metric (lib/metrics/utils.py:151-158) on the device-resident record `rec`, all in
     ONE launch and one copy back (lemon_hparam_search): for each x0 of `x0s`, for each method -- the reference's order -- what
     scipy.optimize.minimize(objective, x0, method=method, options={}) returns on maximize_metric's objective, bit for bit.
     -> [(x [6] float64, fun), ...]; with `ks` (values of knn_k, each <= the record's depth: a search sees the [n, k] prefix)
-    one such list per k.  return_info: (x, fun, nfev, nit, status) instead.  force_zero / force_one: names of HP_ORDER."""
+    one such list per k.  return_info: (x, fun, nfev, nit, status) instead.  force_zero / force_one: names of HP_ORDER.
+    cells=[(force_zero, force_one), ...]: the searches of several mask pairs on the same record -- the ablations of a cell
+    sweep -- still in ONE launch (for each cell, each k, each x0, each method) -> one entry per cell, each what the call with
+    that pair as force_zero / force_one returns, bit for bit (a search is one workgroup and sees only its own row of spec)."""
     dev = rec["D_n"].device
     f32 = lambda key: dev_f32(rec[key], key)
     d1, Dn, trn, dn, Dm, trm, dm = (f32(key) for key in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m"))
@@ -802,15 +832,16 @@ def local_search(rec, y, x0s, methods=("Powell", "Nelder-Mead"), force_zero=(), 
     unknown = [m for m in methods if m not in _lib.SEARCH_METHODS]
     if unknown:
         raise ValueError(f"local_search: unknown method(s) {unknown}; the device path has {sorted(_lib.SEARCH_METHODS)}")
-    fz = sum(1 << HP_ORDER.index(nm) for nm in set(force_zero))
-    fo = sum(1 << HP_ORDER.index(nm) for nm in set(force_one))
+    masks = _cell_masks("local_search", force_zero, force_one, cells)
     x0s = np.asarray(x0s, dtype=np.float64).reshape(-1, 6)
     per_k = len(x0s) * len(methods)
-    S = per_k * len(k_list)
+    S = per_k * len(k_list) * len(masks)
+    shaped = lambda rows: _by_cell(rows, len(masks), len(k_list), per_k, ks, cells)
     if S == 0:
-        return [] if ks is None else [[] for _ in k_list]
-    x0 = np.repeat(np.tile(x0s, (len(k_list), 1)), len(methods), axis=0)              # for each k, each x0, each method
-    spec = np.array([[_lib.SEARCH_METHODS[m], k, fz, fo] for k in k_list for _ in range(len(x0s)) for m in methods], dtype=np.int32)
+        return shaped([])
+    x0 = np.repeat(np.tile(x0s, (len(masks) * len(k_list), 1)), len(methods), axis=0)  # for each cell, each k, each x0, each method
+    spec = np.array([[_lib.SEARCH_METHODS[m], k, fz, fo] for fz, fo in masks for k in k_list for _ in range(len(x0s)) for m in methods],
+                    dtype=np.int32)
     lib = _lib.load()
     need = lib.lemon_hparam_search_workspace_bytes(n, S)
     if need < 0:
@@ -828,19 +859,19 @@ def local_search(rec, y, x0s, methods=("Powell", "Nelder-Mead"), force_zero=(), 
     if bad:
         raise _lib.LemonHipError(f"lemon_hparam_search: search(es) {bad} ended at the iteration limit of scipy's bracket(), where "
                                  "scipy.optimize.minimize raises RuntimeError")
-    if ks is None:
-        return rows
-    return [rows[t * per_k:(t + 1) * per_k] for t in range(len(k_list))]
+    return shaped(rows)
 
 
-def lbfgs_polish(rec, y, x0s, force_zero=(), force_one=(), ks=None, return_info=False):
+def lbfgs_polish(rec, y, x0s, force_zero=(), force_one=(), ks=None, return_info=False, cells=None):
     """The LBFGS polish of maximize_metric (lib/metrics/utils.py:160-176) on the device-resident record `rec`, all start points
     in ONE launch and one copy back (lemon_lbfgs_polish): for each x0 of `x0s` -- the reference's order -- the x that 20
     optimizer.step calls of torch.optim.LBFGS leave on the SoftMargin proxy, computed in fixed-order IEEE double (a function of
     the record alone; not bit-compatible with torch's own float32-promoted run, see include/lemon_hip.h).
     -> [(x [6] float64, status), ...], status 1 = x or the loss is not finite; with `ks` (values of knn_k, each <= the record's
     depth: a polish sees the [n, k] prefix) one such list per k.  return_info: (x, status, loss, nfev, nit) instead.
-    force_zero / force_one: names of HP_ORDER."""
+    force_zero / force_one: names of HP_ORDER.  cells=[(force_zero, force_one), ...]: as in local_search -- the polishes of
+    several mask pairs in ONE launch (for each cell, each k, each x0) -> one entry per cell, each what the call with that pair
+    returns, bit for bit."""
     dev = rec["D_n"].device
     f32 = lambda key: dev_f32(rec[key], key)
     d1, Dn, trn, dn, Dm, trm, dm = (f32(key) for key in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m"))
@@ -848,15 +879,15 @@ def lbfgs_polish(rec, y, x0s, force_zero=(), force_one=(), ks=None, return_info=
     k_list = [kmax] if ks is None else [int(k) for k in ks]
     if any(k < 1 or k > kmax for k in k_list):
         raise ValueError(f"lbfgs_polish: every k must lie in 1 .. {kmax} (the record's depth), got {k_list}")
-    fz = sum(1 << HP_ORDER.index(nm) for nm in set(force_zero))
-    fo = sum(1 << HP_ORDER.index(nm) for nm in set(force_one))
+    masks = _cell_masks("lbfgs_polish", force_zero, force_one, cells)
     x0s = np.asarray(x0s, dtype=np.float64).reshape(-1, 6)
     per_k = len(x0s)
-    S = per_k * len(k_list)
+    S = per_k * len(k_list) * len(masks)
+    shaped = lambda rows: _by_cell(rows, len(masks), len(k_list), per_k, ks, cells)
     if S == 0:
-        return [] if ks is None else [[] for _ in k_list]
-    x0 = np.tile(x0s, (len(k_list), 1))                                               # for each k, each x0
-    spec = np.array([[k, fz, fo] for k in k_list for _ in range(per_k)], dtype=np.int32)
+        return shaped([])
+    x0 = np.tile(x0s, (len(masks) * len(k_list), 1))                                  # for each cell, each k, each x0
+    spec = np.array([[k, fz, fo] for fz, fo in masks for k in k_list for _ in range(per_k)], dtype=np.int32)
     yb = torch.as_tensor(np.asarray(y).astype(bool).astype(np.uint8)).to(dev)
     x0_d, spec_d = torch.from_numpy(x0).to(dev), torch.from_numpy(spec).to(dev)
     out = torch.empty(S * ctypes.sizeof(_lib.PolishResult), dtype=torch.uint8, device=dev)
@@ -865,9 +896,7 @@ def lbfgs_polish(rec, y, x0s, force_zero=(), force_one=(), ks=None, return_info=
     res = (_lib.PolishResult * S).from_buffer_copy(out.cpu().numpy().tobytes())
     rows = [(np.array(list(r.x), dtype=np.float64), int(r.status)) + ((float(r.loss), int(r.nfev), int(r.nit)) if return_info else ())
             for r in res]
-    if ks is None:
-        return rows
-    return [rows[t * per_k:(t + 1) * per_k] for t in range(len(k_list))]
+    return shaped(rows)
 
 
 def _stack_col(df, col, device):

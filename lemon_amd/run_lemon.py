@@ -13,12 +13,17 @@ per-sample record schema (:291-307).  Differences, all explicit:
   * extension flag --dist_type_sweep cosine,euclidean: both metrics of the reference's grid in ONE run -- embed once, one pair
     of IP indices, one search per modality and split; the euclidean lists are derived from the cosine lists and certified row
     by row, the rest searched again (<output_dir>/dist_type=<m>/, dist_sweep.json).  Composes with --knn_k_sweep.
+  * extension flags --subset_val_set_sweep -1,10,50,... / --ablation_sweep none,multimodal_baseline,...|all: the two axes of the
+    reference's grid that only change the tail of a run, in ONE run -- embed and search once on the whole validation set, then
+    the tail of a run per cell on the rows that run would have drawn, the record kept on the device across the cells
+    (<output_dir>/[dist_type=<d>/][subset_val_set=<m>/][ablation=<a>/][knn_k=<k>/], cell_sweep.json).  Compose with both others.
 """
 import argparse
 import copy
 import json
 import os
 import pickle
+import re
 import sys
 from datetime import datetime
 
@@ -27,6 +32,10 @@ import pandas as pd
 import torch
 
 from .cli_common import CLF_DATASETS, add_extension_flags  # noqa: F401  (CLF_DATASETS re-exported: run_lemon.py:32)
+
+
+ABLATIONS = ("none", "tau_1", "tau_2", "tau_1_2", "beta", "gamma", "multimodal_baseline", "d1", "only_gamma",
+             "only_beta")                                                      # run_lemon.py:49-50, in the parser's order
 
 
 def build_parser():
@@ -50,9 +59,7 @@ def build_parser():
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--data_seed", default=0, type=int)
     p.add_argument("--compr_dataset_size_limit", default=50000, type=int)
-    p.add_argument("--ablation", default="none",
-                   choices=["none", "tau_1", "tau_2", "tau_1_2", "beta", "gamma", "multimodal_baseline", "d1",
-                            "only_gamma", "only_beta"])
+    p.add_argument("--ablation", default="none", choices=list(ABLATIONS))
     p.add_argument("--use_discrete_for_text", action="store_true", help="use the discrete metric for text comparisons")
     p.add_argument("--real_dataset", action="store_true", help="Running on real dataset, do not optimize hparams")
     p.add_argument("--custom_cifar_prompt", default=None)
@@ -88,6 +95,19 @@ def build_parser():
     p.add_argument("--dist_sweep_margin", default=4, type=int,
                    help="extra neighbours the cosine search of --dist_type_sweep keeps to certify the euclidean lists (the search "
                         "depth stays within LEMON_MAX_K = 64)")
+    p.add_argument("--ablation_sweep", default=None, type=str,
+                   help="comma-separated values of --ablation, or 'all' for the ten of them (the component table; experiments.py "
+                        "crosses every grid with none,multimodal_baseline): embed, build the DB and search ONCE, then the tail of "
+                        "an --ablation run for every value on the same record -> <output_dir>/ablation=<a>/ and "
+                        "<output_dir>/cell_sweep.json; --ablation is ignored")
+    p.add_argument("--subset_val_set_sweep", default=None, type=str,
+                   help="comma-separated values of --subset_val_set, e.g. -1,10,50,100,500,1000 (experiments.py:205; -1 = the whole "
+                        "validation set): embed and search the whole validation set ONCE, then the tail of a --subset_val_set run "
+                        "for every value on the rows that run would have drawn -> <output_dir>/subset_val_set=<m>/ and "
+                        "<output_dir>/cell_sweep.json; --subset_val_set is ignored.  The sweeps compose: a cell is "
+                        "dist_type=<d>/subset_val_set=<m>/ablation=<a>/knn_k=<k>/, a level for every sweep flag given")
+    # a list that begins with -1 is a value, as a lone negative number is to argparse, not an unknown option
+    p._negative_number_matcher = re.compile(r"^-\d+(,\s*-?\d+)*,?$|^-\d*\.\d+$")
     return p
 
 
@@ -130,6 +150,77 @@ def parse_k_sweep(text):
     return ks
 
 
+def parse_ablation_sweep(text):
+    """'d1,none,d1' -> ['d1', 'none']: de-duplicated, order kept; 'all' -> the ten values of --ablation in the parser's order.
+    Refused (ValueError): an empty list, a name that is not an ablation."""
+    parts = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not parts:
+        raise ValueError("--ablation_sweep: the list is empty; expected comma-separated values of ablation such as "
+                         "none,multimodal_baseline, or all")
+    if parts == ["all"]:
+        return list(ABLATIONS)
+    out = []
+    for t in parts:
+        if t not in ABLATIONS:
+            raise ValueError(f"--ablation_sweep: {t!r} is not an ablation ({'|'.join(ABLATIONS)}, or all alone)")
+        if t not in out:
+            out.append(t)
+    return out
+
+
+def parse_subset_sweep(text):
+    """'-1,10,50,10' -> [-1, 10, 50]: de-duplicated, order kept; -1 = the whole validation set.  Refused (ValueError): an empty
+    list, anything that is not an integer, 0, a value below -1."""
+    parts = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not parts:
+        raise ValueError("--subset_val_set_sweep: the list is empty; expected comma-separated values of subset_val_set such as "
+                         "-1,10,50,100")
+    try:
+        ms = [int(t) for t in parts]
+    except ValueError:
+        raise ValueError(f"--subset_val_set_sweep: {text!r} is not a comma-separated list of integers") from None
+    out = []
+    for m in ms:
+        if m == 0 or m < -1:
+            raise ValueError(f"--subset_val_set_sweep: a subset has at least one row (or is -1, the whole validation set), got {m}")
+        if m not in out:
+            out.append(m)
+    return out
+
+
+def cell_path(dist_type=None, subset_val_set=None, ablation=None, knn_k=None):
+    """The directory of a cell below <output_dir>: dist_type=<d>/subset_val_set=<m>/ablation=<a>/knn_k=<k>, outermost to
+    innermost, a level for every axis that is swept (not None); '' where none is."""
+    levels = (("dist_type", dist_type), ("subset_val_set", subset_val_set), ("ablation", ablation), ("knn_k", knn_k))
+    return "/".join(f"{name}={value}" for name, value in levels if value is not None)
+
+
+def _subset_rows(df, m, data_seed):
+    """Positions in `df` of the rows of subset_val_frame(df, m, data_seed), in its order."""
+    sset = df["sset"].values
+    val = np.flatnonzero(sset == "val")
+    rng = np.random.default_rng(data_seed)         # a generator of its own per m, as a run has: the draws are no prefixes
+    pick = rng.choice(np.arange(len(val)), min(m, len(val)), replace=False)
+    return np.concatenate([np.flatnonzero(sset == "train"), val[pick], np.flatnonzero(sset == "test")])
+
+
+def subset_val_frame(df, m, data_seed, rows=None):
+    """The per-sample frame a `--subset_val_set m --data_seed data_seed` run builds, from the frame `df` of the run on the whole
+    validation set (cli_common.prepare draws the subset in front of the embedding pass; validation rows are never in the
+    DB, so a row's record does not depend on which other validation rows exist): train and test rows as they are, the
+    validation rows rng.choice(arange(n_val), min(m, n_val), replace=False) of default_rng(data_seed) in that order -- for
+    m >= n_val a permutation, not the identity -- with idx renumbered 0 .. m'-1, the blocks in the order train, val, test.
+    m = -1: `df` itself.  The neighbour arrays of the rows are shared with `df`, not copied."""
+    if m == -1:
+        return df
+    out = df.iloc[_subset_rows(df, m, data_seed) if rows is None else rows].reset_index(drop=True)
+    is_val = (out["sset"] == "val").values
+    idx = out["idx"].values.copy()
+    idx[is_val] = np.arange(int(is_val.sum()), dtype=idx.dtype)
+    out["idx"] = idx
+    return out
+
+
 def select_best_k(selected_val):
     """{k: selected_val} -> the k with the highest value, ties to the smaller k; None when there is nothing to select on
     (no k, or a k without a value)."""
@@ -158,6 +249,12 @@ def main(argv=None):
             parser.error(str(e))
         if args.dist_sweep_margin < 0:
             parser.error("--dist_sweep_margin: must be >= 0")
+    for text, parse in ((args.ablation_sweep, parse_ablation_sweep), (args.subset_val_set_sweep, parse_subset_sweep)):
+        if text is not None:
+            try:
+                parse(text)
+            except ValueError as e:
+                parser.error(str(e))
     return run_with_tee(_run, args)
 
 
@@ -243,6 +340,9 @@ def _run(args):
         return 0
     n_samples = sum(len(f) for f in frames[dist_names[0]])
     print(f"Finished {n_samples} samples in {timedelta} seconds; avg of {timedelta / n_samples}s per sample")
+    subsets = parse_subset_sweep(args.subset_val_set_sweep) if getattr(args, "subset_val_set_sweep", None) is not None else None
+    ablations = parse_ablation_sweep(args.ablation_sweep) if getattr(args, "ablation_sweep", None) is not None else None
+    cells = [] if (subsets is not None or ablations is not None) else None
     for m in dist_names:
         df = pd.concat(frames[m], ignore_index=True)
         args_m, out_m = args, out_dir
@@ -254,19 +354,29 @@ def _run(args):
             with open(out_m / "args.json", "w") as f:
                 json.dump(vars(args_m), f, default=str)
             print(f"==== dist_type = {m} ====")
-        if sweep:
+        if cells is not None:
+            cells += _cell_tails(args_m, df, out_dir, device, m if metrics is not None else None, subsets, ablations, sweep)
+        elif sweep:
             _sweep_tail(args_m, df, out_m, device, sweep)
         else:
             _tail(args_m, df, out_m, device)
+    failed = [c for c in cells or [] if c["status"] != "ok"]
+    if cells is not None:
+        with open(out_dir / "cell_sweep.json", "w") as f:
+            json.dump({"axes": {"dist_type": metrics, "subset_val_set": subsets, "ablation": ablations, "knn_k": sweep},
+                       "cells": cells}, f, indent=1)
+        for c in failed:
+            print(f"cell {c['path']}: {c['error']}", file=sys.stderr)
     if metrics is not None:
         with open(out_dir / "dist_sweep.json", "w") as f:
             json.dump({"metrics": list(dist_names), "margin": int(args.dist_sweep_margin) if both else None, "knn_k": int(k),
                        "splits": sweep_counts}, f, indent=1)
+    if (metrics is not None or cells is not None) and not failed:
         with open(os.path.join(out_dir, "done"), "w") as f:
             f.write("done")
     if world > 1:
         torch.distributed.destroy_process_group()
-    return 0
+    return 1 if failed else 0
 
 
 NEIGHBOR_COLUMNS = ("dists_n", "D_n", "dists_tr_n", "dists_m", "D_m", "dists_tr_m")
@@ -285,39 +395,191 @@ def _grid_setup(args):
     grid = {"beta": np.arange(0, 100.01, 5), "gamma": np.arange(0, 100.01, 5), "tau_1": [0, 1, 5, 10],
             "tau_2": [0, 1, 5, 10]} if args.hparam_grid == "full" else \
            {"beta": [0, 5, 10], "gamma": [0, 5, 10], "tau_1": [0, 1], "tau_2": [0, 5]}
-    force_zero = {"none": [], "d1": [], "tau_1": ["tau_1_n", "tau_1_m"], "tau_2": ["tau_2_n", "tau_2_m"],
-                  "tau_1_2": ["tau_1_n", "tau_1_m", "tau_2_n", "tau_2_m"], "beta": ["beta"],
-                  "gamma": ["gamma"]}[args.ablation]
-    force_one = ["beta"] if args.ablation == "d1" else []
-    return grid, force_zero, force_one
+    force_zero, force_one = FORCE_MASKS[args.ablation]
+    return grid, list(force_zero), list(force_one)
 
 
-def _sweep_tail(args, df, out_dir, device, ks):
+FORCE_MASKS = {"none": ([], []), "d1": ([], ["beta"]), "tau_1": (["tau_1_n", "tau_1_m"], []), "tau_2": (["tau_2_n", "tau_2_m"], []),
+               "tau_1_2": (["tau_1_n", "tau_1_m", "tau_2_n", "tau_2_m"], []), "beta": (["beta"], []),
+               "gamma": (["gamma"], [])}                  # the ablations that search: ablation -> (force_zero, force_one)
+
+
+def _selection_entry(sel_res, ssets):
+    """agg_results' entry as k_selection.json and cell_sweep.json record it; None for a run that selects nothing."""
+    from . import metrics as M
+    if sel_res is None:
+        return None
+    entry = {"selected_val": sel_res.get("selected_val"), **{name: float(sel_res[name]) for name in M.HP_NAMES},
+             "thres": sel_res.get("thres"),
+             "splits": {sset: {"AUROC": float(sel_res[sset]["AUROC"]), "F1_optimal": float(sel_res[sset]["F1_optimal"])}
+                        for sset in ssets}}
+    for key in ("selected_val", "thres"):
+        entry[key] = None if entry[key] is None else float(entry[key])
+    return entry
+
+
+def _error_text(e):
+    import traceback
+    traceback.print_exc()
+    return f"{type(e).__name__}: {e}"
+
+
+class _CellRecord:
+    """The record of one (metric, subset) for all of its cells.  The neighbour arrays are uploaded ONCE, at the depth they were
+    searched at, and stay on the device: the prefix of a knn_k, the validation rows and the zeroed d_1 of the d1 ablation are
+    taken there (the same float32 bits _device_rec makes from a cell's own frame).  frame(k): the frame of a cell, its
+    neighbour columns shared between the cells of a k.  search_fn / polish_fn: what maximize_metric asks for, served from ONE
+    ops.local_search / ops.lbfgs_polish launch per distinct d_1 column -- the real one and the zeroed one -- that covers every
+    ablation of the sweep that searches and every k; made on first use, inside the cell that asks."""
+
+    def __init__(self, df, deep, rows, device, ks, ablations):
+        self.df, self.ks, self.ablations = df, ks, [a for a in ablations if a in FORCE_MASKS]
+        self.host = deep if rows is None else {c: v[rows] for c, v in deep.items()}       # numpy [n, depth] a neighbour column
+        self.dev = {c: torch.from_numpy(v.astype(np.float32)).to(device) for c, v in self.host.items()}
+        d1 = torch.from_numpy(df["d_1"].values.astype(np.float32)).to(device)
+        self.d1 = {False: d1, True: torch.zeros_like(d1)}
+        is_val = (df["sset"] == "val").values
+        self.val_rows = torch.from_numpy(np.flatnonzero(is_val)).to(device)
+        self.y_val = df["is_mislabel"].values[is_val]
+        self._recs, self._frames, self._launched = {}, {}, {}
+
+    def rec(self, k, zero_d1, val_only):
+        """_device_rec of the frame of knn_k = k (None: the depth searched at), of all rows or of the validation rows"""
+        if (k, val_only) not in self._recs:
+            out = {}
+            for c, v in self.dev.items():
+                v = v[self.val_rows] if val_only else v
+                out[c] = (v if k is None else v[:, :k]).contiguous()
+            self._recs[(k, val_only)] = out
+        d1 = self.d1[bool(zero_d1)]
+        return {**self._recs[(k, val_only)], "d_1": d1[self.val_rows] if val_only else d1}
+
+    def frame(self, k):
+        """A cell's frame at knn_k = k (None: the record as searched): its own columns, so that what it writes (d_1, the score
+        columns) stays its own; the arrays of the neighbour columns are shared."""
+        if k not in self._frames:
+            base = self.df.copy(deep=False)
+            if k is not None:
+                for c in NEIGHBOR_COLUMNS:
+                    base[c] = list(np.ascontiguousarray(self.host[c][:, :k]))
+            self._frames[k] = base
+        return self._frames[k].copy(deep=False)
+
+    def _launch(self, what, ablation):
+        from . import ops
+        zero = "d1" in ablation
+        if (what, zero) not in self._launched:
+            group = [a for a in self.ablations if ("d1" in a) == zero]
+            rec, masks = self.rec(None, zero, True), [FORCE_MASKS[a] for a in group]
+            if what == "search":
+                res = ops.local_search(rec, self.y_val, SEARCH_STARTS, SEARCH_METHODS, ks=self.ks, cells=masks)
+            else:
+                res = ops.lbfgs_polish(rec, self.y_val, SEARCH_STARTS, ks=self.ks, cells=masks)
+            self._launched[(what, zero)] = dict(zip(group, res))
+        return self._launched[(what, zero)][ablation]
+
+    def search_fn(self, ablation, t=None):
+        """maximize_metric's local_search for a cell of `ablation` (and of the t-th k of the sweep)"""
+        def serve(x0s, methods, force_zero, force_one):
+            asked = ([list(x0) for x0 in x0s], tuple(methods), (list(force_zero), list(force_one)))
+            assert asked == (SEARCH_STARTS, SEARCH_METHODS, FORCE_MASKS[ablation]), \
+                "the searches of maximize_metric are not the ones lemon_hparam_search was called with"
+            res = self._launch("search", ablation)
+            return res if t is None else res[t]
+        return serve
+
+    def polish_fn(self, ablation, t=None):
+        """maximize_metric's lbfgs_polish for a cell of `ablation` (and of the t-th k of the sweep)"""
+        def serve(x0s, force_zero, force_one):
+            asked = ([list(x0) for x0 in x0s], (list(force_zero), list(force_one)))
+            assert asked == (SEARCH_STARTS, FORCE_MASKS[ablation]), \
+                "the polishes of maximize_metric are not the ones lemon_lbfgs_polish was called with"
+            res = self._launch("polish", ablation)
+            return [x for x, _ in (res if t is None else res[t])]
+        return serve
+
+
+def _cell_tails(args, df, out_root, device, dist, subsets, ablations, ks):
+    """The tails of every (subset, ablation, knn_k) cell of one metric on the record `df` that was searched once -> the entries
+    of cell_sweep.json.  dist / subsets / ablations / ks: the swept axes (None: not swept, the value of `args` holds and the
+    directory has no such level).  A cell whose tail raises is recorded with the exception's text and the sweep goes on."""
+    deep = {c: np.stack(df[c].values) for c in NEIGHBOR_COLUMNS}       # stacked once a metric; a subset takes rows of it
+    entries = []
+    for m in subsets or [None]:
+        rows = None if m in (None, -1) else _subset_rows(df, m, args.data_seed)
+        frame = df if rows is None else subset_val_frame(df, m, args.data_seed, rows)
+        args_s = copy.copy(args)
+        if m is not None:
+            args_s.subset_val_set = m
+        cell = _CellRecord(frame, deep, rows, device, ks, ablations or [args.ablation])
+        for a in ablations or [args.ablation]:
+            where = dict(dist_type=dist, subset_val_set=m, ablation=a if ablations is not None else None)
+            args_a = copy.copy(args_s)
+            args_a.ablation = a
+            out_a = out_root / cell_path(**where)
+            out_a.mkdir(exist_ok=True, parents=True)
+            args_a.output_dir = str(out_a)
+            print(f"==== {cell_path(**where)} ====")
+            if ks:
+                results = _sweep_tail(args_a, frame, out_a, device, ks, cell=cell)
+            else:
+                with open(out_a / "args.json", "w") as f:
+                    json.dump(vars(args_a), f, default=str)
+                try:
+                    device_mode = lambda flag: _grid_setup(args_a) is not None and getattr(args_a, flag, "host") == "device"
+                    sel_res = _tail(args_a, cell.frame(None), out_a, device, cell=cell,
+                                    local_search=cell.search_fn(a) if device_mode("hparam_search") else None,
+                                    lbfgs_polish=cell.polish_fn(a) if device_mode("lbfgs_polish") else None)
+                    results = {None: (_selection_entry(sel_res, frame.sset.unique()), None)}
+                except Exception as e:
+                    results = {None: (None, _error_text(e))}
+            for k, (entry, error) in results.items():
+                entries.append({"path": cell_path(**where, knn_k=k), "dist_type": args_a.dist_type,
+                                "subset_val_set": int(args_a.subset_val_set), "ablation": a,
+                                "knn_k": int(args_a.knn_k if k is None else k),
+                                **({"status": "ok"} if error is None else {"status": "error", "error": error}), **(entry or {})})
+    return entries
+
+
+def _sweep_tail(args, df, out_dir, device, ks, cell=None):
     """The tail of a run for every k of the sweep, on the prefix of the record searched at max(ks); the grid of all ks comes
     from ONE ops.grid_f1_ks call made in front of the loop and, with --hparam_search device, the local searches of all ks from
-    ONE ops.local_search call beside it; with --lbfgs_polish device the polishes of all ks from ONE ops.lbfgs_polish call."""
+    ONE ops.local_search call beside it; with --lbfgs_polish device the polishes of all ks from ONE ops.lbfgs_polish call.
+    cell: the _CellRecord of a cell sweep -- the device record, the frames and the searches come from it (shared with the
+    other ablations of its subset), `df` is not written to, and a k whose tail raises is recorded and the others go on.
+    -> {k: (k_selection.json's entry, None | the exception's text)}."""
     import copy
     import json
     from . import metrics as M, ops
     from .neighbors import prefix_record
-    if "d1" in args.ablation:
-        df["d_1"] = 0.0
-    deep = {c: torch.from_numpy(np.stack(df[c].values)) for c in NEIGHBOR_COLUMNS}     # the gathered record, [n, max(ks)]
+    zero_d1 = "d1" in args.ablation
+    if cell is None:
+        if zero_d1:
+            df["d_1"] = 0.0
+        deep = {c: torch.from_numpy(np.stack(df[c].values)) for c in NEIGHBOR_COLUMNS}     # the gathered record, [n, max(ks)]
     setup = _grid_setup(args)
-    grid_f1 = hps = searched = searched_with = polished = polished_with = None
-    if setup is not None:
+    grid_f1 = hps = searched = searched_with = polished = polished_with = failed = None
+    search_on = setup is not None and getattr(args, "hparam_search", "host") == "device"
+    polish_on = setup is not None and getattr(args, "lbfgs_polish", "host") == "device"
+    if setup is not None and cell is not None:
+        hps = M.grid_points(*setup)
+        try:
+            grid_f1 = ops.grid_f1_ks(cell.rec(None, zero_d1, True), cell.y_val, [[hp[n] for n in M.HP_NAMES] for hp in hps], ks)[0]
+        except Exception as e:
+            failed = _error_text(e)
+    elif setup is not None:
         df_val = df.query('sset == "val"')
         hps = M.grid_points(*setup)
         rec_deep = _device_rec(df_val, device)
         grid_f1 = ops.grid_f1_ks(rec_deep, df_val["is_mislabel"].values, [[hp[n] for n in M.HP_NAMES] for hp in hps], ks)[0]
-        if getattr(args, "hparam_search", "host") == "device":
+        if search_on:
             searched_with = (SEARCH_STARTS, SEARCH_METHODS, list(setup[1]), list(setup[2]))
             searched = ops.local_search(rec_deep, df_val["is_mislabel"].values, SEARCH_STARTS, SEARCH_METHODS, setup[1], setup[2],
                                         ks=ks)
-        if getattr(args, "lbfgs_polish", "host") == "device":
+        if polish_on:
             polished_with = (SEARCH_STARTS, list(setup[1]), list(setup[2]))
             polished = ops.lbfgs_polish(rec_deep, df_val["is_mislabel"].values, SEARCH_STARTS, setup[1], setup[2], ks=ks)
-    selection = {}
+    selection, errors = {}, {}
     for t, k in enumerate(ks):
         out_k = out_dir / f"knn_k={k}"
         out_k.mkdir(exist_ok=True, parents=True)
@@ -325,10 +587,11 @@ def _sweep_tail(args, df, out_dir, device, ks):
         args_k.knn_k, args_k.output_dir = k, str(out_k)
         with open(out_k / "args.json", "w") as f:
             json.dump(vars(args_k), f, default=str)
-        df_k = df.copy()
-        pre = prefix_record(deep, k)
-        for c in NEIGHBOR_COLUMNS:
-            df_k[c] = list(pre[c].numpy())
+        if cell is None:
+            df_k = df.copy()
+            pre = prefix_record(deep, k)
+            for c in NEIGHBOR_COLUMNS:
+                df_k[c] = list(pre[c].numpy())
 
         def served(asked, t=t):
             assert asked == hps, "the grid of maximize_metric is not the grid lemon_grid_f1_ks was called with"
@@ -345,38 +608,47 @@ def _sweep_tail(args, df, out_dir, device, ks):
             return [x for x, _ in polished[t]]
 
         print(f"---- knn_k = {k} ----")
-        sel_res = _tail(args_k, df_k, out_k, device, batch_grid=served if grid_f1 is not None else None,
-                        local_search=served_search if searched is not None else None,
-                        lbfgs_polish=served_polish if polished is not None else None)
-        entry = None
-        if sel_res is not None:
-            entry = {"selected_val": sel_res.get("selected_val"), **{name: float(sel_res[name]) for name in M.HP_NAMES},
-                     "thres": sel_res.get("thres"),
-                     "splits": {sset: {"AUROC": float(sel_res[sset]["AUROC"]), "F1_optimal": float(sel_res[sset]["F1_optimal"])}
-                                for sset in df_k.sset.unique()}}
-            for key in ("selected_val", "thres"):
-                entry[key] = None if entry[key] is None else float(entry[key])
-        selection[k] = entry
+        if cell is None:
+            sel_res = _tail(args_k, df_k, out_k, device, batch_grid=served if grid_f1 is not None else None,
+                            local_search=served_search if searched is not None else None,
+                            lbfgs_polish=served_polish if polished is not None else None)
+        else:
+            try:
+                if failed is not None:
+                    raise RuntimeError(f"the grid of all ks: {failed}")
+                sel_res = _tail(args_k, cell.frame(k), out_k, device, batch_grid=served if grid_f1 is not None else None,
+                                local_search=cell.search_fn(args.ablation, t) if search_on else None,
+                                lbfgs_polish=cell.polish_fn(args.ablation, t) if polish_on else None, cell=cell)
+            except Exception as e:
+                selection[k], errors[k] = None, _error_text(e)
+                continue
+        selection[k] = _selection_entry(sel_res, df.sset.unique())
     best = None if any(e is None for e in selection.values()) else \
         select_best_k({k: e["selected_val"] for k, e in selection.items()})
     with open(out_dir / "k_selection.json", "w") as f:
         json.dump({"ks": list(ks), "best_k": best, "per_k": {str(k): e for k, e in selection.items()}}, f, indent=1)
-    with open(os.path.join(out_dir, "done"), "w") as f:
-        f.write("done")
+    if not errors:
+        with open(os.path.join(out_dir, "done"), "w") as f:
+            f.write("done")
+    return {k: (selection[k], errors.get(k)) for k in ks}
 
 
 SEARCH_STARTS = [[0] * 6, [0.5] * 6, [1] * 6, [10] * 6]       # the start points and methods the reference hands to maximize_metric
 SEARCH_METHODS = ("Powell", "Nelder-Mead")
 
 
-def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_polish=None):
+def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_polish=None, cell=None):
     """Everything behind the per-sample record: the d1 ablation, the hyper-parameter search, the final score, the metrics and
     the files of a run.  Returns agg_results' entry (None with --real_dataset / --skip_hparam_optim).  batch_grid: serves the
     grid's F1 values in place of the ops.grid_f1 call (the k sweep); local_search: serves the local searches in place of the
     ops.local_search call of --hparam_search device (the k sweep); lbfgs_polish: serves the polished starts in place of the
-    ops.lbfgs_polish call of --lbfgs_polish device (the k sweep)."""
+    ops.lbfgs_polish call of --lbfgs_polish device (the k sweep).  cell: the _CellRecord of a cell sweep, whose device-resident
+    record serves in place of the upload of `df`'s arrays (the same bits); `df` is then the cell's own frame."""
     from . import metrics as M, ops
-    device_rec = lambda frame: _device_rec(frame, device)
+    if cell is None:
+        device_rec = lambda frame, val_only: _device_rec(frame, device)
+    else:
+        device_rec = lambda frame, val_only: cell.rec(args.knn_k, "d1" in args.ablation, val_only)
     sel_res = None
     if "d1" in args.ablation:
         df["d_1"] = 0.0
@@ -385,7 +657,7 @@ def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_p
         res = {"df": df}
     else:
         df_val = df.query('sset == "val"')
-        rec_val = device_rec(df_val)
+        rec_val = device_rec(df_val, True)
         y_val = df_val["is_mislabel"].values
         score_fn = lambda hp: ops.lemon_score(rec_val, hp).cpu().numpy()      # K5 on the device-resident val arrays
         crit = "know_val_labels"
@@ -400,12 +672,13 @@ def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_p
                 best_f1, best_thres = M.optimize_f1_efficient(y_val, df_val["d_1"].values, return_thres=True)
             else:
                 grid, force_zero, force_one = _grid_setup(args)
-                rec_lbfgs = {c: (df_val[c].values if c == "d_1" else np.stack(df_val[c].values))
-                             for c in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")}
                 if local_search is None and getattr(args, "hparam_search", "host") == "device":
                     local_search = lambda x0s, methods, fz, fo: ops.local_search(rec_val, y_val, x0s, methods, fz, fo)
                 if lbfgs_polish is None and getattr(args, "lbfgs_polish", "host") == "device":
                     lbfgs_polish = lambda x0s, fz, fo: [x for x, _ in ops.lbfgs_polish(rec_val, y_val, x0s, fz, fo)]
+                rec_lbfgs = None if lbfgs_polish is not None else \
+                    {c: (df_val[c].values if c == "d_1" else np.stack(df_val[c].values))      # the host polish's own copy
+                     for c in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")}
                 best, best_f1, best_thres = M.maximize_metric(
                     score_fn, y_val, grid, SEARCH_STARTS, M.optimize_f1_efficient, {}, scipy_methods=SEARCH_METHODS,
                     local_search=local_search, lbfgs_polish=lbfgs_polish,
@@ -415,7 +688,7 @@ def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_p
                     (lambda hps: ops.grid_f1(rec_val, y_val, [[hp[n] for n in M.HP_NAMES] for hp in hps])[0]))
             sel_res = dict(zip(M.HP_NAMES, best))
             sel_res.update(thres=best_thres, selected_val=best_f1)
-        s, dn, dm = ops.lemon_score(device_rec(df), sel_res, return_dn=True)
+        s, dn, dm = ops.lemon_score(device_rec(df, False), sel_res, return_dn=True)
         df[f"{crit}_pred_score"] = s.cpu().numpy()
         df[f"{crit}_d_n"], df[f"{crit}_d_m"] = dn.cpu().numpy(), dm.cpu().numpy()
         df_val = df.query('sset == "val"')
