@@ -17,6 +17,9 @@ per-sample record schema (:291-307).  Differences, all explicit:
     reference's grid that only change the tail of a run, in ONE run -- embed and search once on the whole validation set, then
     the tail of a run per cell on the rows that run would have drawn, the record kept on the device across the cells
     (<output_dir>/[dist_type=<d>/][subset_val_set=<m>/][ablation=<a>/][knn_k=<k>/], cell_sweep.json).  Compose with both others.
+Behind the per-sample record every run takes one path: _cell_tails walks the cells of dist_type x subset_val_set x ablation x
+knn_k -- an axis that is not swept has one level, a plain run is the one cell -- and runs _tail on each, on a frame and on
+device arrays that the _Record of its (metric, subset) hands out; that class makes every grid, search and polish launch.
 """
 import argparse
 import copy
@@ -36,6 +39,12 @@ from .cli_common import CLF_DATASETS, add_extension_flags  # noqa: F401  (CLF_DA
 
 ABLATIONS = ("none", "tau_1", "tau_2", "tau_1_2", "beta", "gamma", "multimodal_baseline", "d1", "only_gamma",
              "only_beta")                                                      # run_lemon.py:49-50, in the parser's order
+FORCE_MASKS = {"none": ([], []), "d1": ([], ["beta"]), "tau_1": (["tau_1_n", "tau_1_m"], []), "tau_2": (["tau_2_n", "tau_2_m"], []),
+               "tau_1_2": (["tau_1_n", "tau_1_m", "tau_2_n", "tau_2_m"], []), "beta": (["beta"], []),
+               "gamma": (["gamma"], [])}                  # the ablations that search: ablation -> (force_zero, force_one)
+SEARCH_STARTS = [[0] * 6, [0.5] * 6, [1] * 6, [10] * 6]       # the start points and methods the reference hands to maximize_metric
+SEARCH_METHODS = ("Powell", "Nelder-Mead")
+NEIGHBOR_COLUMNS = ("dists_n", "D_n", "dists_tr_n", "dists_m", "D_m", "dists_tr_m")      # of the per-sample record, beside d_1
 
 
 def build_parser():
@@ -112,36 +121,41 @@ def build_parser():
 
 
 DIST_TYPES = ("cosine", "euclidean")
+MAX_SWEEP_K = 63       # max + 1 <= LEMON_MAX_K: the train split searches k + 1 (include/lemon_hip.h)
+
+
+def _parse_list(flag, text, such_as, convert=str, refuse=lambda value: None):
+    """The values of a sweep flag, comma-separated in `text`: converted, de-duplicated, in the given order.  Refused
+    (ValueError): an empty list, a list `convert` cannot read, a value `refuse` has a sentence about."""
+    parts = [t.strip() for t in str(text).split(",") if t.strip()]
+    if not parts:
+        axis = flag[len("--"):-len("_sweep")]
+        raise ValueError(f"{flag}: the list is empty; expected comma-separated values of {axis} such as {such_as}")
+    try:
+        values = [convert(t) for t in parts]
+    except ValueError:
+        raise ValueError(f"{flag}: {text!r} is not a comma-separated list of integers") from None
+    out = []
+    for value in values:
+        why = refuse(value)
+        if why:
+            raise ValueError(f"{flag}: {why}")
+        if value not in out:
+            out.append(value)
+    return out
 
 
 def parse_dist_sweep(text):
     """'euclidean,cosine,cosine' -> ['euclidean', 'cosine']: de-duplicated, order kept.  Refused (ValueError): an empty list, a
     name that is not a dist_type."""
-    parts = [t.strip() for t in str(text).split(",") if t.strip()]
-    if not parts:
-        raise ValueError("--dist_type_sweep: the list is empty; expected comma-separated values of dist_type such as cosine,euclidean")
-    out = []
-    for t in parts:
-        if t not in DIST_TYPES:
-            raise ValueError(f"--dist_type_sweep: {t!r} is not a dist_type (cosine|euclidean)")
-        if t not in out:
-            out.append(t)
-    return out
-
-
-MAX_SWEEP_K = 63       # max + 1 <= LEMON_MAX_K: the train split searches k + 1 (include/lemon_hip.h)
+    return _parse_list("--dist_type_sweep", text, "cosine,euclidean",
+                       refuse=lambda t: None if t in DIST_TYPES else f"{t!r} is not a dist_type (cosine|euclidean)")
 
 
 def parse_k_sweep(text):
     """'10,1,5,5' -> [1, 5, 10]: sorted, de-duplicated.  Refused (ValueError): an empty list, anything that is not an integer,
     a value < 1, a largest value whose train-split search (k + 1) would pass LEMON_MAX_K."""
-    parts = [t.strip() for t in str(text).split(",") if t.strip()]
-    if not parts:
-        raise ValueError("--knn_k_sweep: the list is empty; expected comma-separated values of knn_k such as 1,2,5,10")
-    try:
-        ks = sorted({int(t) for t in parts})
-    except ValueError:
-        raise ValueError(f"--knn_k_sweep: {text!r} is not a comma-separated list of integers") from None
+    ks = sorted(_parse_list("--knn_k_sweep", text, "1,2,5,10", int))
     if ks[0] < 1:
         raise ValueError(f"--knn_k_sweep: every knn_k must be >= 1, got {ks[0]}")
     if ks[-1] > MAX_SWEEP_K:
@@ -153,39 +167,27 @@ def parse_k_sweep(text):
 def parse_ablation_sweep(text):
     """'d1,none,d1' -> ['d1', 'none']: de-duplicated, order kept; 'all' -> the ten values of --ablation in the parser's order.
     Refused (ValueError): an empty list, a name that is not an ablation."""
-    parts = [t.strip() for t in str(text).split(",") if t.strip()]
-    if not parts:
-        raise ValueError("--ablation_sweep: the list is empty; expected comma-separated values of ablation such as "
-                         "none,multimodal_baseline, or all")
-    if parts == ["all"]:
+    if str(text).replace(",", " ").split() == ["all"]:
         return list(ABLATIONS)
-    out = []
-    for t in parts:
-        if t not in ABLATIONS:
-            raise ValueError(f"--ablation_sweep: {t!r} is not an ablation ({'|'.join(ABLATIONS)}, or all alone)")
-        if t not in out:
-            out.append(t)
-    return out
+    return _parse_list("--ablation_sweep", text, "none,multimodal_baseline, or all", refuse=lambda t: None if t in ABLATIONS else
+                       f"{t!r} is not an ablation ({'|'.join(ABLATIONS)}, or all alone)")
 
 
 def parse_subset_sweep(text):
     """'-1,10,50,10' -> [-1, 10, 50]: de-duplicated, order kept; -1 = the whole validation set.  Refused (ValueError): an empty
     list, anything that is not an integer, 0, a value below -1."""
-    parts = [t.strip() for t in str(text).split(",") if t.strip()]
-    if not parts:
-        raise ValueError("--subset_val_set_sweep: the list is empty; expected comma-separated values of subset_val_set such as "
-                         "-1,10,50,100")
-    try:
-        ms = [int(t) for t in parts]
-    except ValueError:
-        raise ValueError(f"--subset_val_set_sweep: {text!r} is not a comma-separated list of integers") from None
-    out = []
-    for m in ms:
-        if m == 0 or m < -1:
-            raise ValueError(f"--subset_val_set_sweep: a subset has at least one row (or is -1, the whole validation set), got {m}")
-        if m not in out:
-            out.append(m)
-    return out
+    return _parse_list("--subset_val_set_sweep", text, "-1,10,50,100", int, lambda m: None if m == -1 or m > 0 else
+                       f"a subset has at least one row (or is -1, the whole validation set), got {m}")
+
+
+SWEEP_FLAGS = {"dist_type_sweep": parse_dist_sweep, "subset_val_set_sweep": parse_subset_sweep,
+               "ablation_sweep": parse_ablation_sweep, "knn_k_sweep": parse_k_sweep}       # outermost to innermost level
+
+
+def parse_sweeps(args):
+    """{axis: its parsed list, None where its flag is not given}; ValueError with the refusal of the first list that has one"""
+    return {flag[:-len("_sweep")]: None if getattr(args, flag) is None else parse(getattr(args, flag))
+            for flag, parse in SWEEP_FLAGS.items()}
 
 
 def cell_path(dist_type=None, subset_val_set=None, ablation=None, knn_k=None):
@@ -237,24 +239,12 @@ def main(argv=None):
     from .cli_common import run_with_tee
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.knn_k_sweep is not None:
-        try:
-            parse_k_sweep(args.knn_k_sweep)
-        except ValueError as e:
-            parser.error(str(e))
-    if args.dist_type_sweep is not None:
-        try:
-            parse_dist_sweep(args.dist_type_sweep)
-        except ValueError as e:
-            parser.error(str(e))
-        if args.dist_sweep_margin < 0:
-            parser.error("--dist_sweep_margin: must be >= 0")
-    for text, parse in ((args.ablation_sweep, parse_ablation_sweep), (args.subset_val_set_sweep, parse_subset_sweep)):
-        if text is not None:
-            try:
-                parse(text)
-            except ValueError as e:
-                parser.error(str(e))
+    try:
+        parse_sweeps(args)
+    except ValueError as e:
+        parser.error(str(e))
+    if args.dist_type_sweep is not None and args.dist_sweep_margin < 0:
+        parser.error("--dist_sweep_margin: must be >= 0")
     return run_with_tee(_run, args)
 
 
@@ -283,7 +273,8 @@ def _run(args):
         torch.from_numpy(tr_prompt_ids).to(device)
     sel = torch.from_numpy(np.asarray(train_indices_in_compr)).to(device)
     algo = {"auto": None, "f32": _lib.ALGO_F32_MFMA, "bf16": _lib.ALGO_BF16_FILTER}[args.algo]
-    metrics = parse_dist_sweep(args.dist_type_sweep) if getattr(args, "dist_type_sweep", None) is not None else None
+    swept = parse_sweeps(args)              # axis -> its values, None where the run has the one value of `args`
+    metrics, sweep = swept["dist_type"], swept["knn_k"]
     dist_names = metrics or [args.dist_type]
     both = len(dist_names) == 2             # one IP pair serves both metrics (LemonDB.neighbors_metrics)
     db = LemonDB(full_img[sel], full_txt[sel], tuple(dist_names) if both else dist_names[0], tr_label_id=full_pid[sel], algo=algo)
@@ -295,7 +286,6 @@ def _run(args):
     in_db_mask = np.zeros(n_train, dtype=np.uint8)
     in_db_mask[train_indices_in_compr] = 1
     names = ["val", "test"] if (args.debug or args.skip_train) else ["train", "val", "test"]
-    sweep = parse_k_sweep(args.knn_k_sweep) if getattr(args, "knn_k_sweep", None) is not None else None
     k = sweep[-1] if sweep else args.knn_k        # a sweep searches once, at its largest k
     frames = {m: [] for m in dist_names}
     sweep_counts = {}
@@ -330,7 +320,7 @@ def _run(args):
                 frames[m].append(pd.DataFrame({
                     **meta_columns(sname, n_total, meta, flips),
                     "d_1": host["d_1"].astype(np.float64),
-                    **{c: list(host[c]) for c in ("dists_n", "D_n", "dists_tr_n", "dists_m", "D_m", "dists_tr_m")},
+                    **{c: list(host[c]) for c in NEIGHBOR_COLUMNS},
                 }))
     torch.cuda.synchronize(device)
     timedelta = (datetime.now() - start_t).total_seconds()
@@ -340,9 +330,8 @@ def _run(args):
         return 0
     n_samples = sum(len(f) for f in frames[dist_names[0]])
     print(f"Finished {n_samples} samples in {timedelta} seconds; avg of {timedelta / n_samples}s per sample")
-    subsets = parse_subset_sweep(args.subset_val_set_sweep) if getattr(args, "subset_val_set_sweep", None) is not None else None
-    ablations = parse_ablation_sweep(args.ablation_sweep) if getattr(args, "ablation_sweep", None) is not None else None
-    cells = [] if (subsets is not None or ablations is not None) else None
+    cell_sweep = swept["subset_val_set"] is not None or swept["ablation"] is not None
+    cells = []
     for m in dist_names:
         df = pd.concat(frames[m], ignore_index=True)
         args_m, out_m = args, out_dir
@@ -354,38 +343,24 @@ def _run(args):
             with open(out_m / "args.json", "w") as f:
                 json.dump(vars(args_m), f, default=str)
             print(f"==== dist_type = {m} ====")
-        if cells is not None:
-            cells += _cell_tails(args_m, df, out_dir, device, m if metrics is not None else None, subsets, ablations, sweep)
-        elif sweep:
-            _sweep_tail(args_m, df, out_m, device, sweep)
-        else:
-            _tail(args_m, df, out_m, device)
-    failed = [c for c in cells or [] if c["status"] != "ok"]
-    if cells is not None:
+        cells += _cell_tails(args_m, df, out_dir, device, m if metrics is not None else None, swept["subset_val_set"],
+                             swept["ablation"], sweep, record_errors=cell_sweep)
+    failed = [c for c in cells if c["status"] != "ok"]
+    if cell_sweep:
         with open(out_dir / "cell_sweep.json", "w") as f:
-            json.dump({"axes": {"dist_type": metrics, "subset_val_set": subsets, "ablation": ablations, "knn_k": sweep},
-                       "cells": cells}, f, indent=1)
+            json.dump({"axes": swept, "cells": cells}, f, indent=1)
         for c in failed:
             print(f"cell {c['path']}: {c['error']}", file=sys.stderr)
     if metrics is not None:
         with open(out_dir / "dist_sweep.json", "w") as f:
             json.dump({"metrics": list(dist_names), "margin": int(args.dist_sweep_margin) if both else None, "knn_k": int(k),
                        "splits": sweep_counts}, f, indent=1)
-    if (metrics is not None or cells is not None) and not failed:
+    if (metrics is not None or cell_sweep) and not failed:
         with open(os.path.join(out_dir, "done"), "w") as f:
             f.write("done")
     if world > 1:
         torch.distributed.destroy_process_group()
     return 1 if failed else 0
-
-
-NEIGHBOR_COLUMNS = ("dists_n", "D_n", "dists_tr_n", "dists_m", "D_m", "dists_tr_m")
-
-
-def _device_rec(frame, device):
-    return {c: torch.from_numpy(np.stack(frame[c].values).astype(np.float32)).to(device)
-            for c in ("D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")} | \
-           {"d_1": torch.from_numpy(frame["d_1"].values.astype(np.float32)).to(device)}
 
 
 def _grid_setup(args):
@@ -397,11 +372,6 @@ def _grid_setup(args):
            {"beta": [0, 5, 10], "gamma": [0, 5, 10], "tau_1": [0, 1], "tau_2": [0, 5]}
     force_zero, force_one = FORCE_MASKS[args.ablation]
     return grid, list(force_zero), list(force_one)
-
-
-FORCE_MASKS = {"none": ([], []), "d1": ([], ["beta"]), "tau_1": (["tau_1_n", "tau_1_m"], []), "tau_2": (["tau_2_n", "tau_2_m"], []),
-               "tau_1_2": (["tau_1_n", "tau_1_m", "tau_2_n", "tau_2_m"], []), "beta": (["beta"], []),
-               "gamma": (["gamma"], [])}                  # the ablations that search: ablation -> (force_zero, force_one)
 
 
 def _selection_entry(sel_res, ssets):
@@ -418,22 +388,32 @@ def _selection_entry(sel_res, ssets):
     return entry
 
 
-def _error_text(e):
-    import traceback
-    traceback.print_exc()
-    return f"{type(e).__name__}: {e}"
+def _attempt(record_errors, fn, *args):
+    """-> (fn(*args), None).  record_errors (a cell sweep): an exception is printed and kept, -> (None, its text), and the
+    sweep goes on; elsewhere there is no handler in the way and it propagates."""
+    if not record_errors:
+        return fn(*args), None
+    try:
+        return fn(*args), None
+    except Exception as e:
+        import traceback
+        traceback.print_exc()
+        return None, f"{type(e).__name__}: {e}"
 
 
-class _CellRecord:
-    """The record of one (metric, subset) for all of its cells.  The neighbour arrays are uploaded ONCE, at the depth they were
-    searched at, and stay on the device: the prefix of a knn_k, the validation rows and the zeroed d_1 of the d1 ablation are
-    taken there (the same float32 bits _device_rec makes from a cell's own frame).  frame(k): the frame of a cell, its
-    neighbour columns shared between the cells of a k.  search_fn / polish_fn: what maximize_metric asks for, served from ONE
-    ops.local_search / ops.lbfgs_polish launch per distinct d_1 column -- the real one and the zeroed one -- that covers every
-    ablation of the sweep that searches and every k; made on first use, inside the cell that asks."""
+class _Record:
+    """The record of one (metric, subset), for every tail on it: of the one cell of a plain run as of all cells of a sweep.
+    The only place that uploads record arrays and that calls ops.grid_f1 / grid_f1_ks / local_search / lbfgs_polish.  The
+    neighbour arrays are uploaded ONCE, at the depth they were searched at, and stay on the device: the prefix of a knn_k, the
+    validation rows and the zeroed d_1 of the d1 ablation are taken there (the same float32 bits an upload of a cell's own
+    frame gives).  frame(k): the frame of a cell, its neighbour columns shared between the cells of a k.  grid_fn / search_fn /
+    polish_fn: what maximize_metric asks for.  With a k axis (`ks`) the grid of an ablation is ONE ops.grid_f1_ks for all ks
+    (grid_ks); the searches and the polishes are ONE ops.local_search / ops.lbfgs_polish launch per distinct d_1 column -- the
+    real one and the zeroed one -- that covers every ablation of the run that searches and every k, made on first use, inside
+    the cell that asks."""
 
     def __init__(self, df, deep, rows, device, ks, ablations):
-        self.df, self.ks, self.ablations = df, ks, [a for a in ablations if a in FORCE_MASKS]
+        self.df, self.device, self.ks, self.ablations = df, device, ks, [a for a in ablations if a in FORCE_MASKS]
         self.host = deep if rows is None else {c: v[rows] for c, v in deep.items()}       # numpy [n, depth] a neighbour column
         self.dev = {c: torch.from_numpy(v.astype(np.float32)).to(device) for c, v in self.host.items()}
         d1 = torch.from_numpy(df["d_1"].values.astype(np.float32)).to(device)
@@ -441,10 +421,10 @@ class _CellRecord:
         is_val = (df["sset"] == "val").values
         self.val_rows = torch.from_numpy(np.flatnonzero(is_val)).to(device)
         self.y_val = df["is_mislabel"].values[is_val]
-        self._recs, self._frames, self._launched = {}, {}, {}
+        self._recs, self._frames, self._grids, self._launched = {}, {}, {}, {}
 
     def rec(self, k, zero_d1, val_only):
-        """_device_rec of the frame of knn_k = k (None: the depth searched at), of all rows or of the validation rows"""
+        """the device arrays of the frame of knn_k = k (None: the depth searched at), of all rows or of the validation rows"""
         if (k, val_only) not in self._recs:
             out = {}
             for c, v in self.dev.items():
@@ -465,18 +445,41 @@ class _CellRecord:
             self._frames[k] = base
         return self._frames[k].copy(deep=False)
 
+    def grid_ks(self, ablation, grid):
+        """(the points of `grid` under the masks of `ablation`, their F1 [len(ks), G]): ONE ops.grid_f1_ks, kept"""
+        from . import metrics as M, ops
+        if ablation not in self._grids:
+            hps = M.grid_points(grid, *FORCE_MASKS[ablation])
+            f1 = ops.grid_f1_ks(self.rec(None, "d1" in ablation, True), self.y_val, [[hp[n] for n in M.HP_NAMES] for hp in hps],
+                                self.ks)[0]
+            self._grids[ablation] = hps, f1
+        return self._grids[ablation]
+
     def _launch(self, what, ablation):
         from . import ops
         zero = "d1" in ablation
         if (what, zero) not in self._launched:
             group = [a for a in self.ablations if ("d1" in a) == zero]
             rec, masks = self.rec(None, zero, True), [FORCE_MASKS[a] for a in group]
+            # one mask pair goes as force_zero / force_one, several as cells=: the same launch, the result per cell
+            how = dict(cells=masks) if len(masks) > 1 else dict(force_zero=masks[0][0], force_one=masks[0][1])
             if what == "search":
-                res = ops.local_search(rec, self.y_val, SEARCH_STARTS, SEARCH_METHODS, ks=self.ks, cells=masks)
+                res = ops.local_search(rec, self.y_val, SEARCH_STARTS, SEARCH_METHODS, ks=self.ks, **how)
             else:
-                res = ops.lbfgs_polish(rec, self.y_val, SEARCH_STARTS, ks=self.ks, cells=masks)
-            self._launched[(what, zero)] = dict(zip(group, res))
+                res = ops.lbfgs_polish(rec, self.y_val, SEARCH_STARTS, ks=self.ks, **how)
+            self._launched[(what, zero)] = dict(zip(group, res if len(masks) > 1 else [res]))
         return self._launched[(what, zero)][ablation]
+
+    def grid_fn(self, ablation, grid, t=None):
+        """maximize_metric's batch_grid for a cell of `ablation`: its own ops.grid_f1 at the record's depth, or row t of grid_ks"""
+        def serve(asked):
+            from . import metrics as M, ops
+            if t is None:
+                return ops.grid_f1(self.rec(None, "d1" in ablation, True), self.y_val, [[hp[n] for n in M.HP_NAMES] for hp in asked])[0]
+            hps, f1 = self.grid_ks(ablation, grid)
+            assert asked == hps, "the grid of maximize_metric is not the grid lemon_grid_f1_ks was called with"
+            return f1[t]
+        return serve
 
     def search_fn(self, ablation, t=None):
         """maximize_metric's local_search for a cell of `ablation` (and of the t-th k of the sweep)"""
@@ -499,165 +502,84 @@ class _CellRecord:
         return serve
 
 
-def _cell_tails(args, df, out_root, device, dist, subsets, ablations, ks):
-    """The tails of every (subset, ablation, knn_k) cell of one metric on the record `df` that was searched once -> the entries
-    of cell_sweep.json.  dist / subsets / ablations / ks: the swept axes (None: not swept, the value of `args` holds and the
-    directory has no such level).  A cell whose tail raises is recorded with the exception's text and the sweep goes on."""
+def _cell_tails(args, df, out_root, device, dist, subsets, ablations, ks, record_errors):
+    """The tail of a run for every cell of dist_type x subset_val_set x ablation x knn_k of one metric, on the record `df` that
+    was searched once (at max(ks)) -> the entries of cell_sweep.json.  dist / subsets / ablations / ks: the swept axes (None:
+    not swept -- the value of `args` holds, the directory has no such level; a plain run is the one cell with no level at all).
+    A cell below <output_dir>[/dist_type=<d>] gets its own args.json; k_selection.json and done sit one level above knn_k=.
+    record_errors: a cell whose tail raises is recorded with the exception's text and the sweep goes on (_attempt)."""
     deep = {c: np.stack(df[c].values) for c in NEIGHBOR_COLUMNS}       # stacked once a metric; a subset takes rows of it
     entries = []
     for m in subsets or [None]:
         rows = None if m in (None, -1) else _subset_rows(df, m, args.data_seed)
         frame = df if rows is None else subset_val_frame(df, m, args.data_seed, rows)
-        args_s = copy.copy(args)
-        if m is not None:
-            args_s.subset_val_set = m
-        cell = _CellRecord(frame, deep, rows, device, ks, ablations or [args.ablation])
-        for a in ablations or [args.ablation]:
-            where = dict(dist_type=dist, subset_val_set=m, ablation=a if ablations is not None else None)
-            args_a = copy.copy(args_s)
-            args_a.ablation = a
+        record = _Record(frame, deep, rows, device, ks, ablations or [args.ablation])
+        for a in ablations or [None]:
+            where = dict(dist_type=dist, subset_val_set=m, ablation=a)
             out_a = out_root / cell_path(**where)
-            out_a.mkdir(exist_ok=True, parents=True)
-            args_a.output_dir = str(out_a)
-            print(f"==== {cell_path(**where)} ====")
+            args_a = copy.copy(args)
+            if m is not None:
+                args_a.subset_val_set = m
+            if a is not None:
+                args_a.ablation = a
+            if m is not None or a is not None:
+                print(f"==== {cell_path(**where)} ====")
+            setup, failed = _grid_setup(args_a), None
+            if ks and setup is not None:            # in front of the k loop: a failure is that of every k
+                _, failed = _attempt(record_errors, record.grid_ks, args_a.ablation, setup[0])
+            results = {}
+            for t, k in enumerate(ks) if ks else [(None, None)]:
+                out_k = out_root / cell_path(**where, knn_k=k)
+                out_k.mkdir(exist_ok=True, parents=True)
+                args_k = copy.copy(args_a)
+                if k is not None:
+                    args_k.knn_k = k
+                if not (m is None and a is None and k is None):
+                    args_k.output_dir = str(out_k)
+                    with open(out_k / "args.json", "w") as f:
+                        json.dump(vars(args_k), f, default=str)
+                if k is not None:
+                    print(f"---- knn_k = {k} ----")
+
+                def tail():
+                    if failed is not None:
+                        raise RuntimeError(f"the grid of all ks: {failed}")
+                    return _selection_entry(_tail(args_k, record.frame(k), out_k, record, t), frame.sset.unique())
+                results[k] = _attempt(record_errors, tail)
             if ks:
-                results = _sweep_tail(args_a, frame, out_a, device, ks, cell=cell)
-            else:
-                with open(out_a / "args.json", "w") as f:
-                    json.dump(vars(args_a), f, default=str)
-                try:
-                    device_mode = lambda flag: _grid_setup(args_a) is not None and getattr(args_a, flag, "host") == "device"
-                    sel_res = _tail(args_a, cell.frame(None), out_a, device, cell=cell,
-                                    local_search=cell.search_fn(a) if device_mode("hparam_search") else None,
-                                    lbfgs_polish=cell.polish_fn(a) if device_mode("lbfgs_polish") else None)
-                    results = {None: (_selection_entry(sel_res, frame.sset.unique()), None)}
-                except Exception as e:
-                    results = {None: (None, _error_text(e))}
+                best = None if any(entry is None for entry, _ in results.values()) else \
+                    select_best_k({k: entry["selected_val"] for k, (entry, _) in results.items()})
+                with open(out_a / "k_selection.json", "w") as f:
+                    json.dump({"ks": list(ks), "best_k": best, "per_k": {str(k): entry for k, (entry, _) in results.items()}}, f,
+                              indent=1)
+                if not any(error for _, error in results.values()):
+                    with open(os.path.join(out_a, "done"), "w") as f:
+                        f.write("done")
             for k, (entry, error) in results.items():
                 entries.append({"path": cell_path(**where, knn_k=k), "dist_type": args_a.dist_type,
-                                "subset_val_set": int(args_a.subset_val_set), "ablation": a,
+                                "subset_val_set": int(args_a.subset_val_set), "ablation": args_a.ablation,
                                 "knn_k": int(args_a.knn_k if k is None else k),
                                 **({"status": "ok"} if error is None else {"status": "error", "error": error}), **(entry or {})})
     return entries
 
 
-def _sweep_tail(args, df, out_dir, device, ks, cell=None):
-    """The tail of a run for every k of the sweep, on the prefix of the record searched at max(ks); the grid of all ks comes
-    from ONE ops.grid_f1_ks call made in front of the loop and, with --hparam_search device, the local searches of all ks from
-    ONE ops.local_search call beside it; with --lbfgs_polish device the polishes of all ks from ONE ops.lbfgs_polish call.
-    cell: the _CellRecord of a cell sweep -- the device record, the frames and the searches come from it (shared with the
-    other ablations of its subset), `df` is not written to, and a k whose tail raises is recorded and the others go on.
-    -> {k: (k_selection.json's entry, None | the exception's text)}."""
-    import copy
-    import json
-    from . import metrics as M, ops
-    from .neighbors import prefix_record
-    zero_d1 = "d1" in args.ablation
-    if cell is None:
-        if zero_d1:
-            df["d_1"] = 0.0
-        deep = {c: torch.from_numpy(np.stack(df[c].values)) for c in NEIGHBOR_COLUMNS}     # the gathered record, [n, max(ks)]
-    setup = _grid_setup(args)
-    grid_f1 = hps = searched = searched_with = polished = polished_with = failed = None
-    search_on = setup is not None and getattr(args, "hparam_search", "host") == "device"
-    polish_on = setup is not None and getattr(args, "lbfgs_polish", "host") == "device"
-    if setup is not None and cell is not None:
-        hps = M.grid_points(*setup)
-        try:
-            grid_f1 = ops.grid_f1_ks(cell.rec(None, zero_d1, True), cell.y_val, [[hp[n] for n in M.HP_NAMES] for hp in hps], ks)[0]
-        except Exception as e:
-            failed = _error_text(e)
-    elif setup is not None:
-        df_val = df.query('sset == "val"')
-        hps = M.grid_points(*setup)
-        rec_deep = _device_rec(df_val, device)
-        grid_f1 = ops.grid_f1_ks(rec_deep, df_val["is_mislabel"].values, [[hp[n] for n in M.HP_NAMES] for hp in hps], ks)[0]
-        if search_on:
-            searched_with = (SEARCH_STARTS, SEARCH_METHODS, list(setup[1]), list(setup[2]))
-            searched = ops.local_search(rec_deep, df_val["is_mislabel"].values, SEARCH_STARTS, SEARCH_METHODS, setup[1], setup[2],
-                                        ks=ks)
-        if polish_on:
-            polished_with = (SEARCH_STARTS, list(setup[1]), list(setup[2]))
-            polished = ops.lbfgs_polish(rec_deep, df_val["is_mislabel"].values, SEARCH_STARTS, setup[1], setup[2], ks=ks)
-    selection, errors = {}, {}
-    for t, k in enumerate(ks):
-        out_k = out_dir / f"knn_k={k}"
-        out_k.mkdir(exist_ok=True, parents=True)
-        args_k = copy.copy(args)
-        args_k.knn_k, args_k.output_dir = k, str(out_k)
-        with open(out_k / "args.json", "w") as f:
-            json.dump(vars(args_k), f, default=str)
-        if cell is None:
-            df_k = df.copy()
-            pre = prefix_record(deep, k)
-            for c in NEIGHBOR_COLUMNS:
-                df_k[c] = list(pre[c].numpy())
-
-        def served(asked, t=t):
-            assert asked == hps, "the grid of maximize_metric is not the grid lemon_grid_f1_ks was called with"
-            return grid_f1[t]
-
-        def served_search(x0s, methods, force_zero, force_one, t=t):
-            asked = ([list(x0) for x0 in x0s], tuple(methods), list(force_zero), list(force_one))
-            assert asked == searched_with, "the searches of maximize_metric are not the ones lemon_hparam_search was called with"
-            return searched[t]
-
-        def served_polish(x0s, force_zero, force_one, t=t):
-            asked = ([list(x0) for x0 in x0s], list(force_zero), list(force_one))
-            assert asked == polished_with, "the polishes of maximize_metric are not the ones lemon_lbfgs_polish was called with"
-            return [x for x, _ in polished[t]]
-
-        print(f"---- knn_k = {k} ----")
-        if cell is None:
-            sel_res = _tail(args_k, df_k, out_k, device, batch_grid=served if grid_f1 is not None else None,
-                            local_search=served_search if searched is not None else None,
-                            lbfgs_polish=served_polish if polished is not None else None)
-        else:
-            try:
-                if failed is not None:
-                    raise RuntimeError(f"the grid of all ks: {failed}")
-                sel_res = _tail(args_k, cell.frame(k), out_k, device, batch_grid=served if grid_f1 is not None else None,
-                                local_search=cell.search_fn(args.ablation, t) if search_on else None,
-                                lbfgs_polish=cell.polish_fn(args.ablation, t) if polish_on else None, cell=cell)
-            except Exception as e:
-                selection[k], errors[k] = None, _error_text(e)
-                continue
-        selection[k] = _selection_entry(sel_res, df.sset.unique())
-    best = None if any(e is None for e in selection.values()) else \
-        select_best_k({k: e["selected_val"] for k, e in selection.items()})
-    with open(out_dir / "k_selection.json", "w") as f:
-        json.dump({"ks": list(ks), "best_k": best, "per_k": {str(k): e for k, e in selection.items()}}, f, indent=1)
-    if not errors:
-        with open(os.path.join(out_dir, "done"), "w") as f:
-            f.write("done")
-    return {k: (selection[k], errors.get(k)) for k in ks}
-
-
-SEARCH_STARTS = [[0] * 6, [0.5] * 6, [1] * 6, [10] * 6]       # the start points and methods the reference hands to maximize_metric
-SEARCH_METHODS = ("Powell", "Nelder-Mead")
-
-
-def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_polish=None, cell=None):
+def _tail(args, df, out_dir, record, t=None):
     """Everything behind the per-sample record: the d1 ablation, the hyper-parameter search, the final score, the metrics and
-    the files of a run.  Returns agg_results' entry (None with --real_dataset / --skip_hparam_optim).  batch_grid: serves the
-    grid's F1 values in place of the ops.grid_f1 call (the k sweep); local_search: serves the local searches in place of the
-    ops.local_search call of --hparam_search device (the k sweep); lbfgs_polish: serves the polished starts in place of the
-    ops.lbfgs_polish call of --lbfgs_polish device (the k sweep).  cell: the _CellRecord of a cell sweep, whose device-resident
-    record serves in place of the upload of `df`'s arrays (the same bits); `df` is then the cell's own frame."""
+    the files of a run.  Returns agg_results' entry (None with --real_dataset / --skip_hparam_optim).  df: the cell's own frame,
+    written to; record: the _Record it is a frame of, which holds the device arrays and serves the grid, the local searches of
+    --hparam_search device and the polishes of --lbfgs_polish device; t: the index of the cell's k in record.ks (None: no k
+    axis, the record as searched)."""
     from . import metrics as M, ops
-    if cell is None:
-        device_rec = lambda frame, val_only: _device_rec(frame, device)
-    else:
-        device_rec = lambda frame, val_only: cell.rec(args.knn_k, "d1" in args.ablation, val_only)
+    k, zero_d1 = None if t is None else record.ks[t], "d1" in args.ablation
     sel_res = None
-    if "d1" in args.ablation:
+    if zero_d1:
         df["d_1"] = 0.0
 
     if args.real_dataset or args.skip_hparam_optim:
         res = {"df": df}
     else:
         df_val = df.query('sset == "val"')
-        rec_val = device_rec(df_val, True)
+        rec_val = record.rec(k, zero_d1, True)
         y_val = df_val["is_mislabel"].values
         score_fn = lambda hp: ops.lemon_score(rec_val, hp).cpu().numpy()      # K5 on the device-resident val arrays
         crit = "know_val_labels"
@@ -672,23 +594,20 @@ def _tail(args, df, out_dir, device, batch_grid=None, local_search=None, lbfgs_p
                 best_f1, best_thres = M.optimize_f1_efficient(y_val, df_val["d_1"].values, return_thres=True)
             else:
                 grid, force_zero, force_one = _grid_setup(args)
-                if local_search is None and getattr(args, "hparam_search", "host") == "device":
-                    local_search = lambda x0s, methods, fz, fo: ops.local_search(rec_val, y_val, x0s, methods, fz, fo)
-                if lbfgs_polish is None and getattr(args, "lbfgs_polish", "host") == "device":
-                    lbfgs_polish = lambda x0s, fz, fo: [x for x, _ in ops.lbfgs_polish(rec_val, y_val, x0s, fz, fo)]
+                local_search = record.search_fn(args.ablation, t) if args.hparam_search == "device" else None
+                lbfgs_polish = record.polish_fn(args.ablation, t) if args.lbfgs_polish == "device" else None
                 rec_lbfgs = None if lbfgs_polish is not None else \
                     {c: (df_val[c].values if c == "d_1" else np.stack(df_val[c].values))      # the host polish's own copy
-                     for c in ("d_1", "D_n", "dists_tr_n", "dists_n", "D_m", "dists_tr_m", "dists_m")}
+                     for c in ("d_1",) + NEIGHBOR_COLUMNS}
                 best, best_f1, best_thres = M.maximize_metric(
                     score_fn, y_val, grid, SEARCH_STARTS, M.optimize_f1_efficient, {}, scipy_methods=SEARCH_METHODS,
                     local_search=local_search, lbfgs_polish=lbfgs_polish,
                     force_zero=force_zero, force_one=force_one, rec_for_lbfgs=rec_lbfgs,
-                    lbfgs_device=str(device) if args.lbfgs_device == "cuda" else "cpu",
-                    batch_grid=batch_grid or
-                    (lambda hps: ops.grid_f1(rec_val, y_val, [[hp[n] for n in M.HP_NAMES] for hp in hps])[0]))
+                    lbfgs_device=str(record.device) if args.lbfgs_device == "cuda" else "cpu",
+                    batch_grid=record.grid_fn(args.ablation, grid, t))
             sel_res = dict(zip(M.HP_NAMES, best))
             sel_res.update(thres=best_thres, selected_val=best_f1)
-        s, dn, dm = ops.lemon_score(device_rec(df, False), sel_res, return_dn=True)
+        s, dn, dm = ops.lemon_score(record.rec(k, zero_d1, False), sel_res, return_dn=True)
         df[f"{crit}_pred_score"] = s.cpu().numpy()
         df[f"{crit}_d_n"], df[f"{crit}_d_m"] = dn.cpu().numpy(), dm.cpu().numpy()
         df_val = df.query('sset == "val"')

@@ -128,7 +128,8 @@ def test_the_draws_of_different_m_are_no_prefixes_of_one_another():
 # ---- what the cells of one subset share ------------------------------------------------------------------------------------------
 def test_cells_share_the_neighbour_arrays_and_not_what_they_write():
     import torch
-    from lemon_amd.run_lemon import _CellRecord, _device_rec
+    from lemon_amd.run_lemon import _Record as _CellRecord
+    from tests.tailfx import device_rec as _device_rec
     df = _frame()
     before = df.copy(deep=True)
     deep = {c: np.stack(df[c].values) for c in NEIGHBOR_COLUMNS}
