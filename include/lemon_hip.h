@@ -682,6 +682,53 @@ double lemon_lbfgs_proxy_host(const float *d1, const float *D_n, const float *di
                               int64_t n, int kmax, int k, int force_zero, int force_one, const double *x, double *grad);
 int lemon_lbfgs_math_host(int fn, const double *x, int64_t count, double *out);
 
+/* metrics.eval_metrics (lib/metrics/utils.py:273-441: optimize_f1 :273-284, f1_with_pred_prev_constraint(2) :298-322,
+ * f1_with_local_minima_finder :327-349, the counts of binary_metrics :351-405, prob_metrics :408-412, eval_metrics :414-441)
+ * for every split of a run as ONE launch sequence.  score [total] float64 and y [total] uint8 (non-zero = mislabelled) hold S
+ * segments side by side; segs [S] says where: rows offset .. offset + n of both arrays, n >= 1, segments disjoint and inside
+ * [0, total), total < 2^31.  thres_from = -1: a FREE segment -- its three thresholds are found on its own rows with
+ * `prevalence` (F1_optimal: the 100-candidate sweep, the last candidate at the maximum; F1_prev: scipy's bisect on the
+ * predicted prevalence, the squared-gap fminbound where bisect raises; F1_heuristic: the median local minimum of the Gaussian
+ * KDE on 1 000 grid points, else the median of >= 2 maxima, else np.mean in numpy's summation order).  thres_from = t >= 0:
+ * the segment is counted at the thresholds of the free segment t (before or behind it) and its record repeats them: the
+ * val -> train / val / test pattern of a run is one free and one fixed segment per split.
+ * out[s]: AUROC exact from integer pair counts over groups of equal scores, correctly rounded once; AUPRC = sum over groups
+ * (pos_g / P) precision_g in a fixed order; (TP, FP, FN, TN) at each threshold; status 0 ok, 1 a non-finite score, 2 one class
+ * only, 3 a free segment with fewer than two rows, 4 a free segment whose variance is zero (where scipy's Cholesky raises),
+ * 5 a fixed segment whose free segment has a status -- the first that applies, in the order the host path raises; a status
+ * concerns its own segment only (5 follows its source), and the fields of a record with a status are not meaningful.
+ * kde_branch 1 median of > 1 minima, 2 the one minimum, 3 median of maxima, 4 np.mean; bisect_fallback 1 where fminbound
+ * served F1_prev.  The arithmetic is csrc/eval_metrics_core.hpp: thresholds and counts equal the host path by their bits (the
+ * KDE's where scipy's density separates neighbouring grid points), the device and the host twin agree bit for bit.
+ * lemon_eval_metrics: every pointer is a device pointer; ws: lemon_eval_metrics_workspace_bytes(total, S, S_free) bytes with
+ * S_free >= the number of free segments (for S > 1 the size comes from hipcub's segmented sort, which needs a HIP device:
+ * LEMON_E_HIP without one), 256-byte aligned; nothing is allocated, every launch goes to `stream`; the call
+ * waits for the stream once, to check segs before anything is launched.  Refused with LEMON_E_INVALID, nothing written: a
+ * null pointer, S outside [1, 65535], total outside [1, 2^31), a segment with offset < 0 or n < 1, one that passes `total` or
+ * overlaps another, a thres_from that is neither -1 nor the index of a free segment, a short or misaligned workspace.
+ * lemon_eval_metrics_host: the same header with the lanes looped on the host, host pointers, std::stable_sort; for the
+ * tests, no product path calls it.  lemon_eval_metrics_kde_host: test-only, the KDE of one free segment of n >= 2 host rows as
+ * the twin evaluates it: grid [1000] and dens [1000]; LEMON_E_INVALID for a null pointer, n < 2, a non-finite score or zero
+ * variance. */
+#define LEMON_EVAL_OK 0
+#define LEMON_EVAL_NONFINITE 1
+#define LEMON_EVAL_ONE_CLASS 2
+#define LEMON_EVAL_FEW_ROWS 3
+#define LEMON_EVAL_ZERO_VARIANCE 4
+#define LEMON_EVAL_SOURCE 5
+typedef struct LemonEvalSegment { int64_t offset, n; double prevalence; int32_t thres_from, pad; } LemonEvalSegment;
+typedef struct LemonEvalRecord {
+    double auroc, auprc, thres[3];
+    int64_t counts[3][4];
+    int32_t status, kde_branch, bisect_fallback, pad;
+} LemonEvalRecord;
+int64_t lemon_eval_metrics_workspace_bytes(int64_t total, int S, int S_free); /* < 0: LEMON_E_* */
+int lemon_eval_metrics(const double *score, const uint8_t *y, int64_t total, const LemonEvalSegment *segs, int S,
+                       void *ws, int64_t ws_bytes, LemonEvalRecord *out, void *stream);
+int lemon_eval_metrics_host(const double *score, const uint8_t *y, int64_t total, const LemonEvalSegment *segs, int S,
+                            LemonEvalRecord *out);
+int lemon_eval_metrics_kde_host(const double *score, int64_t n, double *grid, double *dens);
+
 /* ---- k-means on caption embeddings + the deep-kNN label score ------------------------ */
 
 /* FaissKMeans.predict = index.search(x, 1) (lib/datasets/clustering.py:38-41) and the assignment step of faiss.Kmeans.train

@@ -36,6 +36,7 @@ EXPORTS = [
     "lemon_hparam_search_workspace_bytes", "lemon_hparam_search", "lemon_hparam_search_host", "lemon_hparam_objective_host",
     "lemon_hparam_search_set_test_knobs",
     "lemon_lbfgs_polish", "lemon_lbfgs_polish_host", "lemon_lbfgs_proxy_host", "lemon_lbfgs_math_host",
+    "lemon_eval_metrics_workspace_bytes", "lemon_eval_metrics", "lemon_eval_metrics_host", "lemon_eval_metrics_kde_host",
 ]
 
 
@@ -56,6 +57,19 @@ class PolishResult(ctypes.Structure):      # LemonPolishResult
     _fields_ = [("x", ctypes.c_double * 6), ("loss", ctypes.c_double), ("nfev", ctypes.c_int32), ("nit", ctypes.c_int32),
                 ("status", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
+
+class EvalSegment(ctypes.Structure):       # LemonEvalSegment
+    _fields_ = [("offset", ctypes.c_int64), ("n", ctypes.c_int64), ("prevalence", ctypes.c_double), ("thres_from", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
+class EvalRecord(ctypes.Structure):        # LemonEvalRecord
+    _fields_ = [("auroc", ctypes.c_double), ("auprc", ctypes.c_double), ("thres", ctypes.c_double * 3),
+                ("counts", (ctypes.c_int64 * 4) * 3), ("status", ctypes.c_int32), ("kde_branch", ctypes.c_int32),
+                ("bisect_fallback", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+EVAL_OK, EVAL_NONFINITE, EVAL_ONE_CLASS, EVAL_FEW_ROWS, EVAL_ZERO_VARIANCE, EVAL_SOURCE = range(6)      # LEMON_EVAL_*
 
 POLISH_OUTER_STEPS = 20                    # optimizer.step calls of torch_minimize (lib/metrics/utils.py:129-141)
 
@@ -212,6 +226,11 @@ def load():
     lib.lemon_lbfgs_proxy_host.argtypes = [vp] * 8 + [c_i64, c_int, c_int, c_int, c_int, vp, vp]
     lib.lemon_lbfgs_proxy_host.restype = ctypes.c_double
     lib.lemon_lbfgs_math_host.argtypes = [c_int, vp, c_i64, vp]
+    lib.lemon_eval_metrics_workspace_bytes.argtypes = [c_i64, c_int, c_int]
+    lib.lemon_eval_metrics_workspace_bytes.restype = c_i64
+    lib.lemon_eval_metrics.argtypes = [vp, vp, c_i64, vp, c_int, vp, c_i64, vp, vp]
+    lib.lemon_eval_metrics_host.argtypes = [vp, vp, c_i64, vp, c_int, vp]
+    lib.lemon_eval_metrics_kde_host.argtypes = [vp, c_i64, vp, vp]
     _lib = lib
     return lib
 

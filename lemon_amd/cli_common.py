@@ -59,6 +59,39 @@ def add_extension_flags(p):
     return p
 
 
+def add_eval_metrics_flag(p):
+    """--eval_metrics of the CLIs whose tail is metrics.eval_metrics on the validation rows and on every split"""
+    p.add_argument("--eval_metrics", default="host", choices=["host", "device"],
+                   help="where the threshold metrics behind the score run: 'host' = metrics.eval_metrics in scipy / sklearn, once "
+                        "on the validation rows and once per split (the reference's way); 'device' = all of them in one call "
+                        "(lemon_eval_metrics): same thresholds, counts and count-derived values bit for bit, AUROC exact and "
+                        "AUPRC in a fixed order (within n 2^-52 of sklearn); a split with one class raises ValueError there")
+    return p
+
+
+class EvalLayout:
+    """The rows metrics.eval_metrics runs on behind a score, laid out for ops.eval_metrics: the validation rows as the free
+    segment, then every split of df.sset.unique() as a fixed segment at the validation thresholds.  Row indices and labels
+    are uploaded ONCE for a frame; a call gathers the score on the device and makes one ops.eval_metrics call."""
+
+    def __init__(self, df, device):
+        sset = df["sset"].values
+        self.ssets = list(df.sset.unique())
+        parts = [np.flatnonzero(sset == "val")] + [np.flatnonzero(sset == name) for name in self.ssets]
+        self.bounds = np.cumsum([0] + [len(part) for part in parts])
+        rows = np.concatenate(parts)
+        self.rows = torch.from_numpy(rows).to(device)
+        self.y = torch.from_numpy(df["is_mislabel"].values[rows].astype(bool).astype(np.uint8)).to(device)
+
+    def __call__(self, score, prevalence):
+        """score: float64 tensor [len(df)] -> (the validation call's dict, {sset: the dict of its fixed-threshold call})"""
+        from . import ops
+        segments = [(int(lo), int(hi - lo), float(prevalence), -1 if i == 0 else 0)
+                    for i, (lo, hi) in enumerate(zip(self.bounds[:-1], self.bounds[1:]))]
+        res = ops.eval_metrics(score.to(device=self.rows.device, dtype=torch.float64)[self.rows], self.y, segments)
+        return res[0], dict(zip(self.ssets, res[1:]))
+
+
 def prepare(args):
     hparams = vars(args)
     out_dir = Path(args.output_dir)

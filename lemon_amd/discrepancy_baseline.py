@@ -22,7 +22,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from .cli_common import add_extension_flags
+from .cli_common import add_eval_metrics_flag, add_extension_flags
 
 
 METHODS = ("dis_x", "dis_y", "div_x", "div_y")
@@ -49,6 +49,7 @@ def build_parser():
     p.add_argument("--debug", action="store_true")
     p.add_argument("--skip_train", action="store_true")
     add_extension_flags(p)          # local weights / data (not in the reference)
+    add_eval_metrics_flag(p)
     p.add_argument("--knn_k_sweep", default=None, type=str,
                    help="comma-separated knn_k values, e.g. 1,2,5,10,15,20,30,50 (the reference's grid, experiments.py:141-177): "
                         "embed, build the DB and its self-kNN cache and search ONCE at the largest, then write a run per value "
@@ -142,9 +143,13 @@ def _run(args):
     df = pd.concat(frames, ignore_index=True)
     scores = np.concatenate(scores)
     out_dir = ctx.out_dir
+    layout = None
+    if args.eval_metrics == "device":       # the rows of the validation set and of every split: uploaded once for the run
+        from .cli_common import EvalLayout
+        layout = EvalLayout(df, device)
     if sweep is None:
         df["pred_score"] = scores.astype(np.float64)
-        _tail(args, df, out_dir)
+        _tail(args, df, out_dir, layout)
         return 0
     methods, ks = sweep
     results = {}
@@ -159,7 +164,7 @@ def _run(args):
             df_mk = df.copy()
             df_mk["pred_score"] = scores[:, mi, ti].astype(np.float64)
             print(f"---- method = {m}, knn_k = {k} ----")
-            res = _tail(args_mk, df_mk, out_mk)
+            res = _tail(args_mk, df_mk, out_mk, layout)
             results.setdefault(m, {})[str(k)] = {sset: {"AUROC": float(r["AUROC"]), "F1_optimal": float(r["F1_optimal"])}
                                                  for sset, r in res.items()}
     with open(out_dir / "sweep.json", "w") as f:
@@ -169,19 +174,24 @@ def _run(args):
     return 0
 
 
-def _tail(args, df, out_dir):
+def _tail(args, df, out_dir, layout=None):
     """Everything behind the per-sample scores: the files of a run (scores.csv unless --skip_train, res.pkl, done) and its
-    metrics.  Returns agg_results."""
+    metrics.  Returns agg_results.  layout: the EvalLayout of `df` with --eval_metrics device -- the metrics of the validation
+    rows and of every split are one ops.eval_metrics call on the uploaded score; None: metrics.eval_metrics on the host."""
     from . import metrics as M
     if not args.skip_train:
         df.to_csv(out_dir / "scores.csv", index=False)
-    df_val = df.query('sset == "val"')
     prev = df.loc[df.sset == "val", "is_mislabel"].sum() / (df.sset == "val").sum()
-    thress = M.eval_metrics(df_val["is_mislabel"], df_val["pred_score"], prevalence=prev)
-    selection_results = {}
+    if layout is not None:
+        selection_results = layout(torch.from_numpy(df["pred_score"].values.astype(np.float64)), prev)[1]
+    else:
+        df_val = df.query('sset == "val"')
+        thress = M.eval_metrics(df_val["is_mislabel"], df_val["pred_score"], prevalence=prev)
+        selection_results = {}
+        for sset in df.sset.unique():
+            sub = df.loc[df.sset == sset]
+            selection_results[sset] = M.eval_metrics(sub["is_mislabel"], sub["pred_score"], prevalence=prev, fix_thress=thress)
     for sset in df.sset.unique():
-        sub = df.loc[df.sset == sset]
-        selection_results[sset] = M.eval_metrics(sub["is_mislabel"], sub["pred_score"], prevalence=prev, fix_thress=thress)
         print(f"{sset}: AUROC {selection_results[sset]['AUROC']:.4f}  F1 {selection_results[sset]['F1_optimal']:.4f}")
     pickle.dump({"df": df, "agg_results": selection_results}, (out_dir / "res.pkl").open("wb"))
     with open(os.path.join(out_dir, "done"), "w") as f:

@@ -899,6 +899,102 @@ def lbfgs_polish(rec, y, x0s, force_zero=(), force_one=(), ks=None, return_info=
     return shaped(rows)
 
 
+EVAL_THRESHOLDS = ("F1_optimal", "F1_prev", "F1_heuristic")      # the order of LemonEvalRecord.thres / .counts
+
+
+def eval_segments(segments):
+    """[(offset, n, prevalence, thres_from), ...] -> a ctypes array of LemonEvalSegment"""
+    arr = (_lib.EvalSegment * len(segments))()
+    for g, (offset, n, prevalence, thres_from) in zip(arr, segments):
+        g.offset, g.n, g.prevalence, g.thres_from, g.pad = int(offset), int(n), float(prevalence), int(thres_from), 0
+    return arr
+
+
+def _binary_from_counts(tp, fp, fn, tn, suffix):
+    """metrics.binary_metrics(targets, score >= t, suffix=suffix) from the four counts: its keys in its order, its arithmetic
+    on Python ints (sklearn's accuracy, F1 and balanced accuracy are these quotients), its Python types -- the ints 0 / 1
+    where the reference assigns ints."""
+    n = tp + fp + fn + tn
+    res = {"accuracy": (tp + tn) / n, "F1": 2.0 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0, "n_samples": n}
+    res.update(TN=tn, FN=fn, TP=tp, FP=fp, error=fn + fp)
+    res["TPR"], res["FNR"] = ((tp / (tp + fn), fn / (tp + fn)) if tp + fn else (0, 1))
+    res["FPR"], res["TNR"] = ((fp / (fp + tn), tn / (fp + tn)) if fp + tn else (1, 0))
+    res["PPV"] = tp / (tp + fp) if tp + fp > 0 else 0
+    res["NPV"] = tn / (tn + fn) if tn + fn > 0 else 0
+    res["pred_prevalence"] = (tp + fp) / n
+    res["prevalence"] = (tp + fn) / n
+    if tp + fn and fp + tn:
+        res["balanced_acc"] = (tn / (tn + fp) + tp / (tp + fn)) / 2.0
+    return {f"{k}{suffix}": v for k, v in res.items()}
+
+
+def eval_status_error(s, status):
+    """The exception of segment s with a non-zero status: the class the host path raises first (sklearn's and gaussian_kde's
+    ValueError, numpy.linalg.LinAlgError where scipy's Cholesky meets a zero variance)."""
+    if status == _lib.EVAL_ZERO_VARIANCE:
+        return np.linalg.LinAlgError(f"eval_metrics: segment {s}: the scores have zero variance, the KDE's covariance is singular")
+    why = {_lib.EVAL_NONFINITE: "a score is not finite", _lib.EVAL_ONE_CLASS: "only one class is present, AUROC is not defined",
+           _lib.EVAL_FEW_ROWS: "the KDE needs at least two rows",
+           _lib.EVAL_SOURCE: "the segment its thresholds come from could not be served"}.get(status, f"status {status}")
+    return ValueError(f"eval_metrics: segment {s}: {why}")
+
+
+def eval_record_dict(rec, source=None):
+    """A LemonEvalRecord -> the dict of metrics.eval_metrics: its keys in its order, its Python types (AUROC / AUPRC float, the
+    F1_optimal and F1_heuristic thresholds numpy.float64, the F1_prev threshold the float of scipy's bisect or fminbound's
+    numpy.float64).  source: the record of the free segment a fixed one was counted at (None: rec is free itself)."""
+    source = rec if source is None else source
+    t_opt, t_prev, t_heur = (float(t) for t in rec.thres)
+    out = {"AUROC": float(rec.auroc), "AUPRC": float(rec.auprc), "F1_optimal_thres": np.float64(t_opt),
+           "F1_prev_thres": np.float64(t_prev) if source.bisect_fallback else t_prev, "F1_heuristic_thres": np.float64(t_heur)}
+    for k, name in enumerate(EVAL_THRESHOLDS):
+        tp, fp, fn, tn = (int(c) for c in rec.counts[k])
+        out.update(_binary_from_counts(tp, fp, fn, tn, name[len("F1"):]))
+    return out
+
+
+def eval_records_dicts(records, segments):
+    """the dicts of all segments; raises the exception of the first free segment with a status, else of the first fixed one
+    (the host path evaluates the free rows first)"""
+    order = sorted(range(len(segments)), key=lambda s: (segments[s][3] != -1, s))
+    for s in order:
+        if records[s].status != _lib.EVAL_OK:
+            raise eval_status_error(s, records[s].status)
+    return [eval_record_dict(r, None if g[3] == -1 else records[g[3]]) for r, g in zip(records, segments)]
+
+
+def eval_metrics_records(score, y, segments):
+    """lemon_eval_metrics on device tensors: score float64 [total], y uint8 [total], segments [(offset, n, prevalence,
+    thres_from), ...] -> [LemonEvalRecord, ...] (one launch sequence, one copy back; a status is reported, not raised)"""
+    if not (torch.is_tensor(score) and score.is_cuda and torch.is_tensor(y) and y.is_cuda):
+        raise _lib.LemonHipError("eval_metrics: score and y must be CUDA tensors (no CPU fallback for the device path)")
+    if score.dtype != torch.float64 or y.dtype != torch.uint8 or score.dim() != 1 or y.shape != score.shape:
+        raise TypeError("eval_metrics: score float64 [total] and y uint8 [total] expected")
+    score, y, dev = score.contiguous(), y.contiguous(), score.device
+    S, total = len(segments), score.shape[0]
+    lib = _lib.load()
+    need = lib.lemon_eval_metrics_workspace_bytes(total, S, sum(1 for g in segments if g[3] == -1))
+    if need < 0:
+        _lib.check(int(need), "lemon_eval_metrics_workspace_bytes")
+    segs_d = torch.frombuffer(bytearray(bytes(eval_segments(segments))), dtype=torch.uint8).to(dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(S * ctypes.sizeof(_lib.EvalRecord), dtype=torch.uint8, device=dev)
+    _call("lemon_eval_metrics", dev, ptr(score), ptr(y), total, ptr(segs_d), S, ptr(ws), need, ptr(out))
+    return list((_lib.EvalRecord * S).from_buffer_copy(out.cpu().numpy().tobytes()))
+
+
+def eval_metrics(score, y, segments):
+    """metrics.eval_metrics for every segment of one device-resident score in ONE call (lemon_eval_metrics): a free segment
+    (thres_from -1) finds its three thresholds on its own rows, a fixed one is counted at the thresholds of the free segment
+    thres_from names -- the val -> train / val / test pattern of a run.  -> one dict per segment with the keys, order and
+    Python types of metrics.eval_metrics; thresholds, counts and count-derived values equal the host path by their bits, AUROC
+    is the correctly rounded exact value and AUPRC a fixed-order sum (both within n 2^-52 of sklearn).  A segment that cannot
+    be served raises what the host path raises first: ValueError (a non-finite score, one class, fewer than two free rows),
+    numpy.linalg.LinAlgError (zero variance)."""
+    segments = [tuple(g) for g in segments]
+    return eval_records_dicts(eval_metrics_records(score, y, segments), segments)
+
+
 def _stack_col(df, col, device):
     return torch.from_numpy(np.stack(df[col].values).astype(np.float32, copy=False)).to(device)
 

@@ -17,6 +17,8 @@ per-sample record schema (:291-307).  Differences, all explicit:
     reference's grid that only change the tail of a run, in ONE run -- embed and search once on the whole validation set, then
     the tail of a run per cell on the rows that run would have drawn, the record kept on the device across the cells
     (<output_dir>/[dist_type=<d>/][subset_val_set=<m>/][ablation=<a>/][knn_k=<k>/], cell_sweep.json).  Compose with both others.
+  * extension flag --eval_metrics device: the threshold metrics behind the score -- metrics.eval_metrics on the validation rows
+    and on every split -- as ONE ops.eval_metrics call per cell on the score tensor (lemon_eval_metrics); default host.
 Behind the per-sample record every run takes one path: _cell_tails walks the cells of dist_type x subset_val_set x ablation x
 knn_k -- an axis that is not swept has one level, a plain run is the one cell -- and runs _tail on each, on a frame and on
 device arrays that the _Record of its (metric, subset) hands out; that class makes every grid, search and polish launch.
@@ -34,7 +36,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from .cli_common import CLF_DATASETS, add_extension_flags  # noqa: F401  (CLF_DATASETS re-exported: run_lemon.py:32)
+from .cli_common import CLF_DATASETS, add_eval_metrics_flag, add_extension_flags  # noqa: F401  (CLF_DATASETS re-exported: run_lemon.py:32)
 
 
 ABLATIONS = ("none", "tau_1", "tau_2", "tau_1_2", "beta", "gamma", "multimodal_baseline", "d1", "only_gamma",
@@ -91,6 +93,7 @@ def build_parser():
                         "from Python on --lbfgs_device (the reference's way; a few seconds a knn_k, launch-bound); 'device' = every "
                         "polish of a run in one launch (lemon_lbfgs_polish), the same optimiser restated in fixed-order IEEE double: "
                         "the candidates are a function of the record alone; they are scored exactly afterwards, as before")
+    add_eval_metrics_flag(p)
     p.add_argument("--knn_k_sweep", default=None, type=str,
                    help="comma-separated knn_k values, e.g. 1,2,5,10,15,20,30,50 (the reference's grid, experiments.py:86): embed, build "
                         "the DB and search ONCE at the largest, then run the tail of a --knn_k run for every value on the prefix "
@@ -403,7 +406,8 @@ def _attempt(record_errors, fn, *args):
 
 class _Record:
     """The record of one (metric, subset), for every tail on it: of the one cell of a plain run as of all cells of a sweep.
-    The only place that uploads record arrays and that calls ops.grid_f1 / grid_f1_ks / local_search / lbfgs_polish.  The
+    The only place that uploads record arrays and that calls ops.grid_f1 / grid_f1_ks / local_search / lbfgs_polish /
+    eval_metrics.  The
     neighbour arrays are uploaded ONCE, at the depth they were searched at, and stay on the device: the prefix of a knn_k, the
     validation rows and the zeroed d_1 of the d1 ablation are taken there (the same float32 bits an upload of a cell's own
     frame gives).  frame(k): the frame of a cell, its neighbour columns shared between the cells of a k.  grid_fn / search_fn /
@@ -421,7 +425,7 @@ class _Record:
         is_val = (df["sset"] == "val").values
         self.val_rows = torch.from_numpy(np.flatnonzero(is_val)).to(device)
         self.y_val = df["is_mislabel"].values[is_val]
-        self._recs, self._frames, self._grids, self._launched = {}, {}, {}, {}
+        self._recs, self._frames, self._grids, self._launched, self._layout = {}, {}, {}, {}, None
 
     def rec(self, k, zero_d1, val_only):
         """the device arrays of the frame of knn_k = k (None: the depth searched at), of all rows or of the validation rows"""
@@ -444,6 +448,14 @@ class _Record:
                     base[c] = list(np.ascontiguousarray(self.host[c][:, :k]))
             self._frames[k] = base
         return self._frames[k].copy(deep=False)
+
+    def eval_metrics(self, score, prevalence):
+        """--eval_metrics device: (the validation call's dict, {sset: its dict}) of `score`, the device tensor over all rows of
+        the frame, in ONE ops.eval_metrics call; the row indices and labels of the splits are uploaded once for the record"""
+        from .cli_common import EvalLayout
+        if self._layout is None:
+            self._layout = EvalLayout(self.df, self.device)
+        return self._layout(score, prevalence)
 
     def grid_ks(self, ablation, grid):
         """(the points of `grid` under the masks of `ablation`, their F1 [len(ks), G]): ONE ops.grid_f1_ks, kept"""
@@ -612,11 +624,14 @@ def _tail(args, df, out_dir, record, t=None):
         df[f"{crit}_d_n"], df[f"{crit}_d_m"] = dn.cpu().numpy(), dm.cpu().numpy()
         df_val = df.query('sset == "val"')
         prev = df.loc[df.sset == "val", "is_mislabel"].sum() / (df.sset == "val").sum()
-        thress = M.eval_metrics(df_val["is_mislabel"], df_val[f"{crit}_pred_score"], prevalence=prev)
-        for sset in df.sset.unique():
-            sub = df.loc[df.sset == sset]
-            sel_res[sset] = M.eval_metrics(sub["is_mislabel"], sub[f"{crit}_pred_score"], prevalence=prev,
-                                           fix_thress=thress)
+        if args.eval_metrics == "device":              # the free validation rows and every split in one call, on the score tensor
+            sel_res.update(record.eval_metrics(s, prev)[1])
+        else:
+            thress = M.eval_metrics(df_val["is_mislabel"], df_val[f"{crit}_pred_score"], prevalence=prev)
+            for sset in df.sset.unique():
+                sub = df.loc[df.sset == sset]
+                sel_res[sset] = M.eval_metrics(sub["is_mislabel"], sub[f"{crit}_pred_score"], prevalence=prev,
+                                               fix_thress=thress)
         df[["sset", "idx", "actual_label", "noisy_label", "is_mislabel", f"{crit}_pred_score"]].rename(
             columns={f"{crit}_pred_score": "pred_score"}).to_csv(out_dir / f"{crit}_scores.csv")
         res = {"df": df, "agg_results": {crit: sel_res}}
