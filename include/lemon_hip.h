@@ -398,6 +398,9 @@ const float *lemon_index_data(const lemon_index_t *idx);
  * I=-1 and D=-FLT_MAX (IP) / +FLT_MAX (L2).  1 <= k <= LEMON_MAX_K_DEEP (2048; faiss itself has no limit): up to
  * LEMON_MAX_K (64) one scan pass; deeper lists are produced LEMON_MAX_K at a time by key-bounded passes of the exact
  * fp32 scan (each pass admits only rows ranked behind the previous pass's last result: same order, same tie rule).
+ * Non-finite scores follow faiss, whose heaps start at -/+FLT_MAX: a row whose inner product is NaN or -inf, or whose
+ * L2 distance is +inf, is never returned (a list left with fewer than k rows ends in padding, as beyond ntotal); +inf inner products rank first,
+ * ties by ascending index; the L2 expression above is taken literally, so a NaN inside it gives distance 0.
  * Grows an internal workspace on first use of a larger (nq,k): that first call is not
  * graph-capturable; later calls with nq,k no larger only enqueue kernels.  With LEMON_ALGO_AUTO
  * (default) the first LARGE search (ntotal >= 65536, nq*ntotal >= 8e9, d <= 768 -- d <= 1280 once

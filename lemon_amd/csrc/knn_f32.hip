@@ -296,7 +296,9 @@ __global__ __launch_bounds__(NT, 2) void k_scan_f32(ScanParams p) {
             const unsigned jb = (unsigned)(t_begin + jl) * BX + 4 * h;
             if (p.th_pub) {
                 asm volatile("s_waitcnt vmcnt(16)" : "+v"(pub));
-                if (pub > 1u) th = fmaxf(th, lemon_ord2f(pub - 1u));   // strictly below the published bound
+                // strictly below the published bound.  Below +0.0 the order code's next value is -0.0, which is no lower to
+                // '>': a row scoring +0.0 would be refused although it ties the bound, so that step goes on to -denorm_min
+                if (pub > 1u) th = fmaxf(th, lemon_ord2f(pub - (pub == 0x80000000u ? 2u : 1u)));
             }
             if ((unsigned)(t_begin + jl + 1) * BX > (unsigned)p.n) {   // last tile of the database (uniform): padding rows never pass
 #pragma unroll

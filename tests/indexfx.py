@@ -74,7 +74,9 @@ def scan_plan(panels, n_tiles):
     rc = lib.lemon_debug_scan_plan(panels, n_tiles, ctypes.byref(g), ctypes.byref(sp), ip(sb), cap_wgs, ip(pc), ip(sg), cap_segs,
                                    ctypes.byref(ns))
     assert rc == 0
-    return dict(grid=g.value, splits=sp.value, pieces=pc.copy())
+    # seg_begin [grid + 1]: first segment of every workgroup; segs [n_segs, 4]: (panel, first tile, tiles, piece in the panel)
+    return dict(grid=g.value, splits=sp.value, pieces=pc.copy(), seg_begin=sb[:g.value + 1].copy(),
+                segs=sg[:4 * ns.value].reshape(-1, 4).copy())
 
 
 def f32_steps(sequence=F32_SEQUENCE, n=F32_N):

@@ -87,3 +87,58 @@ def test_index_data_view_and_reconstruct(hip):
     assert ix.data().shape == (0, 24)
     ix.add(x)
     assert torch.equal(ix.data(), x) and torch.equal(ix.reconstruct_n(10, 5), x[10:15])
+
+
+# ---- edges of the five dedup kernels (inputs: tests/scanfx.py, their distinct-row counts: tests/test_scan_f32_edges_host.py) ----
+def _on_off(hip, metric, X, Q, k):
+    """search(Q, k) with dedup on and off -> (D, I, nq_distinct) of the folded handle; the two results are bit-identical and the
+    unfolded handle searched every row"""
+    from tests.indexfx import F32, bits_equal, cu, new_index
+    on, off = new_index(hip, metric, X.shape[1], F32, X), new_index(hip, metric, X.shape[1], F32, X, dedup=False)
+    qt = cu(Q)
+    Da, Ia = on.search(qt, k)
+    Db, Ib = off.search(qt, k)
+    assert bits_equal(Ia, Ib), f"I differs in {int((Ia != Ib).sum())} places"
+    assert bits_equal(Da, Db), "D differs"
+    assert off.last_search_info()["nq_distinct"] == Q.shape[0] and on.last_search_info()["nq"] == Q.shape[0]
+    return Da, Ia, on.last_search_info()["nq_distinct"]
+
+
+@pytest.mark.parametrize("metric", ["cosine", "euclidean"])
+@pytest.mark.parametrize("nq", [1024, 1025, 1026, 1027])
+@pytest.mark.parametrize("d", [1, 63, 65, 100])
+def test_dedup_at_odd_widths_and_ragged_row_blocks(hip, oracle, metric, d, nq):
+    """d % 64 != 0: a lane's second trip through the hash and compare loops (none for most lanes at d = 1); nq % 4 != 0: the
+    `row >= n` guard inside a block of four rows"""
+    from tests import scanfx as sx
+    assert (d, nq) in [(a, b) for a in sx.DEDUP_WIDTHS for b in sx.DEDUP_NQS]
+    X, Q = sx.dedup_db(d), sx.dedup_edge_queries(d, nq)
+    D, I, distinct = _on_off(hip, metric, X, Q, sx.DEDUP_K)
+    assert distinct == sx.DEDUP_PROTOS == 40
+    sx.assert_bits(D, I, *oracle.knn(metric, X, Q, sx.DEDUP_K))
+
+
+@pytest.mark.parametrize("metric", ["cosine", "euclidean"])
+def test_dedup_compares_bits_not_values(hip, oracle, metric):
+    """rows one ulp apart, +0.0 against -0.0 (not merged; the results may be equal), permutations of one another, all-NaN rows
+    of equal bits (merged: they get what the unfolded search gives them) and one of another payload (not merged)"""
+    from tests import scanfx as sx
+    Q, rows = sx.dedup_bit_queries()
+    X = sx.dedup_db(sx.DEDUP_BITS_D)
+    D, I, distinct = _on_off(hip, metric, X, Q, sx.DEDUP_K)
+    assert distinct == len({r.tobytes() for r in Q}) == 8
+    sx.assert_bits(D, I, *oracle.knn(metric, X, Q, sx.DEDUP_K))
+    Ic = I.cpu()
+    assert torch.equal(Ic[rows["zero_pos"][0]], Ic[rows["zero_neg"][0]])
+
+
+@pytest.mark.parametrize("metric", ["cosine", "euclidean"])
+@pytest.mark.parametrize("distinct,folded", [(512, 512), (513, 1024)])
+def test_dedup_folds_exactly_up_to_half_the_queries(hip, oracle, metric, distinct, folded):
+    """the 2 U <= nq boundary at nq = 1024: 512 distinct rows fold, 513 do not"""
+    from tests import scanfx as sx
+    Q = sx.dedup_boundary_queries(distinct)
+    X = sx.dedup_db(Q.shape[1])
+    D, I, got = _on_off(hip, metric, X, Q, sx.DEDUP_K)
+    assert got == folded
+    sx.assert_bits(D, I, *oracle.knn(metric, X, Q, sx.DEDUP_K))
