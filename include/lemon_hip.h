@@ -893,6 +893,54 @@ int64_t lemon_jpeg_prog_entropy_workspace_bytes(int64_t batch, int64_t total_ite
 int lemon_jpeg_prog_entropy_par_host(const uint8_t *packet, int64_t packet_bytes, uint8_t *record, int64_t record_cap,
                                      int32_t *status);
 
+/* ---- PNG files on the same path, opt-in (LEMON_PNG=gpu).  lib/datasets/dataloader.py:177-184 opens a frame's down-sampled PNG
+ * with `Image.open(p).convert("RGB")` for mimiccxr_caption, and lib/datasets/dataloader.py:167-198 any PNG of a file dataset.  The
+ * decode is split: chunk parsing (lemon_png_info, lemon_png_idat) and the zlib inflate (Python's zlib, lemon_amd/png_host.py) run
+ * in the workers; unfiltering and the expansion to RGB run on the device (lemon_png_decode).  Between them lies the record
+ * (csrc/png_core.hpp): 256 x 4 palette bytes (R, G, B, 0), then the filtered scanlines as inflated, each behind its filter-type
+ * byte.  The host functions are also exported by liblemon_jpeg_host.so. */
+#define LEMON_PNG_FILTER 13               /* device verdict: a filter-type byte above 4 (PIL raises); RGB region unspecified */
+#define LEMON_PNG_INDEX 14                /* device verdict: a palette index at or above the PLTE count; RGB region unspecified */
+typedef struct LemonPngInfo {
+    int32_t status;                   /* 0 = accepted so far; > 0 = declined, decode with PIL (LemonPngStatus, csrc/png_core.hpp) */
+    int32_t width, height;
+    int32_t colour_type;              /* 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGBA */
+    int32_t channels;                 /* bytes per pixel: 1, 3, 1, 2, 4 */
+    int32_t plte_count;               /* PLTE entries of a palette file, else 0 */
+    int32_t idat_spans;               /* IDAT chunks */
+    int32_t pad;
+    int64_t stride;                   /* width * channels */
+    int64_t record_bytes;             /* 1024 + height * (stride + 1) */
+    int64_t idat_bytes;               /* total IDAT payload */
+    int64_t idat_offset;              /* file offset of the first IDAT payload (the whole stream when idat_spans == 1) */
+    int64_t plte_offset;              /* file offset of the PLTE payload of a palette file, else -1 */
+} LemonPngInfo;
+/* Chunk walk of lib/datasets/dataloader.py:177-184's file: every read bounds-checked, every chunk's CRC-32 verified.  Accepts
+ * 8-bit samples of colour type 0, 2, 3, 4 or 6, not interlaced, consecutive IDAT chunks, IEND present, no acTL; everything
+ * else is declined with its own status.  Returns info->status.  Host only, no GPU. */
+int lemon_png_info(const uint8_t *data, int64_t n, LemonPngInfo *info);
+/* The same walk, copying the concatenated IDAT payload (the zlib stream) into out[0, cap).  Returns the bytes copied, or
+ * -status for a declined file or a buffer that is too small.  Host only, no GPU. */
+int64_t lemon_png_idat(const uint8_t *data, int64_t n, uint8_t *out, int64_t cap);
+/* Device half for a batch (lib/datasets/dataloader.py:184 per image): rec_dev holds the records (rec_bytes long, 16-byte
+ * aligned).  aux_dev (int64 [batch, 8]): record offset (a multiple of 16), height, width, colour type, PLTE count, output
+ * offset, work offset (a multiple of 16), 0.  One workgroup of one wave per image: bands of 64 rows in order, inside a band a
+ * diagonal wavefront (lane = row, one pixel behind the lane above; csrc/png_core.hpp), the filtered bytes and the RGB bytes
+ * staged through LDS in aligned 16-byte pieces.  Writes packed uint8 RGB [h, w, 3] at each image's output offset in out_dev (grey
+ * replicated, alpha dropped, palette looked up) -- the layout lemon_preprocess_ragged reads -- and status_dev int32 [batch]: 0,
+ * LEMON_PNG_FILTER, LEMON_PNG_INDEX, or LEMON_PNG_BUFFER (11) for an image whose record, pixels or work share would leave
+ * rec_bytes / out_bytes / work_bytes (neither read nor written).  No verdict aborts the launch.  work_dev: each image owns
+ * lemon_png_decode_workspace_bytes(1, width) bytes at its work offset. */
+int lemon_png_decode(const uint8_t *rec_dev, int64_t rec_bytes, int64_t batch, const int64_t *aux_dev, uint8_t *work_dev,
+                     int64_t work_bytes, uint8_t *out_dev, int64_t out_bytes, int32_t *status_dev, void *stream);
+/* 16 * batch + 4 * total_width rounded so that every image's share (4 * width rounded up to 16) fits; < 0: LEMON_E_* */
+int64_t lemon_png_decode_workspace_bytes(int64_t batch, int64_t total_width);
+/* lemon_png_decode's schedule with the lanes looped on the host -- the same step functions, so the same pixels and status.  Test
+ * support for lib/datasets/dataloader.py:184's pixels where there is no GPU, and the fuzzer's target; no product path calls it.
+ * Returns 0 unless an argument is invalid. */
+int lemon_png_decode_host(const uint8_t *record, int64_t record_bytes, int32_t h, int32_t w, int32_t colour_type,
+                          int32_t plte_count, uint8_t *rgb, int32_t *status);
+
 /* ---- caption tokenizers on the device, opt-in (LEMON_TOKENIZE=device): the captions cross PCIe as raw bytes and the id matrix is
  * written where the text tower reads it.  Two vocabularies: the CLIP byte-pair encoding and BERT WordPiece.  The device serves
  * the rows inside an envelope -- every byte one of {9, 10, 13, 32 .. 126}, no '&', no "<|", for WordPiece no whitespace-delimited

@@ -432,6 +432,105 @@ def decode_jpegs(files, device, fallback=False, poison=None, entropy="host", pro
     return out
 
 
+def launch_png_decode(data, layout, poison=None):
+    """Enqueue lemon_png_decode on the current stream for the PNG records of a device buffer `data` laid out by a
+    jpeg_host.BatchLayout: their pixels appear at their RaggedImages offsets (lib/datasets/dataloader.py:184's
+    `Image.open(p).convert("RGB")`).  Returns the int32 device tensor of the images' statuses in the order of
+    layout.png_records (0, LEMON_PNG_FILTER, LEMON_PNG_INDEX: the caller decodes those with PIL; None without PNG records).
+    `poison` (a byte, for tests) pre-fills the PNGs' pixel region, the work buffer and the statuses."""
+    from . import _lib
+    import ctypes
+    from .ops import stream_ptr
+    if not getattr(layout, "n_png", 0):
+        return None
+    assert data.is_cuda and data.dtype == torch.uint8 and data.numel() >= layout.total_bytes
+    dev = data.device
+    with torch.cuda.device(dev):
+        work = torch.empty((layout.png_work_bytes,), dtype=torch.uint8, device=dev)
+        status = torch.empty((layout.n_png,), dtype=torch.int32, device=dev)
+        if poison is not None:
+            work.fill_(poison)
+            status.fill_(poison)
+            data[layout.png_decoded_off:].fill_(poison)
+        base, vp = data.data_ptr(), ctypes.c_void_p
+        _lib.check(_lib.load().lemon_png_decode(vp(base), layout.payload_bytes, layout.n_png, vp(base + layout.png_aux_off),
+                                                vp(work.data_ptr()), work.numel(), vp(base), data.numel(), vp(status.data_ptr()),
+                                                stream_ptr(dev)), "lemon_png_decode")
+    return status
+
+
+def decode_pngs(files, device, fallback=False, poison=None):
+    """Decode PNG files on the GPU -> RaggedImages of `Image.open(f).convert("RGB")`'s pixels, bit for bit
+    (lib/datasets/dataloader.py:177-184).  `files`: paths or bytes objects.  The chunk walk and the inflate run here on the host
+    (png_host.py), unfiltering and the expansion to RGB in lemon_png_decode; the statuses are read back once before returning.
+    A file that is declined (16-bit, interlaced, corrupt, not a PNG, a filter byte above 4, a palette index beyond PLTE, ...)
+    raises ValueError naming the status, or with fallback=True is decoded by PIL (whose own exception a corrupt file then
+    raises).  The result carries `layout` (jpeg_host.BatchLayout) and `status` (int32 numpy, per PNG record)."""
+    import io
+    from PIL import Image
+    from . import jpeg_host, png_host
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError("decode_pngs needs a CUDA/HIP device: there is no CPU path")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    lay, items, off, sources = jpeg_host.BatchLayout(), [], 0, []
+    declined = lambda what, status: ValueError(f"{what}: not decodable on the GPU ({png_host.STATUS.get(status, status)})")
+    for f in files:
+        raw = f if isinstance(f, (bytes, bytearray, memoryview)) else open(f, "rb").read()
+        what = "<bytes>" if raw is f else f
+        raw = bytes(raw)
+        rec, info = png_host.decode_record(raw)
+        if rec is None:
+            if not fallback:
+                raise declined(what, info.status)
+            px = np.asarray(Image.open(io.BytesIO(raw)).convert("RGB"), dtype=np.uint8)
+            lay.add_pixels(off, px.shape[0], px.shape[1])
+            items.append((off, px.reshape(-1)))
+            off = (off + px.nbytes + 15) & ~15
+        else:
+            lay.add_png_record(off, rec)
+            sources.append((what, raw))
+            items.append((off, rec.data))
+            off = (off + rec.data.nbytes + 15) & ~15
+    aux = lay.finish(off)
+    buf = torch.empty((max(lay.payload_bytes, 1),), dtype=torch.uint8).pin_memory()
+    flat = buf.numpy()
+    for o, a in items:
+        flat[o:o + a.nbytes] = a
+    if aux.size:
+        flat[lay.aux_off:lay.payload_bytes] = aux.view(np.uint8)
+    data = torch.empty((max(lay.total_bytes, buf.numel()),), dtype=torch.uint8, device=device)
+    data[:buf.numel()].copy_(buf, non_blocking=True)
+    status = launch_png_decode(data, lay, poison)
+    st = status.cpu().numpy() if status is not None else np.zeros(0, np.int32)      # (the one read-back)
+    for k in np.flatnonzero(st):
+        what, raw = sources[k]
+        if not fallback:
+            raise declined(what, int(st[k]))
+        px = np.asarray(Image.open(io.BytesIO(raw)).convert("RGB"), dtype=np.uint8)
+        o, h, w, _ = lay.desc[lay.png_records[k][0]]
+        if px.shape != (h, w, 3):
+            raise declined(what, int(st[k]))
+        data[o:o + px.size].copy_(torch.from_numpy(px.reshape(-1).copy()))
+    out = RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
+    out.layout, out.status = lay, st
+    return out
+
+
+def mimic_image_path(path):
+    """The file lib/datasets/dataloader.py:177-184 opens for a mimiccxr_caption frame path: the fifth path component from the
+    end replaced by `downsampled_files` and the suffix by `.png` when that file exists, else `path` itself."""
+    from pathlib import Path
+    parts = list(Path(path).parts)
+    if len(parts) >= 5:
+        parts[-5] = "downsampled_files"
+        reduced = Path(*parts).with_suffix(".png")
+        if reduced.is_file():
+            return str(reduced)
+    return path
+
+
 def gpu_transform_ragged(images, size=224, patch=0, operand=False):
     """generic_transform of a RaggedImages batch in one lemon_preprocess_ragged call (two launches): float32 [B,3,size,size],
     patch-major [B, (size/P)^2, 3 P^2] with patch=P, or with operand=True a PatchOperand -- row i = image i of the batch, the
@@ -474,7 +573,7 @@ class ImageLabelSet:
       * float32 [N,...] in memory: pixel tensors that are ALREADY what the model consumes (a preprocessed cache);
         passed through unchanged;
       * a list of file paths: with a CUDA device, decoded by worker processes and transformed on the GPU as RaggedImages
-        batches (lemon_amd/loader.py), with LEMON_JPEG=gpu baseline JPEGs with the device half of their decode on the GPU, with LEMON_JPEG=device their Huffman pass too (default pil: all by PIL); otherwise (or with LEMON_DECODE_WORKERS=0) PIL decode + generic_transform in a thread pool.
+        batches (lemon_amd/loader.py), with LEMON_PNG=gpu PNGs unfiltered and expanded on the GPU (default pil), with LEMON_JPEG=gpu baseline JPEGs with the device half of their decode on the GPU, with LEMON_JPEG=device their Huffman pass too (default pil: all by PIL); otherwise (or with LEMON_DECODE_WORKERS=0) PIL decode + generic_transform in a thread pool.
     Labels are ints (class datasets) or strings (captions)."""
 
     def __init__(self, images, clean, noisy, image_size=224, workers=8):
@@ -709,6 +808,8 @@ def get_dataset(name, data_seed, percent_flips=0.40, flip_type="real", data_root
                 raise NotImplementedError(flip_type)
             part = ds.noise_given_dict(part, nd)
             images = np.ascontiguousarray(pixels[part["_row"].values]) if pixels is not None else list(part["path"])
+            if name == "mimiccxr_caption" and pixels is None:
+                images = [mimic_image_path(p) for p in images]       # lib/datasets/dataloader.py:177-184
             out.append(ImageLabelSet(images, list(part["gold_sentence"]), list(part["sentence"]), image_size))
         return tuple(out)
     if name in ("stanford_cars", "mini_imagenet"):

@@ -12,7 +12,11 @@ into the ring, and lemon_jpeg_entropy_device decodes it on the GPU; a file whose
 With PROGRESSIVE = 1 (beside RECORDS 1 or 2) a progressive file is not left to PIL: the progressive host pass writes its record
 (kind 3, the same record) or the progressive packer its packet (kind 4, lemon_jpeg_prog_pack) into the ring.
 
-Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS [PROGRESSIVE]]`), so that not even the lemon_amd package is imported.
+With PNG = 1 a file that starts with the PNG signature goes through png_host (chunk walk in liblemon_jpeg_host.so, inflate by
+Python's zlib) and the ring receives its record -- palette + filtered scanlines, kind 5 -- which lemon_png_decode unfilters and
+expands to the same pixels on the GPU; a file png_host declines falls through to the PIL branch unchanged.
+
+Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS [PROGRESSIVE [PNG]]]`), so that not even the lemon_amd package is imported.
 Protocol (pickled frames on stdin / stdout, in order):
   parent -> worker: ("task", seq, path) | ("free", nbytes) | ("stop",)
   worker -> parent: ("hello", pid, torch_imported)
@@ -20,7 +24,7 @@ Protocol (pickled frames on stdin / stdout, in order):
                     | ("err", seq, path, message)
 `kind` 0: nbytes = h * w * 3 of RGB pixels; `kind` 1: nbytes of coefficient record; `kind` 2: nbytes of scan packet, with
 (components, hs, vs, intervals, scan_bytes); `kind` 3: a record from the progressive host pass; `kind` 4: nbytes of progressive
-packet, with (components, hs, vs, scans, items, levels).
+packet, with (components, hs, vs, scans, items, levels); `kind` 5: nbytes of PNG record, with (colour_type, channels, plte_count).
 The ring is a circular byte buffer of CAPACITY bytes.  An image is written at `offset` once `consumed` bytes (its own plus the
 unused tail skipped when it wraps) are free; the parent returns them with "free" after it has copied the image, in the order
 the results came.  An image larger than the whole ring waits until the ring is empty and goes to a one-off segment
@@ -44,9 +48,13 @@ def main(argv):
     records = len(argv) > 2 and argv[2] == "1"
     packets = len(argv) > 2 and argv[2] == "2"
     progressive = len(argv) > 3 and argv[3] == "1"
-    if records or packets:
+    png = len(argv) > 4 and argv[4] == "1"
+    if records or packets or png:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    if records or packets:
         import jpeg_host
+    if png:
+        import png_host
     inp, out = sys.stdin.buffer, sys.stdout.buffer
     fd = os.open(shm_path, os.O_RDWR)
     ring = mmap.mmap(fd, cap)
@@ -85,6 +93,28 @@ def main(argv):
                 return 0
             continue
         _, seq, path = tasks.popleft()
+        if png:
+            # the chunk walk, then the inflate straight behind the palette in the ring.  Nothing is committed (head, used) until
+            # the stream has ended exactly where the header says; a declined file falls through to PIL below
+            data = None
+            try:
+                with open(path, "rb") as fh:
+                    data = fh.read()
+            except OSError:
+                pass                    # (PIL below reports it)
+            if data is not None and data[:8] == png_host.SIGNATURE:
+                head_info = png_host.info(data)
+                n = head_info.record_bytes
+                if head_info.status == 0 and n + 15 <= cap:
+                    off, consumed = reserve(n + 15)         # (the record starts at a multiple of 16)
+                    at = (off + 15) & ~15
+                    if png_host.fill_record(data, head_info, view[at:at + n]) == 0:
+                        head = off + n + 15
+                        used += consumed
+                        _send(out, ("ok", seq, at, head_info.height, head_info.width, consumed, None, 5, n,
+                                    (head_info.colour_type, head_info.channels, head_info.plte_count)))
+                        continue
+            del data
         if packets:
             # the scan packet, straight into the ring: its capacity is known from the file size, its size after the call; only
             # the bytes it took are committed

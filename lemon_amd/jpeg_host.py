@@ -211,11 +211,20 @@ class BatchLayout:
     16-byte aligned offsets; finish() appends the int64 aux tables of lemon_jpeg_decode and lemon_jpeg_entropy_device to the
     payload, gives every packet a record in the device-only region after it (written by lemon_jpeg_entropy_device) and places
     every JPEG's pixels after that.  `desc` is the RaggedImages table (byte offset, H, W, plan index) in the order the images
-    were added.  `subseq`: bytes per lane of the device Huffman pass (0 = its default)."""
+    were added.  `subseq`: bytes per lane of the device Huffman pass (0 = its default).
+    PNG records (png_host.PngRecord, add_png_record) ride in the same payload; a batch that holds some gains, behind everything a
+    JPEG-only batch holds -- whose bytes and offsets stay what they are --, the aux table of lemon_png_decode at the end of the
+    payload (png_aux_off) and the PNGs' pixels at the end of the buffer (png_decoded_off)."""
 
     def __init__(self, subseq=0):
         self.shapes, self.desc, self.records, self.packets, self.subseq = {}, [], [], [], subseq
         self.prog_packets, self.n_progressive = [], 0
+        self.png_records, self.n_png, self.png_work_bytes = [], 0, 16
+
+    def add_png_record(self, off, rec):
+        """A PNG record (png_host.PngRecord) at payload offset `off`, a multiple of 16."""
+        self.png_records.append((len(self.desc), off, rec.h, rec.w, rec.colour_type, rec.plte_count))
+        self.desc.append([-1, rec.h, rec.w, self.shapes.setdefault((rec.h, rec.w), len(self.shapes))])
 
     def add_packet(self, off, pk):
         """A scan packet at payload offset `off`: its record lies in the device-only region (offset known after finish()).
@@ -247,6 +256,10 @@ class BatchLayout:
         n = len(self.records)
         self.aux_off = _up(off)
         self.payload_bytes = self.aux_off + self.aux_bytes()
+        self.n_png = len(self.png_records)
+        if self.n_png:                 # the PNG aux table: the payload's last part
+            self.png_aux_off = _up(self.payload_bytes)
+            self.payload_bytes = self.png_aux_off + 64 * self.n_png
         # records of the packets: device-only, after the copied payload
         rec = _up(self.payload_bytes)
         self.edesc_off = self.aux_off + 8 * (8 * n + 2 * (n + 1))
@@ -286,4 +299,18 @@ class BatchLayout:
         self.decoded_off = _up(self.rec_end)
         self.total_bytes, self.work_bytes = max(out, 1), max(work, 16)
         self.idct_blocks, self.rgb_blocks, self.n_jpeg = int(apre[-1]), int(bpre[-1]), n
-        return np.concatenate([d8.ravel(), apre, bpre, edesc.ravel(), pdesc.ravel()]) if n else np.zeros(0, np.int64)
+        aux = np.concatenate([d8.ravel(), apre, bpre, edesc.ravel(), pdesc.ravel()]) if n else np.zeros(0, np.int64)
+        if not self.n_png:
+            return aux
+        # the PNGs' pixels follow everything else; lemon_png_decode's table: record offset, h, w, colour type, PLTE count, output
+        # offset, work offset (one uint32 per pixel of a row, include/lemon_hip.h), 0
+        self.png_decoded_off = out = _up(self.total_bytes)
+        g8, work = np.zeros((self.n_png, 8), np.int64), 0
+        for j, (i, roff, h, w, ct, plte) in enumerate(self.png_records):
+            g8[j] = (roff, h, w, ct, plte, out, work, 0)
+            self.desc[i][0] = out
+            out = _up(out + h * w * 3)
+            work += _up(4 * w)
+        self.total_bytes, self.png_work_bytes = out, max(work, 16)
+        pad = np.zeros((self.png_aux_off - self.aux_off) // 8 - aux.size, np.int64)      # (up to the 16-byte boundary)
+        return np.concatenate([aux, pad, g8.ravel()])

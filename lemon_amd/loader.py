@@ -27,6 +27,7 @@ import uuid
 import numpy as np
 
 from .jpeg_host import BatchLayout, JpegPacket, JpegProgPacket, JpegProgRecord, JpegRecord
+from .png_host import PngRecord
 
 _WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_worker.py")
 DEFAULT_RING_BYTES = 1 << 30
@@ -71,6 +72,18 @@ def progressive_default():
     raise ValueError(f"LEMON_JPEG_PROGRESSIVE={env!r}: expected '0' or '1'")
 
 
+def png_default():
+    """How file batches decode PNGs: LEMON_PNG=pil (False: all by PIL in the workers) or gpu (True: chunk walk and inflate in the
+    workers, unfiltering and the expansion to RGB on the GPU).  Default pil until a recorded comparison exists (DESIGN.md
+    section 5); results are identical in both."""
+    env = os.environ.get("LEMON_PNG", "").strip().lower()
+    if env == "gpu":
+        return True
+    if env in ("", "pil"):
+        return False
+    raise ValueError(f"LEMON_PNG={env!r}: expected 'pil' or 'gpu'")
+
+
 def default_workers(world=1):
     """LEMON_DECODE_WORKERS when set (0 = the in-process thread path), else min(8, usable_cpus() // world), at least 1."""
     env = os.environ.get("LEMON_DECODE_WORKERS", "").strip()
@@ -89,11 +102,14 @@ class DecodePool:
     (i, JpegRecord) instead -- its coefficient record, `data` a view of shared memory under the same rule -- and every other
     file as pixels.  With packets=True a baseline JPEG whose header the packer accepts is yielded as (i, JpegPacket): its scan
     packet for lemon_jpeg_entropy_device.  progressive=True (with records or packets): a progressive JPEG is not left to PIL
-    but yielded as (i, JpegProgRecord) -- the same record, from the progressive host pass -- or (i, JpegProgPacket)."""
+    but yielded as (i, JpegProgRecord) -- the same record, from the progressive host pass -- or (i, JpegProgPacket).
+    png=True: a PNG that png_host accepts is yielded as (i, PngRecord) -- palette + filtered scanlines for lemon_png_decode."""
 
-    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False, packets=False, progressive=False):
+    def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False, packets=False, progressive=False,
+                 png=False):
         self.paths = list(paths)
         self.progressive = bool(progressive)
+        self.png = bool(png)
         self.n_workers = default_workers(world) if workers is None else int(workers)
         self.records, self.packets = bool(records) and not packets, bool(packets)
         assert self.n_workers >= 1
@@ -116,7 +132,7 @@ class DecodePool:
                 self.rings.append(np.frombuffer(mmap.mmap(fd, self.cap), np.uint8))
                 os.close(fd)
                 self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap), "2" if self.packets else "1" if self.records else "0",
-                                                    "1" if self.progressive else "0"], stdin=subprocess.PIPE,
+                                                    "1" if self.progressive else "0"] + (["1"] if self.png else []), stdin=subprocess.PIPE,
                                                    stdout=subprocess.PIPE, close_fds=True))
             for p in self.procs:
                 msg = self._read(p, "worker start")
@@ -153,7 +169,7 @@ class DecodePool:
                 raise DecodeError(f"cannot decode image {msg[2]}: {msg[3]}")
             _, seq, off, h, w, consumed, big, kind, n, meta = msg
             assert seq == i, (seq, i)
-            assert kind in (1, 2, 3, 4) or n == h * w * 3, (kind, n, h, w)
+            assert kind in (1, 2, 3, 4, 5) or n == h * w * 3, (kind, n, h, w)
             if big is not None:
                 import mmap
                 fd = os.open(big, os.O_RDONLY)
@@ -165,7 +181,7 @@ class DecodePool:
                 self.held += consumed
                 self.peak_held = max(self.peak_held, self.held)
             last = (k, consumed, big)
-            made = {1: JpegRecord, 2: JpegPacket, 3: JpegProgRecord, 4: JpegProgPacket}.get(kind)
+            made = {1: JpegRecord, 2: JpegPacket, 3: JpegProgRecord, 4: JpegProgPacket, 5: PngRecord}.get(kind)
             yield i, (made(arr, w, h, *meta) if made else arr.reshape(h, w, 3))
         if last is not None:
             self._release(*last)
@@ -215,7 +231,7 @@ class DecodePool:
 
 
 def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, stats=None, slots=3,
-                   device_jpeg=None, progressive=None):
+                   device_jpeg=None, progressive=None, device_png=None):
     """Yield (s, e, RaggedImages of paths[s:e]) over paths[lo:hi] in chunks of `chunk` images, decoded by a DecodePool.
 
     A packing thread copies each chunk's decoded images out of the workers' rings into one of `slots` pinned staging buffers
@@ -235,7 +251,12 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
     image the device declines is read again from its path, decoded by PIL here and copied into its RGB slot (a file PIL cannot
     decode raises DecodeError as in pil mode).  `progressive` (None: LEMON_JPEG_PROGRESSIVE=1; ignored in pil mode): progressive
     files are not left to PIL in the workers but take the progressive Huffman pass, in the workers (gpu) or on the device behind
-    the baseline pass (device); stats["jpeg_progressive"] counts them.  The pool closes (workers exit, segments
+    the baseline pass (device); stats["jpeg_progressive"] counts them.  `device_png` (None: png_default(), LEMON_PNG=gpu): the
+    workers deliver the PNGs they accept as records (palette + filtered scanlines); these ride in the same pinned buffer,
+    lemon_png_decode is enqueued behind the chunk's copy and its statuses take the route of the device Huffman pass's -- an
+    asynchronous copy to pinned memory, the chunk handed out one chunk later, PIL filling the slots of the images the kernel
+    declined (a filter byte above 4, a palette index beyond PLTE); stats["png_records"] counts the records, stats["png_fallback"]
+    those slots.  It composes with every `device_jpeg` mode.  The pool closes (workers exit, segments
     unlinked) when the generator ends, is closed early or raises."""
     import queue
     import threading
@@ -243,9 +264,12 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
 
     import torch
 
-    from .data import RaggedImages, RaggedPlans, launch_jpeg_decode, launch_jpeg_entropy
+    from .data import RaggedImages, RaggedPlans, launch_jpeg_decode, launch_jpeg_entropy, launch_png_decode
     if device_jpeg is None:
         device_jpeg = device_jpeg_default()
+    if device_png is None:
+        device_png = png_default()
+    device_png = bool(device_png)
     packets = device_jpeg == "device"
     if progressive is None:
         progressive = progressive_default()
@@ -307,7 +331,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     t1 = time.perf_counter()
                     if stats is not None:
                         stats["pool_wait_s"] = stats.get("pool_wait_s", 0.0) + t1 - t0
-                    src = a.data if isinstance(a, (JpegRecord, JpegPacket, JpegProgRecord, JpegProgPacket)) else a.reshape(-1)
+                    src = a.data if isinstance(a, (JpegRecord, JpegPacket, JpegProgRecord, JpegProgPacket, PngRecord)) else a.reshape(-1)
                     need = off + src.nbytes
                     buf = room(buf, off, need)
                     np.copyto(buf.numpy()[off:need], src)
@@ -315,6 +339,8 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                         lay.add_packet(off, a)
                     elif isinstance(a, (JpegRecord, JpegProgRecord)):
                         lay.add_record(off, a)
+                    elif isinstance(a, PngRecord):
+                        lay.add_png_record(off, a)
                     else:
                         lay.add_pixels(off, a.shape[0], a.shape[1])
                     off = (need + 15) & ~15
@@ -330,17 +356,19 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
         except BaseException as exc:                 # noqa: BLE001  (re-raised by the consumer)
             put(ready, exc)
 
-    def finished(s, e, data, lay, status, ev):
+    def finished(s, e, data, lay, status, ev, png_status=None):
         """The chunk once its statuses have arrived: the images the device declined are decoded by PIL into their slots."""
         torch.cuda.current_stream(device).wait_event(ev)
-        if status is not None:
+        if status is not None or png_status is not None:
             t0 = time.perf_counter()
             ev.synchronize()
             if stats is not None:
                 stats["status_wait_s"] = stats.get("status_wait_s", 0.0) + time.perf_counter() - t0
-            for k in np.flatnonzero(status.numpy()):
+            declined = [(lay.records[lay.status_record(k)][0], "jpeg_fallback") for k in np.flatnonzero(status.numpy())] if status is not None else []
+            if png_status is not None:
+                declined += [(lay.png_records[k][0], "png_fallback") for k in np.flatnonzero(png_status.numpy())]
+            for i, counter in declined:
                 from PIL import Image
-                i = lay.records[lay.status_record(k)][0]
                 o, h, w, _ = lay.desc[i]
                 try:
                     px = np.asarray(Image.open(paths[s + i]).convert("RGB"), dtype=np.uint8)
@@ -350,14 +378,15 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     raise DecodeError(f"cannot decode image {paths[s + i]}: PIL reads {px.shape}, its header says {(h, w, 3)}")
                 data[o:o + px.size].copy_(torch.from_numpy(px.reshape(-1).copy()))
                 if stats is not None:
-                    stats["jpeg_fallback"] = stats.get("jpeg_fallback", 0) + 1
+                    stats[counter] = stats.get(counter, 0) + 1
         return s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
 
-    with DecodePool(paths, workers, ring_bytes, world, records=bool(device_jpeg), packets=packets, progressive=progressive) as pool:
+    with DecodePool(paths, workers, ring_bytes, world, records=bool(device_jpeg), packets=packets, progressive=progressive,
+                    png=device_png) as pool:
         th = threading.Thread(target=pack, args=(pool,), daemon=True)
         th.start()
-        pending, n_chunks, pinned_status = None, 0, [None, None, None]
-        jpeg_stream = torch.cuda.Stream(device) if packets else None
+        pending, n_chunks, pinned_status, pinned_png = None, 0, [None, None, None], [None, None, None]
+        jpeg_stream = torch.cuda.Stream(device) if packets or device_png else None
         try:
             while True:
                 t_wait = time.perf_counter()
@@ -388,7 +417,9 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     stats.setdefault("h2d", []).append((t0, ev, off))
                     stats["jpeg_images"] = stats.get("jpeg_images", 0) + lay.n_jpeg
                     stats["jpeg_progressive"] = stats.get("jpeg_progressive", 0) + lay.n_progressive
-                if not packets:
+                if timed and device_png:
+                    stats["png_records"] = stats.get("png_records", 0) + lay.n_png
+                if not packets and not device_png:
                     launch_jpeg_decode(data, lay)        # (on the current stream, after the copy's event; nothing without records)
                     yield s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
                     continue
@@ -405,6 +436,13 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                             pinned_status[n_chunks % 3] = torch.empty((max(chunk, status_dev.numel()),), dtype=torch.int32).pin_memory()
                         status = pinned_status[n_chunks % 3][:status_dev.numel()]      # (at most two chunks are in flight)
                         status.copy_(status_dev, non_blocking=True)
+                    png_status = None
+                    png_dev = launch_png_decode(data, lay) if device_png else None
+                    if png_dev is not None:
+                        if pinned_png[n_chunks % 3] is None or pinned_png[n_chunks % 3].numel() < png_dev.numel():
+                            pinned_png[n_chunks % 3] = torch.empty((max(chunk, png_dev.numel()),), dtype=torch.int32).pin_memory()
+                        png_status = pinned_png[n_chunks % 3][:png_dev.numel()]
+                        png_status.copy_(png_dev, non_blocking=True)
                     sev = torch.cuda.Event()
                     sev.record(jpeg_stream)
                 data.record_stream(jpeg_stream)
@@ -412,7 +450,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                 # hand out the chunk enqueued before this one: its statuses arrived while this one was being packed
                 if pending is not None:
                     yield finished(*pending)
-                pending = (s, e, data, lay, status, sev)
+                pending = (s, e, data, lay, status, sev, png_status)
             if pending is not None:
                 yield finished(*pending)
         finally:
