@@ -940,6 +940,24 @@ int64_t lemon_png_decode_workspace_bytes(int64_t batch, int64_t total_width);
  * Returns 0 unless an argument is invalid. */
 int lemon_png_decode_host(const uint8_t *record, int64_t record_bytes, int32_t h, int32_t w, int32_t colour_type,
                           int32_t plte_count, uint8_t *rgb, int32_t *status);
+/* The inflate on the device too, opt-in (LEMON_PNG=device): the workers hand over lib/datasets/dataloader.py:177-184's file as
+ * its palette and its concatenated IDAT payload, still compressed, and the record is written here.  z_dev holds the zlib
+ * streams (z_bytes long); aux_dev (int64 [batch, 4]): stream offset, stream length, offset of the scanlines in rec_dev (record
+ * offset + 1024), and want = height * (stride + 1).  One workgroup of one wave per image (csrc/png_inflate_core.hpp): lane 0
+ * walks the codes into queues of 64 tokens, the wave stages the input, builds the tables of a dynamic block, places the tokens
+ * (matches read a 32 KiB window in LDS), copies stored blocks, writes the window through in aligned 16-byte pieces and sums the
+ * Adler-32.  status_dev int32 [batch]: 0 for a stream that is RFC 1950 / 1951 with CM = 8, CINFO <= 7, FDICT clear, yields
+ * exactly `want` bytes, ends with its final block and a matching Adler-32 and has no byte behind it -- the rule
+ * lemon_amd/png_host.py::fill_record applies with zlib; LEMON_PNG_STREAM (12) otherwise (its rows are unspecified, decode the
+ * file with PIL); LEMON_PNG_BUFFER (11) for an image whose stream or rows would leave z_bytes / rec_bytes (neither read nor
+ * written).  No status aborts the launch.  lemon_png_decode runs next on the same stream over the same rec_dev with a status
+ * array of its own; the caller takes the first non-zero of the two. */
+int lemon_png_inflate(const uint8_t *z_dev, int64_t z_bytes, int64_t batch, const int64_t *aux_dev, uint8_t *rec_dev,
+                      int64_t rec_bytes, int32_t *status_dev, void *stream);
+/* lemon_png_inflate's schedule with the lanes looped on the host -- the same code, so the same bytes and status (0 or
+ * LEMON_PNG_STREAM).  Test support for lib/datasets/dataloader.py:177-184's decode where there is no GPU; no product path calls
+ * it.  Also exported by liblemon_jpeg_host.so.  Returns 0 unless an argument is invalid. */
+int lemon_png_inflate_host(const uint8_t *z, int64_t n, uint8_t *rows, int64_t want, int32_t *status);
 
 /* ---- caption tokenizers on the device, opt-in (LEMON_TOKENIZE=device): the captions cross PCIe as raw bytes and the id matrix is
  * written where the text tower reads it.  Two vocabularies: the CLIP byte-pair encoding and BERT WordPiece.  The device serves

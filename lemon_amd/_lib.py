@@ -31,7 +31,7 @@ EXPORTS = [
     "lemon_jpeg_pack", "lemon_jpeg_entropy_device", "lemon_jpeg_entropy_workspace_bytes", "lemon_jpeg_entropy_par_host",
     "lemon_jpeg_prog_info", "lemon_jpeg_prog_entropy", "lemon_jpeg_prog_pack", "lemon_jpeg_prog_entropy_device",
     "lemon_jpeg_prog_entropy_workspace_bytes", "lemon_jpeg_prog_entropy_par_host",
-    "lemon_png_info", "lemon_png_idat", "lemon_png_decode", "lemon_png_decode_workspace_bytes", "lemon_png_decode_host",
+    "lemon_png_info", "lemon_png_idat", "lemon_png_decode", "lemon_png_decode_workspace_bytes", "lemon_png_decode_host", "lemon_png_inflate", "lemon_png_inflate_host",
     "lemon_tokenizer_create_bpe", "lemon_tokenizer_create_wordpiece", "lemon_tokenizer_free", "lemon_tokenizer_table_info",
     "lemon_tokenize", "lemon_tokenize_host",
     "lemon_hparam_search_workspace_bytes", "lemon_hparam_search", "lemon_hparam_search_host", "lemon_hparam_objective_host",
@@ -215,6 +215,8 @@ def load():
     lib.lemon_png_decode_workspace_bytes.argtypes = [c_i64, c_i64]
     lib.lemon_png_decode_workspace_bytes.restype = c_i64
     lib.lemon_png_decode_host.argtypes = [vp, c_i64] + [ctypes.c_int32] * 4 + [vp, vp]
+    lib.lemon_png_inflate.argtypes = [vp, c_i64, c_i64, vp, vp, c_i64, vp, vp]
+    lib.lemon_png_inflate_host.argtypes = [vp, c_i64, vp, c_i64, vp]
     i32 = ctypes.c_int32
     lib.lemon_tokenizer_create_bpe.argtypes = [vp, vp, vp, vp, c_i64, i32, i32, ctypes.POINTER(vp)]
     lib.lemon_tokenizer_create_wordpiece.argtypes = [vp, vp, vp, c_i64, i32, i32, i32, c_int, c_int, c_int, ctypes.POINTER(vp)]

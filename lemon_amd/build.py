@@ -14,15 +14,15 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 SO = os.path.join(HERE, "liblemon_hip.so")
 SOURCES = ["api.hip", "rowwise.hip", "knn_f32.hip", "knn_bf16.hip", "attention.hip", "attention_hd.hip", "attention_varlen.hip", "linear.hip", "preprocess.hip",
-           "gridf1.hip", "ksweep.hip", "dedup.hip", "encoder.hip", "gemm_f16x3.hip", "kmeans.hip", "jpeg.hip", "jpeg_entropy.hip", "jpeg_prog.hip", "tokenize.hip", "hparam_search.hip", "lbfgs_polish.hip", "discrepancy_ks.hip", "metric_sweep.hip", "eval_metrics.hip", "png.hip"]
+           "gridf1.hip", "ksweep.hip", "dedup.hip", "encoder.hip", "gemm_f16x3.hip", "kmeans.hip", "jpeg.hip", "jpeg_entropy.hip", "jpeg_prog.hip", "tokenize.hip", "hparam_search.hip", "lbfgs_polish.hip", "discrepancy_ks.hip", "metric_sweep.hip", "eval_metrics.hip", "png.hip", "png_inflate.hip"]
 HEADERS = ["common.hpp", "knn_common.hpp", "split3.hpp", "attention_hd64.hpp", "attention_plan.hpp", "scan_plan.hpp", "knn_wide.hpp", "knn_bf16_plan.hpp", "gemm_f16x3_plan.hpp", "jpeg_core.hpp", "jpeg_entropy.hpp", "jpeg_par.hpp", "jpeg_abi.hpp",
-           "jpeg_prog.hpp", "jpeg_prog_par.hpp", "tokenize_core.hpp", "gridf1_brent.hpp", "hparam_search_core.hpp", "lbfgs_core.hpp", "chain_dist.hpp", "discrepancy_core.hpp", "l2_from_ip_core.hpp", "index_ws.hpp", "eval_metrics_core.hpp", "png_core.hpp", "png_abi.hpp", os.path.join("..", "..", "include", "lemon_hip.h")]
+           "jpeg_prog.hpp", "jpeg_prog_par.hpp", "tokenize_core.hpp", "gridf1_brent.hpp", "hparam_search_core.hpp", "lbfgs_core.hpp", "chain_dist.hpp", "discrepancy_core.hpp", "l2_from_ip_core.hpp", "index_ws.hpp", "eval_metrics_core.hpp", "png_core.hpp", "png_abi.hpp", "png_inflate_core.hpp", os.path.join("..", "..", "include", "lemon_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # the JPEG host pass and the PNG chunk parser alone, built with the host compiler: no HIP runtime, loaded by the decode workers
 # (decode_worker.py)
 JPEG_HOST_SO = os.path.join(HERE, "liblemon_jpeg_host.so")
 JPEG_HOST_SOURCE = "jpeg_host.cpp"
-JPEG_HOST_HEADERS = ["jpeg_core.hpp", "jpeg_entropy.hpp", "jpeg_par.hpp", "jpeg_abi.hpp", "jpeg_prog.hpp", "jpeg_prog_par.hpp", "png_core.hpp", "png_abi.hpp",
+JPEG_HOST_HEADERS = ["jpeg_core.hpp", "jpeg_entropy.hpp", "jpeg_par.hpp", "jpeg_abi.hpp", "jpeg_prog.hpp", "jpeg_prog_par.hpp", "png_core.hpp", "png_abi.hpp", "png_inflate_core.hpp",
                      os.path.join("..", "..", "include", "lemon_hip.h")]
 
 

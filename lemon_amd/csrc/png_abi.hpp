@@ -4,6 +4,13 @@
 #include <vector>
 
 #include "png_core.hpp"
+#include "png_inflate_core.hpp"
+
+// The device inflate's schedule (png_inflate_core.hpp) with the lanes looped on the host: a zlib stream -> the `want` bytes of
+// filtered scanlines + status.  For tests, the fuzzer's cross-check and tools; no product path calls it.
+extern "C" int lemon_png_inflate_host(const uint8_t *z, int64_t n, uint8_t *rows, int64_t want, int32_t *status) {
+    return lemon_png_inflate_host_impl(z, n, rows, want, status);
+}
 
 extern "C" int lemon_png_info(const uint8_t *data, int64_t n, LemonPngInfo *info) {
     if (!info) return LEMON_PNG_BUFFER;

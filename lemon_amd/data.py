@@ -453,22 +453,62 @@ def launch_png_decode(data, layout, poison=None):
             status.fill_(poison)
             data[layout.png_decoded_off:].fill_(poison)
         base, vp = data.data_ptr(), ctypes.c_void_p
-        _lib.check(_lib.load().lemon_png_decode(vp(base), layout.payload_bytes, layout.n_png, vp(base + layout.png_aux_off),
+        _lib.check(_lib.load().lemon_png_decode(vp(base), layout.png_rec_end, layout.n_png, vp(base + layout.png_aux_off),
                                                 vp(work.data_ptr()), work.numel(), vp(base), data.numel(), vp(status.data_ptr()),
                                                 stream_ptr(dev)), "lemon_png_decode")
     return status
 
 
-def decode_pngs(files, device, fallback=False, poison=None):
+def launch_png_inflate(data, layout, poison=None):
+    """Enqueue lemon_png_inflate on the current stream for the PNG streams of a device buffer `data` laid out by a
+    jpeg_host.BatchLayout (add_png_stream): the filtered scanlines of lib/datasets/dataloader.py:177-184's file appear in their
+    device-only records, each behind its palette (copied from the payload for palette images), where launch_png_decode -- to be
+    called next on the same stream -- reads them.  Returns the int32 device tensor of the streams' statuses in the order of
+    layout.png_records (0, LEMON_PNG_STREAM; None without streams).  `poison` (a byte, for tests) pre-fills the records and the
+    statuses."""
+    from . import _lib
+    import ctypes
+    from .ops import stream_ptr
+    if not getattr(layout, "png_streams", None):
+        return None
+    assert data.is_cuda and data.dtype == torch.uint8 and data.numel() >= layout.total_bytes
+    dev = data.device
+    with torch.cuda.device(dev):
+        status = torch.empty((len(layout.png_streams),), dtype=torch.int32, device=dev)
+        if poison is not None:
+            status.fill_(poison)
+            data[layout.png_rec_off:layout.png_rec_end].fill_(poison)
+        base, vp = data.data_ptr(), ctypes.c_void_p
+        _lib.check(_lib.load().lemon_png_inflate(vp(base), layout.payload_bytes, len(layout.png_streams), vp(base + layout.png_zaux_off),
+                                                 vp(base), layout.png_rec_end, vp(status.data_ptr()), stream_ptr(dev)), "lemon_png_inflate")
+        for k, zoff, _, _ in layout.png_streams:
+            _, roff, _, _, ct, _ = layout.png_records[k]
+            if ct == 3:                          # (lemon_png_decode reads the palette of a palette image only)
+                data[roff:roff + 1024].copy_(data[zoff:zoff + 1024])
+    return status
+
+
+def first_png_status(inflate_status, decode_status):
+    """The verdict of a PNG that took both kernels: the inflate's where it is not zero, else the decode's (device tensors)."""
+    if inflate_status is None:
+        return decode_status
+    return torch.where(inflate_status != 0, inflate_status, decode_status)
+
+
+def decode_pngs(files, device, fallback=False, poison=None, inflate="host"):
     """Decode PNG files on the GPU -> RaggedImages of `Image.open(f).convert("RGB")`'s pixels, bit for bit
     (lib/datasets/dataloader.py:177-184).  `files`: paths or bytes objects.  The chunk walk and the inflate run here on the host
     (png_host.py), unfiltering and the expansion to RGB in lemon_png_decode; the statuses are read back once before returning.
+    inflate="device": only the chunk walk runs here (png_host.pack_stream), the files cross to the device compressed and
+    lemon_png_inflate writes their records there; a stream it declines is a declined file like any other.
     A file that is declined (16-bit, interlaced, corrupt, not a PNG, a filter byte above 4, a palette index beyond PLTE, ...)
     raises ValueError naming the status, or with fallback=True is decoded by PIL (whose own exception a corrupt file then
     raises).  The result carries `layout` (jpeg_host.BatchLayout) and `status` (int32 numpy, per PNG record)."""
     import io
     from PIL import Image
     from . import jpeg_host, png_host
+    if inflate not in ("host", "device"):
+        raise ValueError(f"inflate={inflate!r}: expected 'host' or 'device'")
     device = torch.device(device)
     if device.type != "cuda":
         raise TypeError("decode_pngs needs a CUDA/HIP device: there is no CPU path")
@@ -480,7 +520,7 @@ def decode_pngs(files, device, fallback=False, poison=None):
         raw = f if isinstance(f, (bytes, bytearray, memoryview)) else open(f, "rb").read()
         what = "<bytes>" if raw is f else f
         raw = bytes(raw)
-        rec, info = png_host.decode_record(raw)
+        rec, info = png_host.pack_stream(raw) if inflate == "device" else png_host.decode_record(raw)
         if rec is None:
             if not fallback:
                 raise declined(what, info.status)
@@ -489,7 +529,7 @@ def decode_pngs(files, device, fallback=False, poison=None):
             items.append((off, px.reshape(-1)))
             off = (off + px.nbytes + 15) & ~15
         else:
-            lay.add_png_record(off, rec)
+            (lay.add_png_stream if inflate == "device" else lay.add_png_record)(off, rec)
             sources.append((what, raw))
             items.append((off, rec.data))
             off = (off + rec.data.nbytes + 15) & ~15
@@ -502,7 +542,7 @@ def decode_pngs(files, device, fallback=False, poison=None):
         flat[lay.aux_off:lay.payload_bytes] = aux.view(np.uint8)
     data = torch.empty((max(lay.total_bytes, buf.numel()),), dtype=torch.uint8, device=device)
     data[:buf.numel()].copy_(buf, non_blocking=True)
-    status = launch_png_decode(data, lay, poison)
+    status = first_png_status(launch_png_inflate(data, lay, poison), launch_png_decode(data, lay, poison))
     st = status.cpu().numpy() if status is not None else np.zeros(0, np.int32)      # (the one read-back)
     for k in np.flatnonzero(st):
         what, raw = sources[k]

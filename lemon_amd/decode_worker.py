@@ -14,9 +14,11 @@ With PROGRESSIVE = 1 (beside RECORDS 1 or 2) a progressive file is not left to P
 
 With PNG = 1 a file that starts with the PNG signature goes through png_host (chunk walk in liblemon_jpeg_host.so, inflate by
 Python's zlib) and the ring receives its record -- palette + filtered scanlines, kind 5 -- which lemon_png_decode unfilters and
-expands to the same pixels on the GPU; a file png_host declines falls through to the PIL branch unchanged.
+expands to the same pixels on the GPU; a file png_host declines falls through to the PIL branch unchanged.  With PNG_STREAMS = 1
+(beside PNG = 1) the worker does not inflate either: after the chunk walk and the CRCs the ring receives the palette and the
+concatenated IDAT payload, still compressed -- kind 6 --, and lemon_png_inflate writes the record on the GPU.
 
-Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS [PROGRESSIVE [PNG]]]`), so that not even the lemon_amd package is imported.
+Run as a script by path (`python decode_worker.py SHM_PATH CAPACITY [RECORDS [PROGRESSIVE [PNG [PNG_STREAMS]]]]`), so that not even the lemon_amd package is imported.
 Protocol (pickled frames on stdin / stdout, in order):
   parent -> worker: ("task", seq, path) | ("free", nbytes) | ("stop",)
   worker -> parent: ("hello", pid, torch_imported)
@@ -24,7 +26,8 @@ Protocol (pickled frames on stdin / stdout, in order):
                     | ("err", seq, path, message)
 `kind` 0: nbytes = h * w * 3 of RGB pixels; `kind` 1: nbytes of coefficient record; `kind` 2: nbytes of scan packet, with
 (components, hs, vs, intervals, scan_bytes); `kind` 3: a record from the progressive host pass; `kind` 4: nbytes of progressive
-packet, with (components, hs, vs, scans, items, levels); `kind` 5: nbytes of PNG record, with (colour_type, channels, plte_count).
+packet, with (components, hs, vs, scans, items, levels); `kind` 5: nbytes of PNG record, with (colour_type, channels, plte_count);
+`kind` 6: nbytes of palette + compressed PNG stream, with (colour_type, channels, plte_count, stream bytes).
 The ring is a circular byte buffer of CAPACITY bytes.  An image is written at `offset` once `consumed` bytes (its own plus the
 unused tail skipped when it wraps) are free; the parent returns them with "free" after it has copied the image, in the order
 the results came.  An image larger than the whole ring waits until the ring is empty and goes to a one-off segment
@@ -49,6 +52,7 @@ def main(argv):
     packets = len(argv) > 2 and argv[2] == "2"
     progressive = len(argv) > 3 and argv[3] == "1"
     png = len(argv) > 4 and argv[4] == "1"
+    png_streams = png and len(argv) > 5 and argv[5] == "1"
     if records or packets or png:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     if records or packets:
@@ -104,8 +108,18 @@ def main(argv):
                 pass                    # (PIL below reports it)
             if data is not None and data[:8] == png_host.SIGNATURE:
                 head_info = png_host.info(data)
+                if png_streams and head_info.status == 0 and png_host.stream_bytes_of(head_info) + 15 <= cap:
+                    n = png_host.stream_bytes_of(head_info)
+                    off, consumed = reserve(n + 15)         # (the palette starts at a multiple of 16)
+                    at = (off + 15) & ~15
+                    png_host.fill_stream(data, head_info, view[at:at + n])
+                    head = off + n + 15
+                    used += consumed
+                    _send(out, ("ok", seq, at, head_info.height, head_info.width, consumed, None, 6, n,
+                                (head_info.colour_type, head_info.channels, head_info.plte_count, n - png_host.PALETTE_BYTES)))
+                    continue
                 n = head_info.record_bytes
-                if head_info.status == 0 and n + 15 <= cap:
+                if not png_streams and head_info.status == 0 and n + 15 <= cap:
                     off, consumed = reserve(n + 15)         # (the record starts at a multiple of 16)
                     at = (off + 15) & ~15
                     if png_host.fill_record(data, head_info, view[at:at + n]) == 0:

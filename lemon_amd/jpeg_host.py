@@ -214,17 +214,29 @@ class BatchLayout:
     were added.  `subseq`: bytes per lane of the device Huffman pass (0 = its default).
     PNG records (png_host.PngRecord, add_png_record) ride in the same payload; a batch that holds some gains, behind everything a
     JPEG-only batch holds -- whose bytes and offsets stay what they are --, the aux table of lemon_png_decode at the end of the
-    payload (png_aux_off) and the PNGs' pixels at the end of the buffer (png_decoded_off)."""
+    payload (png_aux_off) and the PNGs' pixels at the end of the buffer (png_decoded_off).
+    PNG streams (png_host.PngStream, add_png_stream: palette + compressed IDAT payload, LEMON_PNG=device) ride in the payload
+    instead of their records; their records are device-only, between everything else and the PNGs' pixels (png_rec_off ..
+    png_rec_end), written by lemon_png_inflate from its own table (png_zaux_off, behind lemon_png_decode's).  A batch's PNGs are
+    all records or all streams."""
 
     def __init__(self, subseq=0):
         self.shapes, self.desc, self.records, self.packets, self.subseq = {}, [], [], [], subseq
         self.prog_packets, self.n_progressive = [], 0
         self.png_records, self.n_png, self.png_work_bytes = [], 0, 16
+        self.png_streams = []
 
     def add_png_record(self, off, rec):
         """A PNG record (png_host.PngRecord) at payload offset `off`, a multiple of 16."""
         self.png_records.append((len(self.desc), off, rec.h, rec.w, rec.colour_type, rec.plte_count))
         self.desc.append([-1, rec.h, rec.w, self.shapes.setdefault((rec.h, rec.w), len(self.shapes))])
+
+    def add_png_stream(self, off, s):
+        """A PNG stream (png_host.PngStream) at payload offset `off`, a multiple of 16: its record's offset is known after
+        finish()."""
+        self.png_streams.append((len(self.png_records), off, s.z_bytes, 1024 + s.h * (s.w * s.channels + 1)))
+        self.png_records.append((len(self.desc), -1, s.h, s.w, s.colour_type, s.plte_count))
+        self.desc.append([-1, s.h, s.w, self.shapes.setdefault((s.h, s.w), len(self.shapes))])
 
     def add_packet(self, off, pk):
         """A scan packet at payload offset `off`: its record lies in the device-only region (offset known after finish()).
@@ -260,6 +272,9 @@ class BatchLayout:
         if self.n_png:                 # the PNG aux table: the payload's last part
             self.png_aux_off = _up(self.payload_bytes)
             self.payload_bytes = self.png_aux_off + 64 * self.n_png
+            assert len(self.png_streams) in (0, self.n_png), "a batch's PNGs are all records or all streams"
+            self.png_zaux_off = self.payload_bytes
+            self.payload_bytes += 32 * len(self.png_streams)
         # records of the packets: device-only, after the copied payload
         rec = _up(self.payload_bytes)
         self.edesc_off = self.aux_off + 8 * (8 * n + 2 * (n + 1))
@@ -304,7 +319,17 @@ class BatchLayout:
             return aux
         # the PNGs' pixels follow everything else; lemon_png_decode's table: record offset, h, w, colour type, PLTE count, output
         # offset, work offset (one uint32 per pixel of a row, include/lemon_hip.h), 0
-        self.png_decoded_off = out = _up(self.total_bytes)
+        out = _up(self.total_bytes)
+        # the streams' records, device-only; lemon_png_inflate's table: stream offset, stream bytes, offset of the scanlines, want
+        z4 = np.zeros((len(self.png_streams), 4), np.int64)
+        self.png_rec_off = out
+        for j, (k, zoff, zbytes, rbytes) in enumerate(self.png_streams):
+            i, _, h, w, ct, plte = self.png_records[k]
+            self.png_records[k] = (i, out, h, w, ct, plte)
+            z4[j] = (zoff + 1024, zbytes, out + 1024, rbytes - 1024)
+            out = _up(out + rbytes)
+        self.png_rec_end = out if self.png_streams else self.payload_bytes
+        self.png_decoded_off = out
         g8, work = np.zeros((self.n_png, 8), np.int64), 0
         for j, (i, roff, h, w, ct, plte) in enumerate(self.png_records):
             g8[j] = (roff, h, w, ct, plte, out, work, 0)
@@ -313,4 +338,4 @@ class BatchLayout:
             work += _up(4 * w)
         self.total_bytes, self.png_work_bytes = out, max(work, 16)
         pad = np.zeros((self.png_aux_off - self.aux_off) // 8 - aux.size, np.int64)      # (up to the 16-byte boundary)
-        return np.concatenate([aux, pad, g8.ravel()])
+        return np.concatenate([aux, pad, g8.ravel(), z4.ravel()])

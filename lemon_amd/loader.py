@@ -27,7 +27,7 @@ import uuid
 import numpy as np
 
 from .jpeg_host import BatchLayout, JpegPacket, JpegProgPacket, JpegProgRecord, JpegRecord
-from .png_host import PngRecord
+from .png_host import PngRecord, PngStream
 
 _WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_worker.py")
 DEFAULT_RING_BYTES = 1 << 30
@@ -73,15 +73,21 @@ def progressive_default():
 
 
 def png_default():
-    """How file batches decode PNGs: LEMON_PNG=pil (False: all by PIL in the workers) or gpu (True: chunk walk and inflate in the
-    workers, unfiltering and the expansion to RGB on the GPU).  Default pil until a recorded comparison exists (DESIGN.md
-    section 5); results are identical in both."""
+    """How file batches decode PNGs: LEMON_PNG=pil (False: all by PIL in the workers), gpu (True: chunk walk and inflate in the
+    workers, unfiltering and the expansion to RGB on the GPU) or device (True: the inflate on the GPU as well,
+    png_inflate_default()).  Default pil until a recorded comparison exists; results are identical in
+    all three."""
     env = os.environ.get("LEMON_PNG", "").strip().lower()
-    if env == "gpu":
+    if env in ("gpu", "device"):
         return True
     if env in ("", "pil"):
         return False
-    raise ValueError(f"LEMON_PNG={env!r}: expected 'pil' or 'gpu'")
+    raise ValueError(f"LEMON_PNG={env!r}: expected 'pil', 'gpu' or 'device'")
+
+
+def png_inflate_default():
+    """Whether the PNGs of file batches cross to the GPU compressed and are inflated there: LEMON_PNG=device only."""
+    return png_default() and os.environ.get("LEMON_PNG", "").strip().lower() == "device"
 
 
 def default_workers(world=1):
@@ -103,11 +109,14 @@ class DecodePool:
     file as pixels.  With packets=True a baseline JPEG whose header the packer accepts is yielded as (i, JpegPacket): its scan
     packet for lemon_jpeg_entropy_device.  progressive=True (with records or packets): a progressive JPEG is not left to PIL
     but yielded as (i, JpegProgRecord) -- the same record, from the progressive host pass -- or (i, JpegProgPacket).
-    png=True: a PNG that png_host accepts is yielded as (i, PngRecord) -- palette + filtered scanlines for lemon_png_decode."""
+    png=True: a PNG that png_host accepts is yielded as (i, PngRecord) -- palette + filtered scanlines for lemon_png_decode.
+    png_streams=True (with png): the workers do not inflate; a PNG whose chunk walk passes is yielded as (i, PngStream) -- palette
+    + compressed IDAT payload for lemon_png_inflate."""
 
     def __init__(self, paths, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, records=False, packets=False, progressive=False,
-                 png=False):
+                 png=False, png_streams=False):
         self.paths = list(paths)
+        self.png_streams = bool(png_streams) and bool(png)
         self.progressive = bool(progressive)
         self.png = bool(png)
         self.n_workers = default_workers(world) if workers is None else int(workers)
@@ -132,7 +141,8 @@ class DecodePool:
                 self.rings.append(np.frombuffer(mmap.mmap(fd, self.cap), np.uint8))
                 os.close(fd)
                 self.procs.append(subprocess.Popen([sys.executable, _WORKER, path, str(self.cap), "2" if self.packets else "1" if self.records else "0",
-                                                    "1" if self.progressive else "0"] + (["1"] if self.png else []), stdin=subprocess.PIPE,
+                                                    "1" if self.progressive else "0"] + (["1"] if self.png else []) + (["1"] if self.png_streams else []),
+                                                   stdin=subprocess.PIPE,
                                                    stdout=subprocess.PIPE, close_fds=True))
             for p in self.procs:
                 msg = self._read(p, "worker start")
@@ -169,7 +179,7 @@ class DecodePool:
                 raise DecodeError(f"cannot decode image {msg[2]}: {msg[3]}")
             _, seq, off, h, w, consumed, big, kind, n, meta = msg
             assert seq == i, (seq, i)
-            assert kind in (1, 2, 3, 4, 5) or n == h * w * 3, (kind, n, h, w)
+            assert kind in (1, 2, 3, 4, 5, 6) or n == h * w * 3, (kind, n, h, w)
             if big is not None:
                 import mmap
                 fd = os.open(big, os.O_RDONLY)
@@ -181,7 +191,7 @@ class DecodePool:
                 self.held += consumed
                 self.peak_held = max(self.peak_held, self.held)
             last = (k, consumed, big)
-            made = {1: JpegRecord, 2: JpegPacket, 3: JpegProgRecord, 4: JpegProgPacket, 5: PngRecord}.get(kind)
+            made = {1: JpegRecord, 2: JpegPacket, 3: JpegProgRecord, 4: JpegProgPacket, 5: PngRecord, 6: PngStream}.get(kind)
             yield i, (made(arr, w, h, *meta) if made else arr.reshape(h, w, 3))
         if last is not None:
             self._release(*last)
@@ -231,7 +241,7 @@ class DecodePool:
 
 
 def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAULT_RING_BYTES, world=1, stats=None, slots=3,
-                   device_jpeg=None, progressive=None, device_png=None):
+                   device_jpeg=None, progressive=None, device_png=None, png_inflate=None):
     """Yield (s, e, RaggedImages of paths[s:e]) over paths[lo:hi] in chunks of `chunk` images, decoded by a DecodePool.
 
     A packing thread copies each chunk's decoded images out of the workers' rings into one of `slots` pinned staging buffers
@@ -256,7 +266,11 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
     lemon_png_decode is enqueued behind the chunk's copy and its statuses take the route of the device Huffman pass's -- an
     asynchronous copy to pinned memory, the chunk handed out one chunk later, PIL filling the slots of the images the kernel
     declined (a filter byte above 4, a palette index beyond PLTE); stats["png_records"] counts the records, stats["png_fallback"]
-    those slots.  It composes with every `device_jpeg` mode.  The pool closes (workers exit, segments
+    those slots.  `png_inflate` (None: png_inflate_default(), LEMON_PNG=device; needs device_png): the workers deliver the PNGs
+    whose chunk walk passes as streams (palette + compressed IDAT payload); the records are allocated on the device only,
+    lemon_png_inflate writes them and lemon_png_decode runs next on the same stream; an image either kernel declines (the first
+    non-zero of the two statuses) is filled by PIL; stats["png_streams"] counts the streams.  Both compose with every
+    `device_jpeg` mode.  The pool closes (workers exit, segments
     unlinked) when the generator ends, is closed early or raises."""
     import queue
     import threading
@@ -264,12 +278,15 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
 
     import torch
 
-    from .data import RaggedImages, RaggedPlans, launch_jpeg_decode, launch_jpeg_entropy, launch_png_decode
+    from .data import RaggedImages, RaggedPlans, launch_jpeg_decode, launch_jpeg_entropy, launch_png_decode, launch_png_inflate, first_png_status
     if device_jpeg is None:
         device_jpeg = device_jpeg_default()
     if device_png is None:
         device_png = png_default()
     device_png = bool(device_png)
+    if png_inflate is None:
+        png_inflate = png_inflate_default()
+    png_inflate = bool(png_inflate) and device_png
     packets = device_jpeg == "device"
     if progressive is None:
         progressive = progressive_default()
@@ -331,7 +348,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     t1 = time.perf_counter()
                     if stats is not None:
                         stats["pool_wait_s"] = stats.get("pool_wait_s", 0.0) + t1 - t0
-                    src = a.data if isinstance(a, (JpegRecord, JpegPacket, JpegProgRecord, JpegProgPacket, PngRecord)) else a.reshape(-1)
+                    src = a.data if isinstance(a, (JpegRecord, JpegPacket, JpegProgRecord, JpegProgPacket, PngRecord, PngStream)) else a.reshape(-1)
                     need = off + src.nbytes
                     buf = room(buf, off, need)
                     np.copyto(buf.numpy()[off:need], src)
@@ -341,6 +358,8 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                         lay.add_record(off, a)
                     elif isinstance(a, PngRecord):
                         lay.add_png_record(off, a)
+                    elif isinstance(a, PngStream):
+                        lay.add_png_stream(off, a)
                     else:
                         lay.add_pixels(off, a.shape[0], a.shape[1])
                     off = (need + 15) & ~15
@@ -382,7 +401,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
         return s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
 
     with DecodePool(paths, workers, ring_bytes, world, records=bool(device_jpeg), packets=packets, progressive=progressive,
-                    png=device_png) as pool:
+                    png=device_png, png_streams=png_inflate) as pool:
         th = threading.Thread(target=pack, args=(pool,), daemon=True)
         th.start()
         pending, n_chunks, pinned_status, pinned_png = None, 0, [None, None, None], [None, None, None]
@@ -419,6 +438,8 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                     stats["jpeg_progressive"] = stats.get("jpeg_progressive", 0) + lay.n_progressive
                 if timed and device_png:
                     stats["png_records"] = stats.get("png_records", 0) + lay.n_png
+                if timed and png_inflate:
+                    stats["png_streams"] = stats.get("png_streams", 0) + len(lay.png_streams)
                 if not packets and not device_png:
                     launch_jpeg_decode(data, lay)        # (on the current stream, after the copy's event; nothing without records)
                     yield s, e, RaggedImages(data, np.array(lay.desc, np.int64).reshape(-1, 4), RaggedPlans(lay.shapes))
@@ -437,7 +458,7 @@ def ragged_batches(paths, chunk, lo, hi, device, workers=None, ring_bytes=DEFAUL
                         status = pinned_status[n_chunks % 3][:status_dev.numel()]      # (at most two chunks are in flight)
                         status.copy_(status_dev, non_blocking=True)
                     png_status = None
-                    png_dev = launch_png_decode(data, lay) if device_png else None
+                    png_dev = first_png_status(launch_png_inflate(data, lay), launch_png_decode(data, lay)) if device_png else None
                     if png_dev is not None:
                         if pinned_png[n_chunks % 3] is None or pinned_png[n_chunks % 3].numel() < png_dev.numel():
                             pinned_png[n_chunks % 3] = torch.empty((max(chunk, png_dev.numel()),), dtype=torch.int32).pin_memory()

@@ -5,7 +5,10 @@ module; the package imports it as lemon_amd.png_host.
 
 Record of an accepted file (csrc/png_core.hpp): 256 x 4 palette bytes (R, G, B, 0; zeros beyond the PLTE count), then the
 filtered scanlines exactly as inflated, each row behind its filter-type byte: 1024 + h * (w * channels + 1) bytes.  The device
-(lemon_png_decode) unfilters and expands it to RGB."""
+(lemon_png_decode) unfilters and expands it to RGB.
+
+With LEMON_PNG=device the inflate moves to the device as well (lemon_png_inflate): pack_stream does the chunk walk and the CRCs
+and hands over a PngStream -- the palette and the concatenated IDAT payload, still compressed -- and no zlib runs here."""
 import ctypes
 import os
 import zlib
@@ -36,6 +39,9 @@ class Info(ctypes.Structure):      # LemonPngInfo
 # the record of one accepted file: `data` uint8 [record_bytes] (a view; copy it to keep it)
 PngRecord = namedtuple("PngRecord", "data w h colour_type channels plte_count")
 
+# an accepted file before the inflate: `data` uint8 [1024 + z_bytes] (a view), the palette then the concatenated IDAT payload
+PngStream = namedtuple("PngStream", "data w h colour_type channels plte_count z_bytes")
+
 _lib = None
 
 
@@ -50,6 +56,7 @@ def load():
         lib.lemon_png_idat.argtypes = [ctypes.c_char_p, c_i64, vp, c_i64]
         lib.lemon_png_idat.restype = c_i64
         lib.lemon_png_decode_host.argtypes = [vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, ctypes.POINTER(c_i32)]
+        lib.lemon_png_inflate_host.argtypes = [vp, c_i64, vp, c_i64, ctypes.POINTER(c_i32)]
         _lib = lib
     return _lib
 
@@ -73,6 +80,68 @@ def idat(data, head=None):
     return memoryview(buf)[:n]
 
 
+def _fill_palette(data, head, palette):
+    palette[:PALETTE_BYTES] = 0
+    if head.plte_count:
+        pal = np.frombuffer(data, np.uint8, 3 * head.plte_count, head.plte_offset).reshape(-1, 3)
+        palette[:PALETTE_BYTES].reshape(256, 4)[:head.plte_count, :3] = pal
+
+
+def stream_bytes_of(head):
+    """Bytes of the PngStream of an accepted file: the palette and the IDAT payload."""
+    return PALETTE_BYTES + int(head.idat_bytes)
+
+
+def fill_stream(data, head, out):
+    """The palette and the concatenated IDAT payload of an accepted file into `out` (writable contiguous uint8
+    [stream_bytes_of(head)]).  No inflate: whether the payload is a zlib stream of the scanlines is the device's verdict."""
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable and out.size == stream_bytes_of(head)
+    _fill_palette(data, head, out)
+    if head.idat_spans == 1:
+        out[PALETTE_BYTES:] = np.frombuffer(data, np.uint8, int(head.idat_bytes), int(head.idat_offset))
+    elif head.idat_bytes:
+        n = load().lemon_png_idat(data, len(data), out.ctypes.data + PALETTE_BYTES, head.idat_bytes)
+        assert n == head.idat_bytes, n
+
+
+def pack_stream(data, out=None):
+    """bytes -> (PngStream, Info) or (None, Info) when the chunk walk declines the file (Info.status says why).  Chunk walk,
+    CRCs and IDAT concatenation only.  `out`: a writable contiguous uint8 array of at least 1024 + idat_bytes to write into
+    (default: a new one)."""
+    head = info(data)
+    if head.status != OK:
+        return None, head
+    n = stream_bytes_of(head)
+    if out is None:
+        out = np.empty(n, np.uint8)
+    if out.size < n:
+        head.status = BUFFER
+        return None, head
+    fill_stream(data, head, out[:n])
+    return PngStream(out[:n], head.width, head.height, head.colour_type, head.channels, head.plte_count, n - PALETTE_BYTES), head
+
+
+def record_bytes_of(s):
+    """Bytes of the record a PngStream or PngRecord inflates to: 1024 + h * (w * channels + 1)."""
+    return PALETTE_BYTES + s.h * (s.w * s.channels + 1)
+
+
+def inflate_host(stream):
+    """The device inflate's schedule on the host (csrc/png_inflate_core.hpp): PngStream -> (PngRecord, 0) or (None, STREAM).
+    For tests."""
+    rec = np.empty(record_bytes_of(stream), np.uint8)
+    src = np.ascontiguousarray(stream.data)
+    rec[:PALETTE_BYTES] = src[:PALETTE_BYTES]
+    st = ctypes.c_int32(-1)
+    rc = load().lemon_png_inflate_host(src.ctypes.data + PALETTE_BYTES, stream.z_bytes, rec.ctypes.data + PALETTE_BYTES,
+                                       rec.size - PALETTE_BYTES, ctypes.byref(st))
+    if rc != 0:
+        raise ValueError("lemon_png_inflate_host: bad arguments")
+    if st.value != OK:
+        return None, st.value
+    return PngRecord(rec, stream.w, stream.h, stream.colour_type, stream.channels, stream.plte_count), OK
+
+
 def fill_record(data, head, record):
     """Inflate the file's scanlines into `record` (writable contiguous uint8 [head.record_bytes]) behind its palette.  -> a
     status: OK, or STREAM unless the zlib stream yields exactly h * (stride + 1) bytes, ends there with no unused data and
@@ -86,10 +155,7 @@ def fill_record(data, head, record):
         return STREAM
     if len(rows) != want or not z.eof or z.unused_data or z.unconsumed_tail:
         return STREAM
-    record[:PALETTE_BYTES] = 0
-    if head.plte_count:
-        pal = np.frombuffer(data, np.uint8, 3 * head.plte_count, head.plte_offset).reshape(-1, 3)
-        record[:PALETTE_BYTES].reshape(256, 4)[:head.plte_count, :3] = pal
+    _fill_palette(data, head, record)
     record[PALETTE_BYTES:] = np.frombuffer(rows, np.uint8)
     return OK
 
